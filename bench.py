@@ -6,9 +6,12 @@ One *step* = every GPU renders its pixel tiles (32x32 tiles, tile t -> rank t % 
 sample indices, accumulating into its device-resident film; when a step completes the frame (256 indices) the
 N films are reduced to rank 0 with one RCCL reduce over xGMI and the accumulation restarts.  Per-GPU work per step is fixed (weak scaling): W*H*spp_per_step samples.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit, roofline of the dominant
-kernel (by HIP-event time; algorithmic bytes per SURVEY.md §8(d) / its average launch time),
-and the CPU baseline (the oracle's C++ restatement on host cores, bounded sample, N=1 rank 0 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps
+and prints metric/value/unit, ms_per_step, the device counters and the node-level roofline figure of the timed
+region.  `--dump-outputs DIR` also writes the film the last timed step left (DIR/film.npy).  `--full` adds what takes
+runs of its own: the roofline of the dominant kernel (by HIP-event time; algorithmic bytes per SURVEY.md §8(d) / its
+average launch time) and the per-stage times from a single-lane pass, the tile-efficiency projection, and the CPU
+baseline (the oracle's C++ restatement on host cores, bounded sample, N=1 rank 0 only).
 """
 import argparse
 import json
@@ -33,6 +36,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 # (MI355X_MICROARCH.md: "issues each VALU instruction over 2 cycles (32 lanes/cycle x 2)")
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2
 COUNTERS_DIR = ROOT / "profiles"
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: a larger film is written as a fixed seeded sample of its pixels
 
 
 def parse():
@@ -46,13 +50,18 @@ def parse():
     p.add_argument("--res", type=str, default="1920x1080")
     p.add_argument("--config", choices=["cornell", "cfg3", "cfg4", "cfg5"], default="cornell",
                    help="cornell = BASELINE configs[1] (the metric's workload); cfg3..cfg5 = configs[2..4]")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the single-lane pass (per-kernel roofline, "
+                        "stage_ms), the shard projection and the CPU baseline (each has a switch of its own below)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write the film of the last timed step to DIR/film.npy (float32)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full only: skip the CPU baseline")
     p.add_argument("--no-single-lane", action="store_true",
-                   help="profiling runs only: skip the single-lane pass (no per-kernel roofline in the line)")
+                   help="--full only, profiling runs: skip the single-lane pass (no per-kernel roofline in the line)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
     p.add_argument("--project-shards", type=int, default=8,
-                   help="N=1 only: render each of the N pixel-tile shards of an N-GPU run on this GPU alone and project "
-                        "the tile-parallel efficiency at N GPUs (0: off)")
+                   help="--full, N=1 only: render each of the N pixel-tile shards of an N-GPU run on this GPU alone and "
+                        "project the tile-parallel efficiency at N GPUs (0: off)")
     a = p.parse_args()
     if a.spp_per_step is None:
         a.spp_per_step = 16 if a.config == "cornell" else 32
@@ -336,6 +345,22 @@ def cpu_baseline(cfg, seconds):
                       f"(affinity capped by the cgroup quota), {dt:.1f} s"}
 
 
+def dump_outputs(loop, d, rank):
+    """--dump-outputs: what the last timed step left for a caller of FrameLoop.step, as DIR/film.npy ({r,g,b,w} per
+    pixel, float32): the accumulation film after that step, or, when the step completed its frame (the film was then
+    reduced, kept as `frame` and the accumulation restarted), that frame.  A film above DUMP_MAX_BYTES is written
+    as the rows of a fixed seeded sample of its pixels (seed 0: the same pixels in every run).  Rank `dst` writes."""
+    if rank != loop.dst:
+        return
+    done = loop.cursor == 0 and loop.frames_done > 0 and loop.frame is not None
+    film = (loop.frame if done else loop.film).detach().cpu().numpy().astype(np.float32, copy=False)
+    rows = DUMP_MAX_BYTES // (film.shape[1] * film.itemsize)
+    if film.shape[0] > rows:
+        film = film[np.sort(np.random.default_rng(0).choice(film.shape[0], rows, replace=False))]
+    Path(d).mkdir(parents=True, exist_ok=True)
+    np.save(Path(d) / "film.npy", np.ascontiguousarray(film))
+
+
 def main():
     a = parse()
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -376,6 +401,8 @@ def main():
     dt, total_samples = tm["dt"], tm["total"]
     st = r.stats()
     value = total_samples / dt / 1e6
+    if a.dump_outputs:
+        dump_outputs(loop, a.dump_outputs, rank)
     # roofline of the dominant kernel (most HIP-event time), from a single-lane pass (see single_lane_pass)
     # PMC bytes / VALU instructions (profiles/counters_<config>.json, tools/counters.py) are only valid for the
     # workload AND the library build they measured: they are used only when their build id is the loaded library's
@@ -394,7 +421,7 @@ def main():
     else:
         cstat = {"status": "none: traffic / valu omitted", "loaded_lib_sha16": loaded}
     roofline, st1 = {}, None
-    if rank == 0 and not a.no_single_lane:
+    if a.full and rank == 0 and not a.no_single_lane:
         st1, dt1 = single_lane_pass(cfg, world, rank, a.spp_per_step, a.steps)
         # multi-level scenes sort their bounce rays unless RTMI_SORT=0 (decided by the configuration, not by whether
         # the sort's stage events recorded time)
@@ -438,12 +465,12 @@ def main():
                                         "shadow_nodes_tested", "shadow_tris_tested", "hits", "fallback_rays",
                                         "shadow_fallback_rays")},
     }
-    if world == 1 and a.project_shards > 1:
+    if a.full and world == 1 and a.project_shards > 1:
         pj = project_shards(r, cfg, a.project_shards, a.spp_per_step, a.steps, a.warmup, stream)
         out[f"projected_tile_efficiency_{a.project_shards}"] = pj["efficiency"]
         out[f"projected_tile_efficiency_{a.project_shards}_with_reduce"] = pj["efficiency_with_reduce"]
         out["shard_projection"] = pj
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, a.cpu_seconds)
         out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
     if rank == 0:

@@ -5,7 +5,8 @@
 # An item is <variant>[+ENV=value...]; each (round, config, item) is one bench process and one line.
 # TESTS="<pytest -k expression>" or "all" runs the -m gpu suite first, once per variant in TEST_VARIANTS (default: the
 # default library), and stops there on a failure.
-cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}  # where logs and profiles land (relative to the repository root)
+cd "$(dirname "$0")/.." || exit 1; export TMPDIR=/tmp; mkdir -p "$OUT"
 export RTMI_RGBSPEC_TABLE=$PWD/computational_ray_tracer_amd/data/srgb64.rgbspec  # variants live one level deeper
 V=$PWD/computational_ray_tracer_amd/lib/variants
 if [ -n "$AB" ]; then
@@ -20,8 +21,8 @@ if [ -n "$TESTS" ]; then
   for tv in ${TEST_VARIANTS:-default}; do
     L=(); [ "$tv" != "default" ] && L=(env RTMI_LIB=$V/$tv.so)
     "${L[@]}" timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread "${K[@]}" \
-      > gpurun_out/abt_$tv.log 2>&1
-    rc=$?; echo "$tv tests rc=$rc"; tail -n 2 gpurun_out/abt_$tv.log; [ $rc -ne 0 ] && exit $rc
+      > $OUT/abt_$tv.log 2>&1
+    rc=$?; echo "$tv tests rc=$rc"; tail -n 2 $OUT/abt_$tv.log; [ $rc -ne 0 ] && exit $rc
   done
 fi
 for r in $(seq 1 ${ROUNDS:-2}); do
@@ -32,11 +33,11 @@ for r in $(seq 1 ${ROUNDS:-2}); do
       v=${item%%+*}; envs=""; [ "$item" != "$v" ] && envs=$(echo ${item#*+} | tr '+' ' ')
       tag=$(echo "${c}_${item}" | tr '/+=' '___')
       env RTMI_LIB=$V/$v.so $envs timeout -k 10 300 \
-        python bench.py --config $c --steps $s --warmup 1 --no-cpu-baseline --project-shards 0 > gpurun_out/abs_${tag}_$r.log 2>&1
-      rc=$?; [ $rc -ne 0 ] && { echo "$c $item rc=$rc"; tail -3 gpurun_out/abs_${tag}_$r.log; exit $rc; }
+        python bench.py --full --config $c --steps $s --warmup 1 --no-cpu-baseline --project-shards 0 > $OUT/abs_${tag}_$r.log 2>&1
+      rc=$?; [ $rc -ne 0 ] && { echo "$c $item rc=$rc"; tail -3 $OUT/abs_${tag}_$r.log; exit $rc; }
       python3 -c "
 import json
-d=json.loads([x for x in open('gpurun_out/abs_${tag}_$r.log') if x.startswith('{')][-1])
+d=json.loads([x for x in open('$OUT/abs_${tag}_$r.log') if x.startswith('{')][-1])
 print('round $r', '$c', '$item', d['value'], d['stage_ms'])"
     done
   done

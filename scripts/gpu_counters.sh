@@ -2,13 +2,14 @@
 # Single-lane (RTMI_LANES=1) rocprofv3 passes of bench.py per config: kernel trace + stats, FETCH_SIZE, WRITE_SIZE,
 # and the SQ instruction / stall mix — each in a run of its own (never combined with other tracing) — then
 # tools/counters.py -> profiles/counters_<config>.json and the bench line itself.
-cd "$GRAFT_REPO_ROOT"
+export OUT=${OUT:-bench_out}  # where logs and profiles land (relative to the repository root)
+cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 TAG=${TAG:-r02}
-mkdir -p gpurun_out
+mkdir -p "$OUT"
 for c in ${CONFIGS:-cornell cfg3 cfg4}; do
-  D=gpurun_out/cnt_${c}_$TAG
-  B="python3 bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline --project-shards 0"
+  D=$OUT/cnt_${c}_$TAG
+  B="python3 bench.py --full --config $c --steps 2 --warmup 1 --no-cpu-baseline --project-shards 0"
   RTMI_LANES=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $D/kt -o kt --output-format csv -- $B > $D.kt.log 2>&1
   rc=$?; echo "$c kt rc=$rc"; [ $rc -ne 0 ] && exit $rc
   RTMI_LANES=1 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -d $D/fetch -o pmc --output-format csv -- $B > $D.fetch.log 2>&1

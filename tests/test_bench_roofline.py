@@ -1,5 +1,12 @@
 """bench.py's per-kernel roofline arithmetic (CPU): algorithmic bytes per launch from the device counters, the
-sort gather fused into the multi-level trace, the NEE record, the PMC traffic ratio and the stale-counter rule."""
+sort gather fused into the multi-level trace, the NEE record, the PMC traffic ratio and the stale-counter rule;
+its options (a plain run by default, --full, --dump-outputs) and what --dump-outputs writes."""
+import sys
+import types
+
+import numpy as np
+import torch
+
 import bench
 
 
@@ -42,6 +49,42 @@ def test_no_counters_means_no_traffic_fields():
     rl = bench.kernel_rooflines(_stats(), None, "k_path_shadow")
     for v in rl.values():
         assert v.get("traffic") is None and "valu" not in v and "traffic_over_algorithmic" not in v
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (3, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def _loop(film, frame=None, cursor=16, frames_done=0):
+    return types.SimpleNamespace(film=film, frame=frame, cursor=cursor, frames_done=frames_done, dst=0)
+
+
+def test_dump_outputs_writes_the_film_of_the_last_step(tmp_path):
+    film = torch.arange(40, dtype=torch.float32).reshape(10, 4)
+    bench.dump_outputs(_loop(film), tmp_path / "mid", 0)  # mid-frame: the accumulation film
+    got = np.load(tmp_path / "mid" / "film.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, film.numpy())
+    # the step completed its frame: the film was reduced into `frame` and the accumulation restarted from zero
+    bench.dump_outputs(_loop(torch.zeros_like(film), frame=film + 1, cursor=0, frames_done=1), tmp_path / "end", 0)
+    assert np.array_equal(np.load(tmp_path / "end" / "film.npy"), film.numpy() + 1)
+    bench.dump_outputs(_loop(film), tmp_path / "other", 1)  # only rank dst writes
+    assert not (tmp_path / "other").exists()
+
+
+def test_dump_outputs_samples_a_large_film_the_same_way_every_time(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 * 100)  # room for 100 {r,g,b,w} rows
+    film = torch.arange(4 * 1000, dtype=torch.float32).reshape(1000, 4)
+    bench.dump_outputs(_loop(film), tmp_path / "a", 0)
+    bench.dump_outputs(_loop(film), tmp_path / "b", 0)
+    a, b = np.load(tmp_path / "a" / "film.npy"), np.load(tmp_path / "b" / "film.npy")
+    assert a.shape == (100, 4) and a.nbytes <= bench.DUMP_MAX_BYTES and np.array_equal(a, b)
+    rows = (a[:, 0] / 4).astype(int)  # whole rows of the film, distinct pixels in increasing order
+    assert np.array_equal(a, film.numpy()[rows]) and np.all(np.diff(rows) > 0)
 
 
 def test_effective_cpus_reads_the_cgroup_quota(tmp_path):
