@@ -23,6 +23,7 @@
 #include "../../include/rtmi355x.h"
 #include "../data/spectra_data.h"
 #include "../data/sensor_data.h"
+#include "rt_devbuf.h"
 #include "rt_guard.h"
 #include "rt_internal.h"
 
@@ -303,33 +304,23 @@ int octree_build_device(hipStream_t st, OctBuild& ob, int nt, std::string& err) 
         if (e != hipSuccess) err = std::string("octree build: ") + what + ": " + hipGetErrorString(e);
         return e == hipSuccess;
     };
-    std::vector<void*> owned;
-    auto dmalloc = [&](void** p, size_t bytes) {
-        hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) owned.push_back(*p);
-        return e;
-    };
-    struct Free {
-        std::vector<void*>& v;
-        ~Free() { for (void* p : v) hipFree(p); }
-    } free_all{owned};
     const std::vector<F3>& tri3 = *ob.tri3;
-    float* d_tri9 = nullptr;
-    int *d_ent = nullptr, *d_seg = nullptr, *d_stats = nullptr, *d_job = nullptr, *d_s0 = nullptr;
-    unsigned char* d_mask = nullptr;
-    float* d_cbox = nullptr;
-    if (!ok(dmalloc((void**)&d_tri9, sizeof(F3) * tri3.size()), "alloc") ||
-        !ok(hipMemcpyAsync(d_tri9, tri3.data(), sizeof(F3) * tri3.size(), hipMemcpyHostToDevice, st), "upload"))
+    DevBuf<float> d_tri9, d_cbox;
+    DevBuf<int> d_ent, d_next, d_seg, d_stats, d_job, d_s0;
+    DevBuf<unsigned char> d_mask;  // one mask byte per entry of the largest level
+    if (!ok(d_tri9.reserve(3 * tri3.size()), "alloc") ||
+        !ok(hipMemcpyAsync(d_tri9.get(), tri3.data(), sizeof(F3) * tri3.size(), hipMemcpyHostToDevice, st), "upload"))
         return RT_E_HIP;
+    // the per-node arrays of a level of n nodes: child boxes, segments, statistics, scatter jobs, s0
+    auto reserve_nodes = [&](size_t n) {
+        return ok(d_cbox.reserve(48 * n), "alloc") && ok(d_seg.reserve(2 * n), "alloc") &&
+               ok(d_stats.reserve(9 * n), "alloc") && ok(d_job.reserve(12 * n), "alloc") && ok(d_s0.reserve(8 * n), "alloc");
+    };
     // root pass: A_root = the triangles overlapping the root box, in insertion order
     std::vector<int> iota(nt);
     for (int t = 0; t < nt; ++t) iota[t] = t;
-    size_t cap_ent = std::max<size_t>(nt, 1), cap_nodes = 1, cap_mask = cap_ent;
-    int* d_next = nullptr;
-    if (!ok(dmalloc((void**)&d_ent, 4 * cap_ent), "alloc") || !ok(dmalloc((void**)&d_next, 4 * cap_ent), "alloc") ||
-        !ok(dmalloc((void**)&d_mask, cap_ent), "alloc") || !ok(dmalloc((void**)&d_cbox, 4 * 48), "alloc") ||
-        !ok(dmalloc((void**)&d_seg, 4 * 2), "alloc") || !ok(dmalloc((void**)&d_stats, 4 * 9), "alloc") ||
-        !ok(dmalloc((void**)&d_job, 4 * 12), "alloc") || !ok(dmalloc((void**)&d_s0, 4 * 8), "alloc"))
+    if (!ok(d_ent.reserve(nt), "alloc") || !ok(d_next.reserve(nt), "alloc") || !ok(d_mask.reserve(nt), "alloc") ||
+        !reserve_nodes(1))
         return RT_E_OOM;
     {
         float box[48];
@@ -339,13 +330,15 @@ int octree_build_device(hipStream_t st, OctBuild& ob, int nt, std::string& err) 
             box[6 * k + 3] = rmx.x; box[6 * k + 4] = rmx.y; box[6 * k + 5] = rmx.z;
         }
         int seg[2] = {0, nt}, job[12] = {0, nt, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stats[9];
-        if (!ok(hipMemcpyAsync(d_ent, iota.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st), "upload") ||
-            !ok(hipMemcpyAsync(d_cbox, box, sizeof(box), hipMemcpyHostToDevice, st), "upload") ||
-            !ok(hipMemcpyAsync(d_seg, seg, sizeof(seg), hipMemcpyHostToDevice, st), "upload") ||
-            !ok(hipMemcpyAsync(d_job, job, sizeof(job), hipMemcpyHostToDevice, st), "upload") ||
-            !ok(launch_oct_classify(st, 1, d_cbox, d_seg, d_ent, d_tri9, d_mask, d_stats), "classify") ||
-            !ok(launch_oct_scatter(st, 1, 1, d_job, d_ent, d_mask, d_next, d_s0), "scatter") ||
-            !ok(hipMemcpyAsync(stats, d_stats, sizeof(stats), hipMemcpyDeviceToHost, st), "download") ||
+        if (!ok(hipMemcpyAsync(d_ent.get(), iota.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st), "upload") ||
+            !ok(hipMemcpyAsync(d_cbox.get(), box, sizeof(box), hipMemcpyHostToDevice, st), "upload") ||
+            !ok(hipMemcpyAsync(d_seg.get(), seg, sizeof(seg), hipMemcpyHostToDevice, st), "upload") ||
+            !ok(hipMemcpyAsync(d_job.get(), job, sizeof(job), hipMemcpyHostToDevice, st), "upload") ||
+            !ok(launch_oct_classify(st, 1, d_cbox.get(), d_seg.get(), d_ent.get(), d_tri9.get(), d_mask.get(),
+                                    d_stats.get()), "classify") ||
+            !ok(launch_oct_scatter(st, 1, 1, d_job.get(), d_ent.get(), d_mask.get(), d_next.get(), d_s0.get()),
+                "scatter") ||
+            !ok(hipMemcpyAsync(stats, d_stats.get(), sizeof(stats), hipMemcpyDeviceToHost, st), "download") ||
             !ok(hipStreamSynchronize(st), "sync"))
             return RT_E_HIP;
         std::swap(d_ent, d_next);
@@ -354,7 +347,6 @@ int octree_build_device(hipStream_t st, OctBuild& ob, int nt, std::string& err) 
         std::vector<LNode> all{root};
         std::vector<std::vector<int>> level_ents;
         std::vector<int> frontier{0};
-        size_t cap_next = cap_ent;
         while (!frontier.empty()) {
             const int n = (int)frontier.size();
             std::vector<float> cbox(48 * (size_t)n);
@@ -371,32 +363,18 @@ int octree_build_device(hipStream_t st, OctBuild& ob, int nt, std::string& err) 
                 segs[2 * i] = N.begin; segs[2 * i + 1] = N.len;
                 total = std::max(total, N.begin + N.len);
             }
-            if ((size_t)n > cap_nodes) {
-                cap_nodes = 2 * (size_t)n;
-                for (void* p : {(void*)d_cbox, (void*)d_seg, (void*)d_stats, (void*)d_job, (void*)d_s0}) {
-                    hipFree(p);
-                    owned.erase(std::find(owned.begin(), owned.end(), p));
-                }
-                if (!ok(dmalloc((void**)&d_cbox, 4 * 48 * cap_nodes), "alloc") ||
-                    !ok(dmalloc((void**)&d_seg, 4 * 2 * cap_nodes), "alloc") ||
-                    !ok(dmalloc((void**)&d_stats, 4 * 9 * cap_nodes), "alloc") ||
-                    !ok(dmalloc((void**)&d_job, 4 * 12 * cap_nodes), "alloc") ||
-                    !ok(dmalloc((void**)&d_s0, 4 * 8 * cap_nodes), "alloc"))
-                    return RT_E_OOM;
-            }
-            if ((size_t)total > cap_mask) {  // one mask byte per entry of the largest level
-                cap_mask = 2 * (size_t)total;
-                hipFree(d_mask);
-                owned.erase(std::find(owned.begin(), owned.end(), (void*)d_mask));
-                if (!ok(dmalloc((void**)&d_mask, cap_mask), "alloc")) return RT_E_OOM;
-            }
+            // buffers that are too small are replaced by ones of twice the size needed
+            if ((size_t)n > d_seg.capacity() / 2 && !reserve_nodes(2 * (size_t)n)) return RT_E_OOM;
+            if ((size_t)total > d_mask.capacity() && !ok(d_mask.reserve(2 * (size_t)total), "alloc")) return RT_E_OOM;
             std::vector<int> stats(9 * (size_t)n);
             level_ents.emplace_back((size_t)total);
-            if (!ok(hipMemcpyAsync(d_cbox, cbox.data(), 4 * cbox.size(), hipMemcpyHostToDevice, st), "upload") ||
-                !ok(hipMemcpyAsync(d_seg, segs.data(), 4 * segs.size(), hipMemcpyHostToDevice, st), "upload") ||
-                !ok(launch_oct_classify(st, n, d_cbox, d_seg, d_ent, d_tri9, d_mask, d_stats), "classify") ||
-                !ok(hipMemcpyAsync(stats.data(), d_stats, 4 * stats.size(), hipMemcpyDeviceToHost, st), "download") ||
-                !ok(hipMemcpyAsync(level_ents.back().data(), d_ent, 4 * (size_t)total, hipMemcpyDeviceToHost, st),
+            if (!ok(hipMemcpyAsync(d_cbox.get(), cbox.data(), 4 * cbox.size(), hipMemcpyHostToDevice, st), "upload") ||
+                !ok(hipMemcpyAsync(d_seg.get(), segs.data(), 4 * segs.size(), hipMemcpyHostToDevice, st), "upload") ||
+                !ok(launch_oct_classify(st, n, d_cbox.get(), d_seg.get(), d_ent.get(), d_tri9.get(), d_mask.get(),
+                                        d_stats.get()), "classify") ||
+                !ok(hipMemcpyAsync(stats.data(), d_stats.get(), 4 * stats.size(), hipMemcpyDeviceToHost, st),
+                    "download") ||
+                !ok(hipMemcpyAsync(level_ents.back().data(), d_ent.get(), 4 * (size_t)total, hipMemcpyDeviceToHost, st),
                     "download") ||
                 !ok(hipStreamSynchronize(st), "sync"))
                 return RT_E_HIP;
@@ -424,22 +402,17 @@ int octree_build_device(hipStream_t st, OctBuild& ob, int nt, std::string& err) 
             }
             if (jobs.empty()) break;
             const int nj = (int)jobs.size() / 12;
-            if ((size_t)running > cap_next) {
-                cap_next = 2 * (size_t)running;
-                hipFree(d_next);
-                owned.erase(std::find(owned.begin(), owned.end(), (void*)d_next));
-                if (!ok(dmalloc((void**)&d_next, 4 * cap_next), "alloc")) return RT_E_OOM;
-            }
+            if ((size_t)running > d_next.capacity() && !ok(d_next.reserve(2 * (size_t)running), "alloc")) return RT_E_OOM;
             std::vector<int> s0(8 * (size_t)nj);
-            if (!ok(hipMemcpyAsync(d_job, jobs.data(), 4 * jobs.size(), hipMemcpyHostToDevice, st), "upload") ||
-                !ok(launch_oct_scatter(st, nj, 8, d_job, d_ent, d_mask, d_next, d_s0), "scatter") ||
-                !ok(hipMemcpyAsync(s0.data(), d_s0, 4 * s0.size(), hipMemcpyDeviceToHost, st), "download") ||
+            if (!ok(hipMemcpyAsync(d_job.get(), jobs.data(), 4 * jobs.size(), hipMemcpyHostToDevice, st), "upload") ||
+                !ok(launch_oct_scatter(st, nj, 8, d_job.get(), d_ent.get(), d_mask.get(), d_next.get(), d_s0.get()),
+                    "scatter") ||
+                !ok(hipMemcpyAsync(s0.data(), d_s0.get(), 4 * s0.size(), hipMemcpyDeviceToHost, st), "download") ||
                 !ok(hipStreamSynchronize(st), "sync"))
                 return RT_E_HIP;
             for (int j = 0; j < nj; ++j)
                 for (int c = 0; c < 8; ++c) all[next_frontier[8 * j + c]].s0 = s0[8 * (size_t)j + c];
             std::swap(d_ent, d_next);
-            std::swap(cap_ent, cap_next);
             frontier.swap(next_frontier);
         }
         // renumber: the sequential build appends a split node's 8 children when its trigger triangle is inserted
@@ -468,50 +441,138 @@ int octree_build_device(hipStream_t st, OctBuild& ob, int nt, std::string& err) 
 }
 
 // ---------------------------------------------------------------------------------------- buffers
-template <class T>
-struct DBuf {
-    T* p = nullptr;
-    size_t n = 0;
+// The regions of a lane's NEE index workspace (Batch neeSlot: one allocation, every region one queue capacity long);
+// all null without a workspace.
+struct NeeSlots {
+    int* queue = nullptr;         // the NEE queue's slots (NeeIO slot)
+    int* fallback = nullptr;      // the vertices k_path_nee's BVH walk could not decide (NeeIO fb_slot)
+    unsigned* key = nullptr;      // the NEE sort's keys at the queue positions (NeeIO key)
+    int* bin[kMatClasses] = {};   // the material bins' index lists (BinIO idx)
+    static size_t ints(size_t ncap) { return (3 + kMatClasses) * ncap; }
+    NeeSlots() = default;
+    NeeSlots(int* base, size_t ncap)
+        : queue(base), fallback(base + ncap), key(reinterpret_cast<unsigned*>(base + 2 * ncap)) {
+        for (int cl = 0; cl < kMatClasses; ++cl) bin[cl] = base + (3 + cl) * ncap;
+    }
+};
+
+// The device buffers of one batch in flight.  A lane releases them all at once — assigning an empty Batch — when its
+// queue capacity must grow or the pass changes between the path and the reference layout (ensure_workspace); the
+// sort, shadow and NEE groups are allocated on first use by the scenes that need them.
+struct Batch {
+    DevBuf<float4> ray;           // rays as interleaved (o, d) pairs: rayO = ray, rayD = ray + 1
+    DevBuf<float4> lamA, lamB;    // reference mode
+    DevBuf<float4> pdfA, pdfB, hitB;
+    DevBuf<float4> rec;           // path mode: one 128-B record per slot (rt_internal.h R_*)
+    DevBuf<int> hitPrim;
+    // coherence sort of path queues (multi-level octrees): side queue (interleaved pairs like ray), radix-sort buffers
+    DevBuf<float4> sRay;
+    DevBuf<int> sS, sVals, sValsAlt;       // sS: the sort permutation (TraceIO perm)
+    DevBuf<unsigned> sKeys, sKeysAlt;
+    DevBuf<unsigned> sQKey;                // the ray queue's sort keys at queue positions (written by the shade kernels)
+    DevBuf<unsigned char> sTemp;           // the sorts' histograms and meta (sort_temp_bytes)
+    // shadow queue (multi-level octrees): {o, tMax}, {d, slot}, pending contribution (2 x float4)
+    DevBuf<float4> shO, shD, shLA, shLB;
+    // deferred NEE of the mixed-scene shade (rt_internal.h NeeIO): records per slot, the index workspace
+    DevBuf<float4> neeRec;
+    DevBuf<int> neeSlot;
+    NeeSlots nee;                          // neeSlot's regions for the current queue capacity
+
+    float4* rayO() const { return ray.get(); }
+    float4* rayD() const { return ray.get() + 1; }
+    // slots the buffers of this layout hold (0: the other layout's, or none)
+    size_t capacity(bool path) const { return path ? rec.capacity() / kRecF4 : lamB.capacity(); }
 };
 
 }  // namespace
 
-// The device buffers of one batch in flight (grown on demand).  Path mode keeps kLanes of them so that consecutive
-// batches run concurrently on separate streams: one batch's VALU-bound traversal overlaps the other's HBM-bound
-// path-state traffic.
+// One lane: its batch buffers and the state that lives as long as the context.  Path mode keeps kLanes lanes so that
+// consecutive batches run concurrently on separate streams: one batch's VALU-bound traversal overlaps the other's
+// HBM-bound path-state traffic.
 static const int kLanes = 4;
 struct Work {
-    size_t cap = 0;
-    float4 *rayO = nullptr, *rayD = nullptr, *lamA = nullptr, *lamB = nullptr, *pdfA = nullptr, *pdfB = nullptr;
-    float4* hitB = nullptr;
-    float4* rec = nullptr;     // path mode: one 128-B record per slot (rt_internal.h R_*)
-    int* hitPrim = nullptr;
-    int* d_qcount = nullptr;   // queue q's counters at [q * kQRegion + kQLen / kQTraceTicket / ...] (rt_internal.h)
-    // coherence sort of path queues (multi-level octrees): side queue, radix-sort buffers
-    float4 *sO = nullptr, *sD = nullptr;
-    int *sS = nullptr, *sVals = nullptr, *sValsAlt = nullptr;  // sS: the sort permutation (TraceIO perm)
-    unsigned *sKeys = nullptr, *sKeysAlt = nullptr;
-    unsigned* sQKey = nullptr;  // the ray queue's sort keys at queue positions (written by the shade kernels)
-    void* sTemp = nullptr;      // the sorts' histograms and meta (sort_temp_bytes)
-    size_t sCap = 0;
-    // shadow queue (multi-level octrees): {o, tMax}, {d, slot}, pending contribution (2 x float4)
-    float4 *shO = nullptr, *shD = nullptr, *shLA = nullptr, *shLB = nullptr;
-    size_t shCap = 0;
-    // deferred NEE of the mixed-scene shade (rt_internal.h NeeIO): records per slot, the NEE queue's slots
-    float4* neeRec = nullptr;
-    int* neeSlot = nullptr;
-    size_t neeRecCap = 0, neeSlotCap = 0;  // float4s, ints
+    Batch b;
+    DevBuf<int> qcount;  // queue q's counters at [q * kQRegion + kQLen / kQTraceTicket / ...] (rt_internal.h)
     // BFS FIFO overflow ring of the multi-level traversal (qcap 0): one per lane, because the lanes' kernels run
     // concurrently and index the ring by their own global thread id
-    int* ring = nullptr;
-    size_t ring_cap = 0;   // ints
+    DevBuf<int> ring;
     // multi-level scenes in path mode: the queue positions of the rays the trace kernel's BVH walk could not decide
     // (TraceIO fb_pos; k_trace_fallback traces them with the reference BFS)
-    int* tfb = nullptr;
-    size_t tfb_cap = 0;    // ints
+    DevBuf<int> tfb;
     hipStream_t stream = nullptr;  // lanes >= 1: own stream (lane 0 runs on the caller's stream)
     hipEvent_t film_done = nullptr;
 };
+
+// The tuning and test knobs of the environment, with their defaults (INTEGRATION.md lists them): read once per
+// context, and by rt_debug_bvh_build, so the exported and the uploaded BVHs come from the same parameters.
+struct Knobs {
+    bool stage_events = true;   // per-stage HIP events (rt_stats ms_*); RTMI_NO_STAGE_EVENTS=1 turns them off
+    int lanes = kDefaultLanes;  // batches in flight in path mode (RTMI_LANES)
+    // multi-level simple path scenes: NEE rays traced by k_path_shadow (RTMI_SHADOW_QUEUE=1; measured slower than
+    // the inline any-hit, kept as a parity-tested option), depth first (RTMI_SHADOW_DFS, exact any-hit, §6)
+    int shadow_queue = 0;
+    int shadow_dfs = 1;
+    int sort_rays = 1;         // RTMI_SORT=0: no coherence sort (A/B)
+    float bvh_node_cost = 2.5f;  // SAH node cost relative to a triangle test (RTMI_BVH_CI; r04 with 64 bins: 2.5 vs 3 CFG3 +1.6 %, CFG4 +1.2 %)
+    int bvh_max_leaf = kBvhMaxLeaf;  // triangles per BVH leaf at most (RTMI_BVH_LEAF)
+    // the any-hit walks' BVH: its own (SAH node cost 2, leaves <= 4), or with RTMI_BVH_ANY="0/4" the closest-hit BVH
+    // of set 0 itself (one working set for both queries).  r04 A/B: the shared BVH made CFG4's NEE stage 7.7 % slower
+    // (30.0 vs 27.9 ms per step): the shadow rays' better tree outweighs the smaller working set
+    float bvh_any_cost = 2.f;
+    int bvh_any_leaf = 4;
+    int force_amb = -1;        // RTMI_FORCE_AMB=k (test knob, DevScene amb_force / amb_mask): -1 off
+    int coop = 1;              // RTMI_COOP=0 (test knob): undecided rays to the fallback kernels (DevScene coop_ok 0)
+    int mat_bins = 1;          // RTMI_MAT_BINS=0: mixed multi-level scenes shade every material in one kernel (A/B)
+    int emit_filter = 1;       // RTMI_EMIT_FILTER=0: the last depth of a mixed scene traces every ray (A/B)
+    int debug_path = 0;        // RTMI_DEBUG_PATH_KERNELS=1 (tests): rt_debug_trace / _occluded run path mode's kernels
+    int sort_dir_bits = 3, sort_org_bits = 3;  // sort key widths (RTMI_SORT_BITS="dir/org[/major]"; r03 A/B: 3/3 vs 3/4 CFG3 +1 %, 2/3 -4 %)
+    // origin Morton code in the key's high bits (1) or the direction (0); -1: origin-major on the simple path, whose
+    // shade kernel traces the NEE shadow rays inline (CFG3 588 -> 600), direction-major in mixed scenes, whose NEE
+    // queue has a sort of its own (CFG4 372 vs 367)
+    int sort_org_major = -1;
+    // Morton sort of the NEE queue (mixed multi-level scenes; RTMI_SORT_NEE="on[/bits]"): CFG4 337 -> 364 at 9 bits
+    // per axis (6 / 7 bits: 353 / 356; CFG5 334 -> 355 at 7)
+    int sort_nee = 1, sort_nee_bits = 8;  // (r03, device radix sort: 8 bits = 3 passes, CFG4 +1.5 % over 9 bits = 4 passes)
+    size_t batch_samples = 0;  // samples in flight per batch (0: 16 Mi single leaf, 32 Mi multi-level; RTMI_BATCH_SAMPLES)
+};
+
+static Knobs read_knobs() {
+    Knobs k;
+    if (std::getenv("RTMI_NO_STAGE_EVENTS")) k.stage_events = false;
+    if (const char* e = std::getenv("RTMI_LANES")) k.lanes = std::max(1, std::min(kLanes, std::atoi(e)));
+    if (const char* e = std::getenv("RTMI_SHADOW_QUEUE")) k.shadow_queue = std::atoi(e);
+    if (const char* e = std::getenv("RTMI_SHADOW_DFS")) k.shadow_dfs = std::atoi(e);
+    if (const char* e = std::getenv("RTMI_SORT")) k.sort_rays = std::atoi(e);
+    if (const char* e = std::getenv("RTMI_BVH_CI")) k.bvh_node_cost = (float)std::atof(e);
+    if (const char* e = std::getenv("RTMI_BVH_LEAF")) k.bvh_max_leaf = std::max(1, std::min(15, std::atoi(e)));
+    if (const char* e = std::getenv("RTMI_BVH_ANY")) {  // "cost/leaf": both fields, or the defaults stay
+        float ac;
+        int al;
+        if (std::sscanf(e, "%f/%d", &ac, &al) == 2) {
+            k.bvh_any_cost = ac;
+            k.bvh_any_leaf = std::max(1, std::min(15, al));
+        }
+    }
+    if (const char* e = std::getenv("RTMI_FORCE_AMB")) k.force_amb = std::max(-1, std::min(30, std::atoi(e)));
+    if (const char* e = std::getenv("RTMI_COOP")) k.coop = std::atoi(e) != 0;
+    if (const char* e = std::getenv("RTMI_MAT_BINS")) k.mat_bins = std::atoi(e);
+    if (const char* e = std::getenv("RTMI_EMIT_FILTER")) k.emit_filter = std::atoi(e);
+    if (const char* e = std::getenv("RTMI_DEBUG_PATH_KERNELS")) k.debug_path = std::atoi(e) != 0;
+    if (const char* e = std::getenv("RTMI_SORT_BITS")) {
+        int db = 3, ob = 4, om = -1;
+        const int got = std::sscanf(e, "%d/%d/%d", &db, &ob, &om);
+        // the key is 3 octant bits + 2 x db direction bits + 3 x ob origin bits in one u32, ob <= 9 (spread3_9)
+        if (got >= 2 && db >= 0 && db <= 9 && ob >= 0 && ob <= 9 && 3 + 2 * db + 3 * ob <= 32) {
+            k.sort_dir_bits = db;
+            k.sort_org_bits = ob;
+            if (got == 3) k.sort_org_major = om < 0 ? -1 : (om ? 1 : 0);
+        }
+    }
+    if (const char* e = std::getenv("RTMI_SORT_NEE")) std::sscanf(e, "%d/%d", &k.sort_nee, &k.sort_nee_bits);
+    k.sort_nee_bits = std::max(1, std::min(9, k.sort_nee_bits));
+    if (const char* e = std::getenv("RTMI_BATCH_SAMPLES")) k.batch_samples = (size_t)std::max(0L, std::atol(e));
+    return k;
+}
 
 struct rt_ctx {
     // coherence sort of path queues (multi-level octrees): scene quantisation of the sort key
@@ -533,59 +594,31 @@ struct rt_ctx {
     bool cull = false;
     bool scene_full = false;   // the scene needs the general path-shade kernel
     DevScene dsc{};
-    std::vector<void*> scene_allocs;
+    std::vector<DevBuf<unsigned char>> scene_allocs;  // the arrays dsc points to
     // spectra + resolve matrices
     HostSpectra hs;
-    DevSpectra* d_spec = nullptr;
+    DevBuf<DevSpectra> d_spec;
     float resolveA[9], resolveB[9];
-    float* d_resolve = nullptr;
+    DevBuf<float> d_resolve;
     // pixel work list
     int tile = 32, n_shards = 1, shard_id = 0;
     bool work_dirty = true;
     int n_work = 0;
-    int* d_work = nullptr;
-    // batch workspaces, one per lane (path mode runs kLanes batches concurrently on separate streams)
+    DevBuf<int> d_work;
+    // one workspace per lane (path mode runs up to kLanes batches concurrently on separate streams)
     Work ws[kLanes];
     bool warned_eye = false;    // check_ready: the camera-eye-beyond-oguard warning was printed
-    bool stage_events = true;   // per-stage HIP events (rt_stats ms_*); RTMI_NO_STAGE_EVENTS=1 turns them off
-    int lanes = kDefaultLanes;  // batches in flight in path mode (RTMI_LANES overrides)
-    // multi-level simple path scenes: NEE rays traced by k_path_shadow (RTMI_SHADOW_QUEUE=1; measured slower than
-    // the inline any-hit, kept as a parity-tested option), depth first (RTMI_SHADOW_DFS, exact any-hit, §6)
-    int shadow_queue = 0;
-    int shadow_dfs = 1;
-    int sort_rays = 1;         // RTMI_SORT=0: no coherence sort (A/B)
-    float bvh_node_cost = 2.5f;  // SAH node cost relative to a triangle test (RTMI_BVH_CI; r04 with 64 bins: 2.5 vs 3 CFG3 +1.6 %, CFG4 +1.2 %)
-    int bvh_max_leaf = kBvhMaxLeaf;  // triangles per BVH leaf at most (RTMI_BVH_LEAF)
+    Knobs knobs;
     int bvh_count[3][2] = {};  // per BVH (set 0, set 1, any-hit): nodes, tiles (rt_bvh_export)
-    // the any-hit walks' BVH: its own (SAH node cost 2, leaves <= 4), or with RTMI_BVH_ANY="0/4" the closest-hit BVH
-    // of set 0 itself (one working set for both queries).  r04 A/B: the shared BVH made CFG4's NEE stage 7.7 % slower
-    // (30.0 vs 27.9 ms per step): the shadow rays' better tree outweighs the smaller working set
-    float bvh_any_cost = 2.f;
-    int bvh_any_leaf = 4;
-    int force_amb = -1;        // RTMI_FORCE_AMB=k (test knob, DevScene amb_force / amb_mask): -1 off
-    int coop = 1;              // RTMI_COOP=0 (test knob): undecided rays to the fallback kernels (DevScene coop_ok 0)
-    int mat_bins = 1;          // RTMI_MAT_BINS=0: mixed multi-level scenes shade every material in one kernel (A/B)
-    int emit_filter = 1;       // RTMI_EMIT_FILTER=0: the last depth of a mixed scene traces every ray (A/B)
-    int debug_path = 0;        // RTMI_DEBUG_PATH_KERNELS=1 (tests): rt_debug_trace / _occluded run path mode's kernels
-    int sort_dir_bits = 3, sort_org_bits = 3;  // sort key widths (RTMI_SORT_BITS="dir/org[/major]"; r03 A/B: 3/3 vs 3/4 CFG3 +1 %, 2/3 -4 %)
-    // origin Morton code in the key's high bits (1) or the direction (0); -1: origin-major on the simple path, whose
-    // shade kernel traces the NEE shadow rays inline (CFG3 588 -> 600), direction-major in mixed scenes, whose NEE
-    // queue has a sort of its own (CFG4 372 vs 367)
-    int sort_org_major = -1;
-    // Morton sort of the NEE queue (mixed multi-level scenes; RTMI_SORT_NEE="on[/bits]"): CFG4 337 -> 364 at 9 bits
-    // per axis (6 / 7 bits: 353 / 356; CFG5 334 -> 355 at 7)
-    int sort_nee = 1, sort_nee_bits = 8;  // (r03, device radix sort: 8 bits = 3 passes, CFG4 +1.5 % over 9 bits = 4 passes)
     hipEvent_t done = nullptr; // recorded at the end of every pass: a later call on another stream waits for it
-    size_t batch_samples = 0;  // samples in flight per batch (0: 16 Mi single leaf, 32 Mi multi-level; RTMI_BATCH_SAMPLES)
-    unsigned long long* d_ctr = nullptr;
-    float4* d_film = nullptr;  // staging film for rt_render_pass (host film)
-    float* d_cdf = nullptr;    // Gaussian / Lanczos filter tables: x then y, cdf_n + 1 floats each
+    DevBuf<unsigned long long> d_ctr;
+    DevBuf<float4> d_film;     // staging film for rt_render_pass (host film)
+    DevBuf<float> d_cdf;       // Gaussian / Lanczos filter tables: x then y, cdf_n + 1 floats each
     int cdf_n = 0;
     int film_y_int = 0;  // the film's raster y (float division + floor) equals the integer division for every pixel
-    uint32_t* d_sobol_mats = nullptr;  // Sobol generator columns; d_sobol_fwd: fwd then inv tables for sobol_m
-    uint64_t* d_sobol_fwd = nullptr;
+    DevBuf<uint32_t> d_sobol_mats;  // Sobol generator columns; d_sobol_fwd: fwd then inv tables for sobol_m
+    DevBuf<uint64_t> d_sobol_fwd;
     int sobol_m = 0;
-    size_t film_cap = 0;
     int grid = 0;              // persistent grid size (blocks)
     // stats
     rt_stats stats{};
@@ -597,31 +630,16 @@ struct rt_ctx {
     // peers[j] on devices[j + 1]; tile t of the caller's shard goes to device (t / n_shards) mod n_devices
     std::vector<rt_ctx*> peers;
     struct PeerLink {          // on devices[0]: peer j's owned pixel ids and its compact exchange buffer
-        int* work0 = nullptr;
-        float4* xfer0 = nullptr;
-        size_t cap = 0;
+        DevBuf<int> work0;
+        DevBuf<float4> xfer0;
         int n = 0, epoch = -1;
     };
     std::vector<PeerLink> links;
     hipEvent_t gathered = nullptr;   // devices[0]: peers' pixels packed (multi-device) / peer: pass done
-    float4* xfer = nullptr;          // on a peer: its compact exchange buffer
-    size_t xfer_cap = 0;
+    DevBuf<float4> xfer;             // on a peer: its compact exchange buffer
 };
 
 namespace {
-
-// RTMI_BVH_ANY = "cost/leaf" (both fields required; anything else keeps the defaults): the any-hit BVH's SAH node cost
-// and largest leaf, cost 0 = the closest-hit BVH of set 0 itself.  One parser for rt_create and rt_debug_bvh_build, so
-// the exported and the uploaded any-hit BVHs come from the same parameters.
-void parse_bvh_any(float& cost, int& leaf) {
-    const char* e = std::getenv("RTMI_BVH_ANY");
-    float ac;
-    int al;
-    if (e && std::sscanf(e, "%f/%d", &ac, &al) == 2) {
-        cost = ac;
-        leaf = std::max(1, std::min(15, al));
-    }
-}
 
 void set_error(rt_ctx* c, const std::string& msg) {
     if (c) c->err = msg;
@@ -638,160 +656,75 @@ int fail(rt_ctx* c, int code, const std::string& msg) {
                         std::string(#call) + ": " + hipGetErrorString(_e));                               \
     } while (0)
 
-template <class T>
-hipError_t dalloc(T** p, size_t n) {
-    return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-}
-
 void free_scene(rt_ctx* c) {
-    for (void* p : c->scene_allocs) hipFree(p);
     c->scene_allocs.clear();
     c->dsc = DevScene{};
     c->have_scene = false;
 }
 
-void free_shadow_workspace(Work& w) {
-    void* ptrs[] = {w.shO, w.shD, w.shLA, w.shLB, w.neeRec, w.neeSlot};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    w.shO = w.shD = w.shLA = w.shLB = nullptr;
-    w.neeRec = nullptr;
-    w.neeSlot = nullptr;
-    w.shCap = w.neeRecCap = w.neeSlotCap = 0;
-}
-
-int ensure_nee_workspace(rt_ctx* c, Work& w, size_t rec_f4, size_t nq) {
-    if (w.neeRecCap < rec_f4) {
-        if (w.neeRec) hipFree(w.neeRec);
-        w.neeRec = nullptr;
-        w.neeRecCap = 0;
-        HIPCHK(c, dalloc(&w.neeRec, rec_f4));
-        w.neeRecCap = rec_f4;
-    }
-    if (w.neeSlotCap < nq) {
-        if (w.neeSlot) hipFree(w.neeSlot);
-        w.neeSlot = nullptr;
-        w.neeSlotCap = 0;
-        HIPCHK(c, dalloc(&w.neeSlot, nq));
-        w.neeSlotCap = nq;
-    }
+// (the NEE queue, the fallback list, the NEE sort keys: rt_internal.h NeeIO; the material bins' index lists: BinIO)
+int ensure_nee_workspace(rt_ctx* c, Batch& b, size_t rec_f4, size_t ncap) {
+    HIPCHK(c, b.neeRec.reserve(rec_f4));
+    HIPCHK(c, b.neeSlot.reserve(NeeSlots::ints(ncap)));
+    b.nee = NeeSlots(b.neeSlot.get(), ncap);
     return RT_OK;
 }
 
-int ensure_shadow_workspace(rt_ctx* c, Work& w, size_t n) {
-    if (w.shCap >= n) return RT_OK;
-    free_shadow_workspace(w);
-    HIPCHK(c, dalloc(&w.shO, n)); HIPCHK(c, dalloc(&w.shD, n));
-    HIPCHK(c, dalloc(&w.shLA, n)); HIPCHK(c, dalloc(&w.shLB, n));
-    w.shCap = n;
-    return RT_OK;
-}
-
-void free_sort_workspace(Work& w) {
-    void* ptrs[] = {w.sO, w.sS, w.sVals, w.sValsAlt, w.sKeys, w.sKeysAlt, w.sQKey, w.sTemp};  // (sD = sO + 1)
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    w.sO = w.sD = nullptr;
-    w.sS = w.sVals = w.sValsAlt = nullptr;
-    w.sKeys = w.sKeysAlt = w.sQKey = nullptr;
-    w.sTemp = nullptr;
-    w.sCap = 0;
-}
-
-int ensure_sort_workspace(rt_ctx* c, Work& w, size_t n) {
-    if (w.sCap >= n) return RT_OK;
-    free_sort_workspace(w);
-    // the side queue's rays as interleaved (o, d) pairs like the queues' (sD = sO + 1)
-    HIPCHK(c, dalloc(&w.sO, 2 * n)); w.sD = w.sO + 1; HIPCHK(c, dalloc(&w.sS, n));
-    HIPCHK(c, dalloc(&w.sVals, n)); HIPCHK(c, dalloc(&w.sValsAlt, n));
-    HIPCHK(c, dalloc(&w.sKeys, n)); HIPCHK(c, dalloc(&w.sKeysAlt, n)); HIPCHK(c, dalloc(&w.sQKey, n));
-    HIPCHK(c, hipMalloc(&w.sTemp, sort_temp_bytes()));
-    w.sCap = n;
-    return RT_OK;
-}
-
-// batch buffers only (the queue counters, stream and event of a lane live as long as the context)
-void free_workspace(Work& w) {
-    free_sort_workspace(w);
-    free_shadow_workspace(w);
-    void* ptrs[] = {w.rayO, w.lamA, w.lamB, w.pdfA, w.pdfB, w.hitB, w.rec, w.hitPrim};  // (rayD = rayO + 1)
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    w.rayO = w.rayD = w.lamA = w.lamB = w.pdfA = w.pdfB = w.hitB = w.rec = nullptr;
-    w.hitPrim = nullptr;
-    w.cap = 0;
-}
-void free_ring(Work& w) {
-    if (w.ring) hipFree(w.ring);
-    w.ring = nullptr;
-    w.ring_cap = 0;
-    if (w.tfb) hipFree(w.tfb);
-    w.tfb = nullptr;
-    w.tfb_cap = 0;
-}
-void free_workspace(rt_ctx* c) {
-    for (Work& w : c->ws) {
-        free_workspace(w);
-        free_ring(w);
+int ensure_shadow_workspace(rt_ctx* c, Batch& b, size_t n) {
+    if (b.shLB.capacity() < n) {  // allocating: a NEE workspace left by a mixed scene is given back first
+        b.neeRec.reset();
+        b.neeSlot.reset();
+        b.nee = NeeSlots{};
     }
+    HIPCHK(c, b.shO.reserve(n)); HIPCHK(c, b.shD.reserve(n));
+    HIPCHK(c, b.shLA.reserve(n)); HIPCHK(c, b.shLB.reserve(n));
+    return RT_OK;
+}
+
+int ensure_sort_workspace(rt_ctx* c, Batch& b, size_t n) {
+    HIPCHK(c, b.sRay.reserve(2 * n)); HIPCHK(c, b.sS.reserve(n));
+    HIPCHK(c, b.sVals.reserve(n)); HIPCHK(c, b.sValsAlt.reserve(n));
+    HIPCHK(c, b.sKeys.reserve(n)); HIPCHK(c, b.sKeysAlt.reserve(n)); HIPCHK(c, b.sQKey.reserve(n));
+    HIPCHK(c, b.sTemp.reserve(sort_temp_bytes()));
+    return RT_OK;
 }
 
 // this lane's BFS overflow ring (multi-level octrees whose FIFO bound exceeds the register variants)
 int ensure_ring(rt_ctx* c, Work& w) {
     if (c->dsc.qcap != 0) return RT_OK;
-    const size_t need = (size_t)c->dsc.ring_threads * (size_t)(c->dsc.ring_mask + 1);
-    if (w.ring_cap < need) {
-        free_ring(w);
-        HIPCHK(c, dalloc(&w.ring, need));
-        w.ring_cap = need;
-    }
-    return RT_OK;
-}
-// this lane's trace-fallback list (multi-level octrees, path mode): one entry per queue position at most
-int ensure_trace_fallback(rt_ctx* c, Work& w, size_t n) {
-    if (w.tfb_cap >= n) return RT_OK;
-    if (w.tfb) hipFree(w.tfb);
-    w.tfb = nullptr;
-    w.tfb_cap = 0;
-    HIPCHK(c, dalloc(&w.tfb, n));
-    w.tfb_cap = n;
+    HIPCHK(c, w.ring.reserve((size_t)c->dsc.ring_threads * (size_t)(c->dsc.ring_mask + 1)));
     return RT_OK;
 }
 // the scene as a lane's kernels see it: its own overflow ring
 DevScene lane_scene(const rt_ctx* c, const Work& w) {
     DevScene d = c->dsc;
-    d.ring = w.ring;
+    d.ring = w.ring.get();
     return d;
 }
 
 int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path) {
     int rc;
-    if (!w.d_qcount) HIPCHK(c, dalloc(&w.d_qcount, 2 * kQRegion));
-    if (&w != &c->ws[0]) {
-        if (!w.stream) HIPCHK(c, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-        if (!w.film_done) HIPCHK(c, hipEventCreateWithFlags(&w.film_done, hipEventDisableTiming));
-    } else if (!w.film_done) {
-        HIPCHK(c, hipEventCreateWithFlags(&w.film_done, hipEventDisableTiming));
-    }
+    HIPCHK(c, w.qcount.reserve(2 * kQRegion));
+    if (&w != &c->ws[0] && !w.stream) HIPCHK(c, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    if (!w.film_done) HIPCHK(c, hipEventCreateWithFlags(&w.film_done, hipEventDisableTiming));
     if ((rc = ensure_ring(c, w))) return rc;
-    if (w.cap >= n && (path ? w.rec != nullptr : w.lamA != nullptr)) return RT_OK;
-    free_workspace(w);
+    Batch& b = w.b;
+    if (b.capacity(path) >= n) return RT_OK;
+    b = Batch{};  // every batch buffer of the lane, the sort, shadow and NEE groups included
     // path mode: queue arrays hold 2 ping-pong queues of n entries each
     size_t nq = path ? 2 * n : n;
     // rays as interleaved (o, d) pairs, 32 B per ray (rayD = rayO + 1, kernels index [k << rsh] with rsh = 1): a
     // scattered read of one ray (the coherence sort's gather) touches one line instead of two
-    HIPCHK(c, dalloc(&w.rayO, 2 * nq)); w.rayD = w.rayO + 1;
-    HIPCHK(c, dalloc(&w.pdfA, n)); HIPCHK(c, dalloc(&w.pdfB, n));
-    HIPCHK(c, dalloc(&w.hitB, n)); HIPCHK(c, dalloc(&w.hitPrim, n));
+    HIPCHK(c, b.ray.reserve(2 * nq));
+    HIPCHK(c, b.pdfA.reserve(n)); HIPCHK(c, b.pdfB.reserve(n));
+    HIPCHK(c, b.hitB.reserve(n)); HIPCHK(c, b.hitPrim.reserve(n));
     if (path) {
-        HIPCHK(c, dalloc(&w.rec, (size_t)kRecF4 * n));
+        HIPCHK(c, b.rec.reserve((size_t)kRecF4 * n));
     } else {
-        HIPCHK(c, dalloc(&w.lamA, n)); HIPCHK(c, dalloc(&w.lamB, n));
+        HIPCHK(c, b.lamA.reserve(n)); HIPCHK(c, b.lamB.reserve(n));
     }
-    w.cap = n;
     return RT_OK;
 }
-int ensure_workspace(rt_ctx* c, size_t n, bool path) { return ensure_workspace(c, c->ws[0], n, path); }
 
 // Sampler dimension bookkeeping of the simple path integrator (rt_device.h Smp): every path of a depth has drawn
 // the same dimensions — the camera sample, then two Get2D per bounce — so the shade kernel takes its starting
@@ -829,7 +762,7 @@ void ev_mark(rt_ctx* c, hipStream_t st, int stage, hipEvent_t a) {
     c->pending.push_back({a, b, stage});
 }
 hipEvent_t ev_start(rt_ctx* c, hipStream_t st) {
-    if (!c->stage_events) return nullptr;
+    if (!c->knobs.stage_events) return nullptr;
     hipEvent_t a = ev_get(c);
     hipEventRecord(a, st);
     return a;
@@ -859,7 +792,7 @@ void harvest(rt_ctx* c) {
 // Owned pixels in tile order: tile_size² tiles in row-major tile order, tile t owned iff t % n == id;
 // inside a tile 8×8 micro-tiles (one wave64 = one micro-tile → coherent rays), row-major inside.
 int build_work(rt_ctx* c) {
-    if (!c->work_dirty && c->d_work) return RT_OK;
+    if (!c->work_dirty && c->d_work.get()) return RT_OK;
     int W = c->film.res_x, H = c->film.res_y, T = c->tile;
     int tx = (W + T - 1) / T, ty = (H + T - 1) / T;
     std::vector<int> px;
@@ -875,10 +808,9 @@ int build_work(rt_ctx* c) {
                         if (mx + xx < T && my + yy < T && x < W && y < H) px.push_back(y * W + x);
                     }
     }
-    if (c->d_work) hipFree(c->d_work);
-    c->d_work = nullptr;
-    HIPCHK(c, dalloc(&c->d_work, px.size()));
-    HIPCHK(c, hipMemcpy(c->d_work, px.data(), px.size() * sizeof(int), hipMemcpyHostToDevice));
+    c->d_work.reset();  // (the release waits for the queued passes that still read the old list)
+    HIPCHK(c, c->d_work.reserve(px.size()));
+    HIPCHK(c, hipMemcpy(c->d_work.get(), px.data(), px.size() * sizeof(int), hipMemcpyHostToDevice));
     c->n_work = (int)px.size();
     c->work_dirty = false;
     ++c->work_epoch;
@@ -1007,9 +939,9 @@ DevSampler dev_sampler(const rt_ctx* c) {
     s.randomize = d.randomize;
     s.sobol_m = c->sobol_m;
     s.scale = 1 << c->sobol_m;
-    s.sobol_mats = c->d_sobol_mats;
-    s.sobol_fwd = c->d_sobol_fwd;
-    s.sobol_inv = c->d_sobol_fwd ? c->d_sobol_fwd + kSobolMatrixSize : nullptr;
+    s.sobol_mats = c->d_sobol_mats.get();
+    s.sobol_fwd = c->d_sobol_fwd.get();
+    s.sobol_inv = s.sobol_fwd ? s.sobol_fwd + kSobolMatrixSize : nullptr;
     auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
     if (s.kind == RT_SAMPLER_STRATIFIED && pow2(s.xs) && pow2(s.ys)) {
         s.p2 = 1;
@@ -1023,7 +955,7 @@ DevSampler dev_sampler(const rt_ctx* c) {
 
 // sample ids of a batch starting at sample index b0 (s = i n_pixels + j)
 SampleIds sample_ids(const rt_ctx* c, int b0) {
-    SampleIds ids{c->d_work, c->n_work, b0, nullptr, nullptr};
+    SampleIds ids{c->d_work.get(), c->n_work, b0, nullptr, nullptr};
     ids.np_div = make_intdiv((uint32_t)c->n_work);
     return ids;
 }
@@ -1035,18 +967,17 @@ int ensure_sobol(rt_ctx* c) {
     v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16;
     int m = (int)std::log2((float)(v + 1));
     if (m > 16) return fail(c, RT_E_LIMIT, "Sobol sampler supports film resolutions up to 65536");
-    if (c->d_sobol_mats && c->sobol_m == m) return RT_OK;
+    if (c->d_sobol_mats.get() && c->sobol_m == m) return RT_OK;
     std::vector<uint32_t> mats;
     std::vector<uint64_t> fwd, inv;
     sobol_tables(m, mats, fwd, inv);
-    if (!c->d_sobol_mats) {
-        HIPCHK(c, hipMalloc(&c->d_sobol_mats, mats.size() * 4));
-        HIPCHK(c, hipMalloc(&c->d_sobol_fwd, 2 * kSobolMatrixSize * 8));
-    }
+    HIPCHK(c, c->d_sobol_mats.reserve(mats.size()));
+    HIPCHK(c, c->d_sobol_fwd.reserve(2 * kSobolMatrixSize));
+    uint64_t* const d_fwd = c->d_sobol_fwd.get();
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(c->d_sobol_mats, mats.data(), mats.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_sobol_fwd, fwd.data(), kSobolMatrixSize * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_sobol_fwd + kSobolMatrixSize, inv.data(), kSobolMatrixSize * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_sobol_mats.get(), mats.data(), mats.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_fwd, fwd.data(), kSobolMatrixSize * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_fwd + kSobolMatrixSize, inv.data(), kSobolMatrixSize * 8, hipMemcpyHostToDevice));
     c->sobol_m = m;
     return RT_OK;
 }
@@ -1055,23 +986,36 @@ DevFilm dev_film(const rt_ctx* c) {
     DevFilm f;
     f.res_x = d.res_x; f.res_y = d.res_y; f.filter = d.filter;
     f.rx = d.filter_radius[0]; f.ry = d.filter_radius[1]; f.imaging_ratio = d.imaging_ratio;
-    f.cdf_x = c->d_cdf;
-    f.cdf_y = c->d_cdf ? c->d_cdf + (c->cdf_n + 1) : nullptr;
+    f.cdf_x = c->d_cdf.get();
+    f.cdf_y = f.cdf_x ? f.cdf_x + (c->cdf_n + 1) : nullptr;
     f.cdf_n = c->cdf_n;
     f.rx_div = make_intdiv((uint32_t)d.res_x);
     f.y_int = c->film_y_int;
     return f;
 }
 
-ShadeRefIO shade_ref_io(rt_ctx* c) {
-    ShadeRefIO io{};
+// The reference integrator's kernel arguments over a lane's batch buffers, n samples in a queue of nsh shards
+// (render pass and rt_debug_samples).  The caller adds the shade's pixel list and film.
+struct RefIO {
+    GenOut go;
+    TraceIO tio;
+    ShadeRefIO sio;
+};
+RefIO ref_io(const rt_ctx* c, const Batch& b, int n, int nsh) {
+    RefIO r{};
+    r.go = GenOut{b.rayO(), b.rayD(), b.lamA.get(), b.lamB.get(), b.pdfA.get(), b.pdfB.get(), RecView{nullptr, 0, 0}, 0, 1};
+    r.tio = TraceIO{b.rayO(), b.rayD(), QueueView{nullptr, shard_stride(n, nsh), n, nsh}, c->cull ? 1 : 0, b.hitB.get(),
+                    b.hitPrim.get(), nullptr, 1};
+    ShadeRefIO& io = r.sio;
     io.rsh = 1;  // the workspace's interleaved rays
     float a = c->integ.albedo_rgb[0];
     io.albedo_c2 = (a - .5f) / std::sqrt(a * (1 - a));  // color.cpp:35-37
     float g = 1.0f / (2.0f * 1.0f);                      // RGBIlluminant(1,1,1): scale = 2*max = 2, rgb/scale = .5
     io.illum_c2 = (g - .5f) / std::sqrt(g * (1 - g));
     io.illum_scale = 2.0f;
-    return io;
+    io.rayD = b.rayD(); io.lamA = b.lamA.get(); io.lamB = b.lamB.get(); io.pdfA = b.pdfA.get(); io.pdfB = b.pdfB.get();
+    io.hitB = b.hitB.get(); io.hitPrim = b.hitPrim.get();
+    return r;
 }
 
 int check_ready(rt_ctx* c) {
@@ -1130,7 +1074,8 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
     // samples per path batch: 16 Mi on a single-leaf octree (8 Mi: Cornell 1874 -> 1827; flat above 16 Mi, r06_ab7),
     // 32 Mi on multi-level ones, whose fewer, fuller launches keep more rays in every wave's reach (16 -> 32 Mi: CFG3
     // +2.5 %, CFG4 +3.5 %, flat above, r06_ab23/24)
-    const size_t target = c->batch_samples ? c->batch_samples : (size_t)(c->dsc.qcap == 1 ? 16 : 32) << 20;
+    const Knobs& kn = c->knobs;
+    const size_t target = kn.batch_samples ? kn.batch_samples : (size_t)(c->dsc.qcap == 1 ? 16 : 32) << 20;
     int B = (int)std::max<size_t>(1, target / (size_t)c->n_work);
     B = std::min(B, ie - ib);
     size_t nmax = (size_t)B * c->n_work;
@@ -1139,6 +1084,8 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
     const size_t ncap = (size_t)nsh * (size_t)shard_stride((int)nmax, nsh);
     DevCamera cam = dev_camera(c->cam);
     DevFilm fd = dev_film(c);
+    const DevSpectra* const d_spec = c->d_spec.get();
+    unsigned long long* const d_ctr = c->d_ctr.get();
     if (!path) {
         Work& w = c->ws[0];
         if ((rc = ensure_workspace(c, w, ncap, false))) return rc;
@@ -1146,21 +1093,17 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
             int nIdx = std::min(B, ie - b0);
             int nS = nIdx * c->n_work;
             SampleIds ids = sample_ids(c, b0);
-            GenOut go{w.rayO, w.rayD, w.lamA, w.lamB, w.pdfA, w.pdfB, RecView{nullptr, 0, 0}, 0, 1};
+            RefIO r = ref_io(c, w.b, nS, nsh);
             hipEvent_t e0 = ev_start(c, st);
-            HIPCHK(c, launch_generate(st, c->grid, nS, ids, cam, smp, fd, go));
+            HIPCHK(c, launch_generate(st, c->grid, nS, ids, cam, smp, fd, r.go));
             ev_mark(c, st, ST_GEN, e0);
-            TraceIO tio{w.rayO, w.rayD, QueueView{nullptr, shard_stride(nS, nsh), nS, nsh}, c->cull ? 1 : 0, w.hitB, w.hitPrim,
-                        nullptr, 1};
             e0 = ev_start(c, st);
-            HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), tio, c->d_ctr));
+            HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), r.tio, d_ctr));
             ev_mark(c, st, ST_TRACE, e0);
-            ShadeRefIO sio = shade_ref_io(c);
-            sio.work_pixels = c->d_work; sio.n_pixels = c->n_work; sio.n_index = nIdx;
-            sio.rayD = w.rayD; sio.lamA = w.lamA; sio.lamB = w.lamB; sio.pdfA = w.pdfA; sio.pdfB = w.pdfB;
-            sio.hitB = w.hitB; sio.hitPrim = w.hitPrim; sio.film = film;
+            r.sio.work_pixels = c->d_work.get(); r.sio.n_pixels = c->n_work; r.sio.n_index = nIdx;
+            r.sio.film = film;
             e0 = ev_start(c, st);
-            HIPCHK(c, launch_ref_shade_film(st, 0, c->dsc, c->d_spec, fd, sio, c->d_ctr));
+            HIPCHK(c, launch_ref_shade_film(st, 0, c->dsc, d_spec, fd, r.sio, d_ctr));
             ev_mark(c, st, ST_FILM, e0);
         }
         return RT_OK;
@@ -1170,14 +1113,15 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
     // Within a lane everything is stream-ordered; across lanes only the film kernels are chained (batch k's film
     // after batch k-1's), so every pixel still adds its sample indices in increasing order.
     const int nbatch = (ie - ib + B - 1) / B;
-    const int lanes = std::max(1, std::min(std::min(c->lanes, kLanes), nbatch));
+    const int lanes = std::max(1, std::min(std::min(kn.lanes, kLanes), nbatch));
     // multi-level octrees: coherence-sort each bounce's rays (rt_sort.hip); on the single-leaf Cornell box the sort
     // costs more than it saves (1110 -> 720 Msamples/s)
-    const bool sort_rays = c->dsc.qcap != 1 && c->sort_rays;
+    const bool sort_rays = c->dsc.qcap != 1 && kn.sort_rays;
     for (int l = 0; l < lanes; ++l) {
         if ((rc = ensure_workspace(c, c->ws[l], ncap, true))) return rc;
-        if (sort_rays && (rc = ensure_sort_workspace(c, c->ws[l], ncap))) return rc;
-        if (c->dsc.qcap != 1 && (rc = ensure_trace_fallback(c, c->ws[l], ncap))) return rc;
+        if (sort_rays && (rc = ensure_sort_workspace(c, c->ws[l].b, ncap))) return rc;
+        // the trace-fallback list (multi-level octrees): one entry per queue position at most
+        if (c->dsc.qcap != 1) HIPCHK(c, c->ws[l].tfb.reserve(ncap));
     }
     // Cornell-like single-leaf scenes cost the same per ray: static chunks on a resident grid beat tickets there
     // (A/B 1229 vs 1106-1158 Msamples/s); multi-level octrees vary per ray by 100x: tickets (CFG3 71 -> 96)
@@ -1192,18 +1136,15 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
     const bool shq = c->dsc.qcap != 1 && !c->dsc.full;
     if (shq)
         for (int l = 0; l < lanes; ++l)
-            if ((rc = ensure_shadow_workspace(c, c->ws[l], ncap))) return rc;
+            if ((rc = ensure_shadow_workspace(c, c->ws[l].b, ncap))) return rc;
     // mixed scenes: NEE deferred to k_path_nee (one record per slot, one queue entry per Lambert vertex)
     const bool nee = c->dsc.full && c->dsc.n_lights > 0;
     if (nee)
         for (int l = 0; l < lanes; ++l)
-            if ((rc = ensure_nee_workspace(c, c->ws[l], nmax * (size_t)nee_stride(c->dsc.n_lights),
-                                           (3 + kMatClasses) * (size_t)ncap)))
-                return rc;  // (the NEE queue, the fallback list, the NEE sort keys: rt_internal.h NeeIO; the
-                            // material bins' index lists: TraceIO bin_idx)
+            if ((rc = ensure_nee_workspace(c, c->ws[l].b, nmax * (size_t)nee_stride(c->dsc.n_lights), ncap))) return rc;
     // mixed multi-level scenes: the trace kernel bins the hits by material class and each class is shaded by a kernel
     // holding only its materials' code (k_path_shade_full<Q, 1 / 2>)
-    const bool bins = nee && c->dsc.qcap != 1 && c->mat_bins;
+    const bool bins = nee && c->dsc.qcap != 1 && kn.mat_bins;
     // Concurrent lanes share the CUs.  Each launch still asks for every resident block (grid_div 1): the dispatcher
     // hands blocks to whichever lane's kernel has them pending, so a VALU-bound trace and an HBM-bound shade of the
     // other lane end up co-resident (Cornell A/B: 1 lane 1217, 2 lanes with half grids 1422, with full grids 1500)
@@ -1227,18 +1168,19 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
             int b0 = g0 + l * B;
             if (b0 >= ie) break;
             Work& w = c->ws[l];
+            const Batch& b = w.b;
             hipStream_t s = lstream(l);
-            const RecView rv{w.rec, rec_fs, rec_ss, rec_rng8};
+            const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
             nIdx[l] = std::min(B, ie - b0);
             int nS = nIdx[l] * c->n_work;
             nSq[l] = nS;
             Sq[l] = shard_stride(nS, nsh);  // every queue of this batch: shard j at [j S, j S + len_j)
             SampleIds ids = sample_ids(c, b0);
-            GenOut go{w.rayO, w.rayD, nullptr, nullptr, w.pdfA, w.pdfB, rv, lean, 1};
+            GenOut go{b.rayO(), b.rayD(), nullptr, nullptr, b.pdfA.get(), b.pdfB.get(), rv, lean, 1};
             // camera rays fill queue 0 densely (positions 0..nS-1: QueueView without lengths); both counter regions
             // start at zero: k_generate zeroes them (a memset launch here waited for the other lane's resident blocks
             // in two-lane mode, r05 kernel traces)
-            go.zero = w.d_qcount;
+            go.zero = w.qcount.get();
             hipEvent_t e0 = ev_start(c, s);
             HIPCHK(c, launch_generate(s, grid, nS, ids, cam, smp, fd, go));
             ev_mark(c, s, ST_GEN, e0);
@@ -1248,20 +1190,24 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
             if (depth == c->integ.max_depth && depth > 0 && !c->dsc.full) break;
             for (int l = 0; l < lanes && nIdx[l] > 0; ++l) {
                 Work& w = c->ws[l];
+                const Batch& b = w.b;
                 hipStream_t s = lstream(l);
-                const RecView rv{w.rec, rec_fs, rec_ss, rec_rng8};
+                const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
                 SampleIds ids = sample_ids(c, g0 + l * B);
                 int nxt = cur[l] ^ 1;
-                const float4* cO = w.rayO + 2 * (size_t)cur[l] * qs;
+                const float4* cO = b.rayO() + 2 * (size_t)cur[l] * qs;
                 const float4* cD = cO + 1;
-                int* qc_cur = w.d_qcount + kQRegion * cur[l];
-                int* qc_nxt = w.d_qcount + kQRegion * nxt;
+                int* qc_cur = w.qcount.get() + kQRegion * cur[l];
+                int* qc_nxt = w.qcount.get() + kQRegion * nxt;
+                // the last depth of a mixed scene: only emitter hits still add to L, so the rays that hit no emissive
+                // surface are dropped first (k_emitter_filter, EmitIO) into the free next queue, whose rays the trace
+                // and shade kernels then take (the shade appends nothing at this depth); no coherence sort
+                const bool efilter = kn.emit_filter && c->dsc.full && depth == c->integ.max_depth && depth > 0 &&
+                                     c->dsc.n_emit_tris >= 0;
                 // the next queue's length and the chunk tickets its trace and shade launches will use start at zero:
                 // depth 0 (k_generate zeroed both regions) / the trace kernel zeroes it (below), except before the
                 // emitter filter, which appends to it ahead of the trace
-                const bool efilter0 = c->emit_filter && c->dsc.full && depth == c->integ.max_depth && depth > 0 &&
-                                      c->dsc.n_emit_tris >= 0;
-                if (efilter0) HIPCHK(c, hipMemsetAsync(qc_nxt, 0, kQRegion * sizeof(int), s));
+                if (efilter) HIPCHK(c, hipMemsetAsync(qc_nxt, 0, kQRegion * sizeof(int), s));
                 hipEvent_t e0;
                 // multi-level octrees: bounce rays sorted by (octant, direction cell, origin Morton code) before
                 // the trace.  The queue length is read back so only live rays are sorted (sorting the capacity with
@@ -1269,13 +1215,8 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
                 QueueView qv = depth == 0 ? QueueView{nullptr, Sq[l], nSq[l], nsh}
                                           : QueueView{qc_cur + kQLen, Sq[l], 0, nsh};
                 const DevScene dsl = lane_scene(c, w);
-                // the last depth of a mixed scene: only emitter hits still add to L, so the rays that hit no emissive
-                // surface are dropped first (k_emitter_filter, EmitIO) into the free next queue, whose rays the trace
-                // and shade kernels then take (the shade appends nothing at this depth); no coherence sort
-                const bool efilter = c->emit_filter && c->dsc.full && depth == c->integ.max_depth && depth > 0 &&
-                                     c->dsc.n_emit_tris >= 0;
                 if (efilter) {
-                    const EmitIO eio{qv, cO, w.rayO + 2 * (size_t)nxt * qs, qc_nxt + kQLen};
+                    const EmitIO eio{qv, cO, b.rayO() + 2 * (size_t)nxt * qs, qc_nxt + kQLen};
                     e0 = ev_start(c, s);
                     HIPCHK(c, launch_emitter_filter(s, grid, dsl, eio));
                     ev_mark(c, s, ST_FILTER, e0);
@@ -1283,40 +1224,42 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
                     cD = cO + 1;
                     qv = QueueView{qc_nxt + kQLen, Sq[l], 0, nsh};
                 }
-                TraceIO tio{cO, cD, qv, 0, w.hitB, w.hitPrim, dyn ? qc_cur + kQTraceTicket : nullptr, 1};
+                TraceIO tio{cO, cD, qv, 0, b.hitB.get(), b.hitPrim.get(), dyn ? qc_cur + kQTraceTicket : nullptr, 1};
                 if (depth > 0 && !efilter) tio.zero = qc_nxt;
                 if (c->dsc.qcap != 1) {  // ambiguous rays listed for k_trace_fallback (the trace holds no BFS)
-                    tio.fb_pos = w.tfb;
+                    tio.fb_pos = w.tfb.get();
                     tio.fb_len = qc_cur + kQTraceFallback;
                 }
-                BinIO bio{qv, w.hitPrim, {w.neeSlot + 3 * ncap, w.neeSlot + 4 * ncap}, qc_cur + kQBinLen};
+                const NeeSlots ns = nee ? b.nee : NeeSlots{};
+                BinIO bio{qv, b.hitPrim.get(), {}, qc_cur + kQBinLen};
+                for (int cl = 0; cl < kMatClasses; ++cl) bio.idx[cl] = ns.bin[cl];
                 if (depth == 0) { bio.rayO = cO; bio.rec = rv; }  // lean depth 0: the misses' L = 0 (BinIO)
-                static_assert(kMatClasses == 2, "bin index lists");
                 if (sort_rays && depth > 0 && !efilter) {  // the device reads the queue length itself: no host read
-                    SortRaysIO so{w.sQKey, w.sS, w.sKeys, w.sKeysAlt, w.sVals, w.sValsAlt, w.sTemp,
-                                  c->sort_dir_bits, c->sort_org_bits, qc_cur + kQLen, Sq[l]};
+                    SortRaysIO so{b.sQKey.get(), b.sS.get(), b.sKeys.get(), b.sKeysAlt.get(), b.sVals.get(),
+                                  b.sValsAlt.get(), b.sTemp.get(), kn.sort_dir_bits, kn.sort_org_bits, qc_cur + kQLen,
+                                  Sq[l]};
                     e0 = ev_start(c, s);
                     HIPCHK(c, launch_sort_rays(s, so));
                     ev_mark(c, s, ST_SORT, e0);
-                    tio.perm = w.sS;  // the trace kernel gathers the sorted rays into the side queue
-                    tio.so = w.sO;
-                    cO = w.sO; cD = w.sD;
+                    tio.perm = b.sS.get();  // the trace kernel gathers the sorted rays into the side queue
+                    tio.so = b.sRay.get();
+                    cO = tio.so; cD = cO + 1;
                 }
                 e0 = ev_start(c, s);
-                HIPCHK(c, launch_trace_closest(s, grid, c->dsc.qcap, dsl, tio, c->d_ctr));
+                HIPCHK(c, launch_trace_closest(s, grid, c->dsc.qcap, dsl, tio, d_ctr));
                 // (an ambiguous ray is listed only if the cooperative BFS's FIFO overflows, which the octree's exact
                 // queue bound excludes when coop_ok: then no launch, which in two-lane mode would wait for the other
                 // lane's resident blocks, r05 kernel traces: 1.28 ms per bounce)
                 if (tio.fb_pos && !c->dsc.coop_ok)
-                    HIPCHK(c, launch_trace_fallback(s, grid, c->dsc.qcap, dsl, tio, c->d_ctr));
+                    HIPCHK(c, launch_trace_fallback(s, grid, c->dsc.qcap, dsl, tio, d_ctr));
                 ev_mark(c, s, ST_TRACE, e0);
                 PathIO pio{};
                 pio.lean = lean;
                 pio.rayO = cO; pio.rayD = cD; pio.q = qv;
-                pio.hitB = w.hitB; pio.hitPrim = w.hitPrim;
-                pio.nO = w.rayO + 2 * (size_t)nxt * qs; pio.nD = pio.nO + 1;
+                pio.hitB = b.hitB.get(); pio.hitPrim = b.hitPrim.get();
+                pio.nO = b.rayO() + 2 * (size_t)nxt * qs; pio.nD = pio.nO + 1;
                 pio.nCount = qc_nxt + kQLen;
-                pio.rec = rv; pio.pdfA = w.pdfA; pio.pdfB = w.pdfB;
+                pio.rec = rv; pio.pdfA = b.pdfA.get(); pio.pdfB = b.pdfB.get();
                 pio.depth = depth; pio.max_depth = c->integ.max_depth;
                 pio.dim = -1;
                 if (lean == 1) {
@@ -1325,27 +1268,26 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
                 }
                 pio.ticket = dyn ? qc_cur + kQShadeTicket : nullptr;
                 if (sort_rays && depth < c->integ.max_depth) {  // keys of the rays this shade appends (next sort)
-                    pio.nkey.key = w.sQKey;
+                    pio.nkey.key = b.sQKey.get();
                     pio.nkey.lo = c->sort_lo;
                     pio.nkey.scale = c->sort_scale;
-                    pio.nkey.dir_bits = c->sort_dir_bits;
-                    pio.nkey.org_bits = c->sort_org_bits;
-                    pio.nkey.org_major = c->sort_org_major >= 0 ? c->sort_org_major : (c->dsc.full ? 0 : 1);
+                    pio.nkey.dir_bits = kn.sort_dir_bits;
+                    pio.nkey.org_bits = kn.sort_org_bits;
+                    pio.nkey.org_major = kn.sort_org_major >= 0 ? kn.sort_org_major : (c->dsc.full ? 0 : 1);
                 }
                 ShadowQueueIO sqio{};
                 if (shq) {  // this queue's region holds the shadow-queue length and ticket (zeroed with it)
-                    sqio.shO = w.shO; sqio.shD = w.shD; sqio.shLA = w.shLA; sqio.shLB = w.shLB;
+                    sqio.shO = b.shO.get(); sqio.shD = b.shD.get(); sqio.shLA = b.shLA.get(); sqio.shLB = b.shLB.get();
                     sqio.shCount = qc_cur + kQShadowLen;
                     sqio.shTicket = qc_cur + kQShadowTicket;
-                    sqio.defer = c->shadow_queue ? 0 : 1;
+                    sqio.defer = kn.shadow_queue ? 0 : 1;
                 }
                 NeeIO nio{};
-                const bool sort_nee = nee && sort_rays && c->sort_nee;
-                unsigned* nee_key = reinterpret_cast<unsigned*>(w.neeSlot + 2 * ncap);
+                const bool sort_nee = nee && sort_rays && kn.sort_nee;
                 if (nee)
-                    nio = NeeIO{w.neeRec, w.neeSlot, qc_cur + kQShadowLen, qc_cur + kQShadowTicket, w.neeSlot + ncap,
-                                qc_cur + kQNeeFallback, sort_nee ? nee_key : nullptr, c->sort_lo, c->sort_scale,
-                                c->sort_nee_bits};
+                    nio = NeeIO{b.neeRec.get(), ns.queue, qc_cur + kQShadowLen, qc_cur + kQShadowTicket, ns.fallback,
+                                qc_cur + kQNeeFallback, sort_nee ? ns.key : nullptr, c->sort_lo, c->sort_scale,
+                                kn.sort_nee_bits};
                 e0 = ev_start(c, s);
                 if (bins) {  // the hits binned by material, then one kernel per bin over its index list
                     HIPCHK(c, launch_bin_materials(s, grid, dsl, bio));
@@ -1354,34 +1296,34 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
                         bp.q = QueueView{qc_cur + kQBinLen + cl * kShards * kQStride, Sq[l], 0, nsh};
                         bp.ticket = qc_cur + kQBinTicket + cl * kShards * kQStride;
                         bp.bin_idx = bio.idx[cl];
-                        HIPCHK(c, launch_path_shade(s, grid, c->dsc.qcap, dsl, c->d_spec, smp, fd, ids, bp, c->d_ctr,
+                        HIPCHK(c, launch_path_shade(s, grid, c->dsc.qcap, dsl, d_spec, smp, fd, ids, bp, d_ctr,
                                                     sqio, nio, 1 + cl));
                     }
                 } else {
-                    HIPCHK(c, launch_path_shade(s, grid, c->dsc.qcap, dsl, c->d_spec, smp, fd, ids, pio, c->d_ctr, sqio,
+                    HIPCHK(c, launch_path_shade(s, grid, c->dsc.qcap, dsl, d_spec, smp, fd, ids, pio, d_ctr, sqio,
                                                 nio));
                 }
                 ev_mark(c, s, ST_SHADE, e0);
                 if (sort_nee) {  // NEE vertices in Morton order of their shading points (no host round trip)
-                    SortNeeIO so{w.neeSlot, qc_cur + kQShadowLen, Sq[l], nee_key, w.sKeys, w.sKeysAlt, w.sVals,
-                                 w.sValsAlt, w.sTemp, c->sort_nee_bits};
+                    SortNeeIO so{ns.queue, qc_cur + kQShadowLen, Sq[l], ns.key, b.sKeys.get(), b.sKeysAlt.get(),
+                                 b.sVals.get(), b.sValsAlt.get(), b.sTemp.get(), kn.sort_nee_bits};
                     e0 = ev_start(c, s);
                     HIPCHK(c, launch_sort_nee(s, so));
                     ev_mark(c, s, ST_SORT, e0);
                 }
                 if (nee) {  // this bounce's shadow rays, before the next bounce reads L
                     e0 = ev_start(c, s);
-                    HIPCHK(c, launch_path_nee(s, grid, c->dsc.qcap, dsl, c->d_spec, pio, nio, c->d_ctr));
+                    HIPCHK(c, launch_path_nee(s, grid, c->dsc.qcap, dsl, d_spec, pio, nio, d_ctr));
                     // (no fallback launch when k_path_nee resolves its undecided shadow rays itself, coop_ok)
                     if (c->dsc.qcap != 1 && !c->dsc.coop_ok)
-                        HIPCHK(c, launch_path_nee_fallback(s, grid, c->dsc.qcap, dsl, c->d_spec, pio, nio, c->d_ctr));
+                        HIPCHK(c, launch_path_nee_fallback(s, grid, c->dsc.qcap, dsl, d_spec, pio, nio, d_ctr));
                     ev_mark(c, s, ST_SHADOW, e0);
                 }
                 // (the deferred shadow rays are resolved in k_path_shade itself when coop_ok: no launch, which in
                 // two-lane mode waits for the other lane's resident blocks, r05 kernel traces: 0.87 ms per bounce)
                 if (shq && !(sqio.defer && c->dsc.coop_ok)) {
                     e0 = ev_start(c, s);
-                    HIPCHK(c, launch_path_shadow(s, grid, c->dsc.qcap, c->shadow_dfs != 0, dsl, pio, sqio, c->d_ctr));
+                    HIPCHK(c, launch_path_shadow(s, grid, c->dsc.qcap, kn.shadow_dfs != 0, dsl, pio, sqio, d_ctr));
                     ev_mark(c, s, ST_SHADOW, e0);
                 }
                 cur[l] = nxt;
@@ -1389,13 +1331,14 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
         }
         for (int l = 0; l < lanes && nIdx[l] > 0; ++l) {
             Work& w = c->ws[l];
+            const Batch& b = w.b;
             hipStream_t s = lstream(l);
-            const RecView rv{w.rec, rec_fs, rec_ss, rec_rng8};
+            const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
             if (last_film >= 0 && last_film != l) HIPCHK(c, hipStreamWaitEvent(s, c->ws[last_film].film_done, 0));
-            PathFilmIO fio{c->d_work, c->n_work, nIdx[l], rv, w.pdfA, w.pdfB, film};
+            PathFilmIO fio{c->d_work.get(), c->n_work, nIdx[l], rv, b.pdfA.get(), b.pdfB.get(), film};
             fio.lean = lean;
             hipEvent_t e0 = ev_start(c, s);
-            HIPCHK(c, launch_path_film(s, 0, c->d_spec, fd, fio, c->d_ctr));
+            HIPCHK(c, launch_path_film(s, 0, d_spec, fd, fio, d_ctr));
             ev_mark(c, s, ST_FILM, e0);
             HIPCHK(c, hipEventRecord(w.film_done, s));
             last_film = l;
@@ -1532,8 +1475,8 @@ int setup_sensor(rt_ctx* c, const rt_film_desc& d) {
     float both[18];
     std::memcpy(both, c->resolveA, 36);
     std::memcpy(both + 9, c->resolveB, 36);
-    char* base = (char*)c->d_spec;
-    if (hipMemcpy(c->d_resolve, both, sizeof(both), hipMemcpyHostToDevice) != hipSuccess ||
+    char* base = (char*)c->d_spec.get();
+    if (hipMemcpy(c->d_resolve.get(), both, sizeof(both), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(base + offsetof(DevSpectra, SR), bars[0].v.data(), 4 * kSpecN, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(base + offsetof(DevSpectra, SG), bars[1].v.data(), 4 * kSpecN, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(base + offsetof(DevSpectra, SB), bars[2].v.data(), 4 * kSpecN, hipMemcpyHostToDevice) != hipSuccess)
@@ -1559,30 +1502,13 @@ int peer_prepare(rt_ctx* c, size_t j) {
     int rc = build_work(p);
     if (rc) return fail(c, rc, "device " + std::to_string(p->device) + ": " + p->err);
     size_t n = (size_t)p->film.res_x * p->film.res_y;
-    if (p->film_cap < n) {
-        if (p->d_film) hipFree(p->d_film);
-        p->d_film = nullptr;
-        HIPCHK(c, dalloc(&p->d_film, n));
-        p->film_cap = n;
-    }
-    if (p->xfer_cap < (size_t)p->n_work) {
-        if (p->xfer) hipFree(p->xfer);
-        p->xfer = nullptr;
-        HIPCHK(c, dalloc(&p->xfer, (size_t)p->n_work));
-        p->xfer_cap = p->n_work;
-    }
+    HIPCHK(c, p->d_film.reserve(n));
+    HIPCHK(c, p->xfer.reserve((size_t)p->n_work));
     hipSetDevice(c->device);
     if (L.epoch != p->work_epoch) {
-        if (L.cap < (size_t)p->n_work) {
-            if (L.work0) hipFree(L.work0);
-            if (L.xfer0) hipFree(L.xfer0);
-            L.work0 = nullptr;
-            L.xfer0 = nullptr;
-            HIPCHK(c, dalloc(&L.work0, (size_t)p->n_work));
-            HIPCHK(c, dalloc(&L.xfer0, (size_t)p->n_work));
-            L.cap = p->n_work;
-        }
-        HIPCHK(c, hipMemcpyPeer(L.work0, c->device, p->d_work, p->device, sizeof(int) * p->n_work));
+        HIPCHK(c, L.work0.reserve((size_t)p->n_work));
+        HIPCHK(c, L.xfer0.reserve((size_t)p->n_work));
+        HIPCHK(c, hipMemcpyPeer(L.work0.get(), c->device, p->d_work.get(), p->device, sizeof(int) * p->n_work));
         L.n = p->n_work;
         L.epoch = p->work_epoch;
     }
@@ -1599,14 +1525,14 @@ int peer_pass(rt_ctx* c, size_t j, int ib, int ie) {
     const size_t bytes = sizeof(float4) * L.n;
     HIPCHK(p, hipStreamWaitEvent(ps, c->gathered, 0));
     if (L.n) {
-        HIPCHK(p, hipMemcpyPeerAsync(p->xfer, p->device, L.xfer0, c->device, bytes, ps));
-        HIPCHK(p, launch_film_scatter(ps, L.n, p->d_work, p->xfer, p->d_film));
+        HIPCHK(p, hipMemcpyPeerAsync(p->xfer.get(), p->device, L.xfer0.get(), c->device, bytes, ps));
+        HIPCHK(p, launch_film_scatter(ps, L.n, p->d_work.get(), p->xfer.get(), p->d_film.get()));
     }
-    int rc = render_device(p, ib, ie, p->d_film, ps);
+    int rc = render_device(p, ib, ie, p->d_film.get(), ps);
     if (rc) return rc;
     if (L.n) {
-        HIPCHK(p, launch_film_gather(ps, L.n, p->d_work, p->d_film, p->xfer));
-        HIPCHK(p, hipMemcpyPeerAsync(L.xfer0, c->device, p->xfer, p->device, bytes, ps));
+        HIPCHK(p, launch_film_gather(ps, L.n, p->d_work.get(), p->d_film.get(), p->xfer.get()));
+        HIPCHK(p, hipMemcpyPeerAsync(L.xfer0.get(), c->device, p->xfer.get(), p->device, bytes, ps));
     }
     HIPCHK(p, hipEventRecord(p->gathered, ps));
     return RT_OK;
@@ -1621,7 +1547,7 @@ int render_multi(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) {
         if ((rc = peer_prepare(c, j))) return rc;
     hipSetDevice(c->device);
     for (const rt_ctx::PeerLink& L : c->links)
-        if (L.n) HIPCHK(c, launch_film_gather(st, L.n, L.work0, film, L.xfer0));
+        if (L.n) HIPCHK(c, launch_film_gather(st, L.n, L.work0.get(), film, L.xfer0.get()));
     HIPCHK(c, hipEventRecord(c->gathered, st));
     std::vector<int> prc(c->peers.size(), RT_OK);
     std::vector<std::thread> th;
@@ -1636,7 +1562,7 @@ int render_multi(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) {
     for (size_t j = 0; j < c->peers.size(); ++j) {
         const rt_ctx::PeerLink& L = c->links[j];
         HIPCHK(c, hipStreamWaitEvent(st, c->peers[j]->gathered, 0));
-        if (L.n) HIPCHK(c, launch_film_scatter(st, L.n, L.work0, L.xfer0, film));
+        if (L.n) HIPCHK(c, launch_film_scatter(st, L.n, L.work0.get(), L.xfer0.get(), film));
     }
     return RT_OK;
 }
@@ -1668,35 +1594,10 @@ static int create_one(const rt_options* opt, rt_ctx** out) {
         return RT_E_HIP;
     }
     c->grid = prop.multiProcessorCount * 8;  // persistent grid: 8 blocks of 256 per CU
-    if (std::getenv("RTMI_NO_STAGE_EVENTS")) c->stage_events = false;
-    if (const char* e = std::getenv("RTMI_LANES")) c->lanes = std::max(1, std::min(kLanes, std::atoi(e)));
-    if (const char* e = std::getenv("RTMI_SHADOW_QUEUE")) c->shadow_queue = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_SHADOW_DFS")) c->shadow_dfs = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_SORT")) c->sort_rays = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_BVH_CI")) c->bvh_node_cost = (float)std::atof(e);
-    if (const char* e = std::getenv("RTMI_BVH_LEAF")) c->bvh_max_leaf = std::max(1, std::min(15, std::atoi(e)));
-    parse_bvh_any(c->bvh_any_cost, c->bvh_any_leaf);
-    if (const char* e = std::getenv("RTMI_FORCE_AMB")) c->force_amb = std::max(-1, std::min(30, std::atoi(e)));
-    if (const char* e = std::getenv("RTMI_COOP")) c->coop = std::atoi(e) != 0;
-    if (const char* e = std::getenv("RTMI_MAT_BINS")) c->mat_bins = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_EMIT_FILTER")) c->emit_filter = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_DEBUG_PATH_KERNELS")) c->debug_path = std::atoi(e) != 0;
-    if (const char* e = std::getenv("RTMI_SORT_BITS")) {
-        int db = 3, ob = 4, om = -1;
-        const int got = std::sscanf(e, "%d/%d/%d", &db, &ob, &om);
-        // the key is 3 octant bits + 2 x db direction bits + 3 x ob origin bits in one u32, ob <= 9 (spread3_9)
-        if (got >= 2 && db >= 0 && db <= 9 && ob >= 0 && ob <= 9 && 3 + 2 * db + 3 * ob <= 32) {
-            c->sort_dir_bits = db;
-            c->sort_org_bits = ob;
-            if (got == 3) c->sort_org_major = om < 0 ? -1 : (om ? 1 : 0);
-        }
-    }
-    if (const char* e = std::getenv("RTMI_SORT_NEE")) std::sscanf(e, "%d/%d", &c->sort_nee, &c->sort_nee_bits);
-    c->sort_nee_bits = std::max(1, std::min(9, c->sort_nee_bits));
-    if (const char* e = std::getenv("RTMI_BATCH_SAMPLES")) c->batch_samples = (size_t)std::max(0L, std::atol(e));
+    c->knobs = read_knobs();
     c->hs.init();
-    if (dalloc(&c->d_spec, 1) != hipSuccess || dalloc(&c->ws[0].d_qcount, 2 * kQRegion) != hipSuccess ||
-        dalloc(&c->d_ctr, kCtrWords) != hipSuccess || dalloc(&c->d_resolve, 18) != hipSuccess) {
+    if (c->d_spec.reserve(1) != hipSuccess || c->ws[0].qcount.reserve(2 * kQRegion) != hipSuccess ||
+        c->d_ctr.reserve(kCtrWords) != hipSuccess || c->d_resolve.reserve(18) != hipSuccess) {
         destroy_one(c);
         return RT_E_OOM;
     }
@@ -1711,8 +1612,8 @@ static int create_one(const rt_options* opt, rt_ctx** out) {
     ds.bk7_n = (int)c->hs.BK7.l.size();
     std::memcpy(ds.bk7_lambda, c->hs.BK7.l.data(), 4 * ds.bk7_n);
     std::memcpy(ds.bk7_value, c->hs.BK7.v.data(), 4 * ds.bk7_n);
-    hipMemcpy(c->d_spec, &ds, sizeof(ds), hipMemcpyHostToDevice);
-    hipMemset(c->d_ctr, 0, sizeof(unsigned long long) * kCtrWords);
+    hipMemcpy(c->d_spec.get(), &ds, sizeof(ds), hipMemcpyHostToDevice);
+    hipMemset(c->d_ctr.get(), 0, sizeof(unsigned long long) * kCtrWords);
     {
         rt_film_desc fd{};  // XYZ sensor under D65 until rt_film_set says otherwise
         if (setup_sensor(c, fd) != RT_OK) {
@@ -1732,20 +1633,14 @@ static void destroy_one(rt_ctx* c) {
         if (w.stream) hipStreamSynchronize(w.stream);
     harvest(c);
     for (hipEvent_t e : c->pool) hipEventDestroy(e);
-    free_scene(c);
-    free_workspace(c);
     for (Work& w : c->ws) {
-        if (w.d_qcount) hipFree(w.d_qcount);
         if (w.film_done) hipEventDestroy(w.film_done);
         if (w.stream) hipStreamDestroy(w.stream);
     }
-    void* ptrs[] = {c->d_spec, c->d_ctr, c->d_resolve, c->d_work, c->d_film, c->d_cdf, c->d_sobol_mats,
-                    c->d_sobol_fwd};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
     if (c->done) hipEventDestroy(c->done);
+    if (c->gathered) hipEventDestroy(c->gathered);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // every DevBuf member, while c->device is current
 }
 
 const char* rt_last_error(const rt_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -1816,114 +1711,104 @@ static void scene_bvh(const SceneWorld& w, int set, float node_cost, int max_lea
     build_bvh8(t9.data(), ids.data(), (int)ids.size(), pad, node_cost, out, max_leaf);
 }
 
-static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
-    if (!c || !s) return RT_E_ARG;
+// The first rule a scene description breaks, or an empty string.  geometry_only: the rules a BVH build alone depends
+// on (rt_debug_bvh_build).
+static std::string validate_scene(const rt_scene_desc* s, bool geometry_only = false) {
     if (s->n_triangles <= 0 || s->n_vertices <= 0 || !s->positions || !s->indices)
-        return fail(c, RT_E_ARG, "scene needs positions and indices");
-    if (s->cull_backfaces && !s->normals) return fail(c, RT_E_ARG, "back-face culling needs vertex normals");
+        return "scene needs positions and indices";
+    if (s->cull_backfaces && !s->normals) return "back-face culling needs vertex normals";
     for (int t = 0; t < 3 * s->n_triangles; ++t)
-        if (s->indices[t] >= (uint32_t)s->n_vertices) return fail(c, RT_E_ARG, "triangle index out of range");
+        if (s->indices[t] >= (uint32_t)s->n_vertices) return "triangle index out of range";
+    if (geometry_only) return "";
+    auto mat_ok = [&](int m) { return m >= 0 && m < std::max(1, s->n_materials); };
     if (s->tri_material)
         for (int t = 0; t < s->n_triangles; ++t)
-            if (s->tri_material[t] < 0 || s->tri_material[t] >= std::max(1, s->n_materials))
-                return fail(c, RT_E_ARG, "material id out of range");
-    auto mat_ok = [&](int m) { return m >= 0 && m < std::max(1, s->n_materials); };
+            if (!mat_ok(s->tri_material[t])) return "material id out of range";
     for (int i = 0; i < s->n_materials; ++i) {
         const rt_material& m = s->materials[i];
-        if (m.type < RT_MAT_DIFFUSE || m.type > RT_MAT_DIELECTRIC) return fail(c, RT_E_ARG, "unknown material type");
-        if (m.type == RT_MAT_DIELECTRIC && m.eta < 0) return fail(c, RT_E_ARG, "dielectric eta must be >= 0");
+        if (m.type < RT_MAT_DIFFUSE || m.type > RT_MAT_DIELECTRIC) return "unknown material type";
+        if (m.type == RT_MAT_DIELECTRIC && m.eta < 0) return "dielectric eta must be >= 0";
     }
-    if (s->n_shapes < 0 || (s->n_shapes > 0 && !s->shapes)) return fail(c, RT_E_ARG, "shapes");
+    if (s->n_shapes < 0 || (s->n_shapes > 0 && !s->shapes)) return "shapes";
     for (int i = 0; i < s->n_shapes; ++i) {
         const rt_shape& h = s->shapes[i];
-        if (!mat_ok(h.material)) return fail(c, RT_E_ARG, "shape material out of range");
+        if (!mat_ok(h.material)) return "shape material out of range";
         if (h.type == RT_SHAPE_SPHERE) {
             if (!(h.radius > 0) || h.zmin > -h.radius || h.zmax < h.radius || h.phimax < 360.f)
-                return fail(c, RT_E_ARG, "only full spheres are supported (zmin <= -r, zmax >= r, phimax >= 360)");
+                return "only full spheres are supported (zmin <= -r, zmax >= r, phimax >= 360)";
         } else if (h.type == RT_SHAPE_DISK) {
             if (h.phimax < 360.f || !(h.outer_radius > 0) || h.inner_radius < 0)
-                return fail(c, RT_E_ARG, "only full disks are supported (phimax >= 360)");
+                return "only full disks are supported (phimax >= 360)";
         } else if (h.type != RT_SHAPE_TRIANGLE) {
-            return fail(c, RT_E_ARG, "unknown shape type");
+            return "unknown shape type";
         }
     }
     if (s->n_lights < 0 || s->n_lights > kMaxLights || (s->n_lights > 0 && !s->lights))
-        return fail(c, RT_E_ARG, "lights: at most " + std::to_string(kMaxLights));
+        return "lights: at most " + std::to_string(kMaxLights);
     for (int i = 0; i < s->n_lights; ++i) {
         const rt_light& L = s->lights[i];
         if (L.type == RT_LIGHT_QUAD) {
             if (!mat_ok(L.material) || !(s->materials && s->materials[L.material].emission_scale > 0))
-                return fail(c, RT_E_ARG, "quad light needs an emissive material");
+                return "quad light needs an emissive material";
         } else if (L.type == RT_LIGHT_DISK) {
             if (L.shape < 0 || L.shape >= s->n_shapes || s->shapes[L.shape].type != RT_SHAPE_DISK ||
                 s->shapes[L.shape].inner_radius != 0 || !(s->materials[s->shapes[L.shape].material].emission_scale > 0))
-                return fail(c, RT_E_ARG, "disk light needs an emissive full DISK shape with inner radius 0");
+                return "disk light needs an emissive full DISK shape with inner radius 0";
         } else if (L.type == RT_LIGHT_DISTANT) {
-            if (L.dir[0] == 0 && L.dir[1] == 0 && L.dir[2] == 0) return fail(c, RT_E_ARG, "distant light direction");
+            if (L.dir[0] == 0 && L.dir[1] == 0 && L.dir[2] == 0) return "distant light direction";
         } else if (L.type != RT_LIGHT_POINT) {
-            return fail(c, RT_E_ARG, "unknown light type");
+            return "unknown light type";
         }
     }
-    hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
-    free_scene(c);
-    const int nt = s->n_triangles, nv = s->n_vertices;
-    SceneWorld sw;
-    scene_world(s, sw);
-    const std::vector<F3>& tri3 = sw.tri3;
-    const std::vector<uint8_t>&back = sw.back, &degen = sw.degen;
-    c->cull = s->cull_backfaces != 0;
-    // root bounds: TriModel::Bounds (Shapes.h:1390-1397): object-space min/max (max starts at FLT_MIN, :1292)
-    // then Bounds3::Transform (Shapes.h:60-98, same FLT_MIN quirk)
+    return "";
+}
+
+// The octree's root box — TriModel::Bounds (Shapes.h:1390-1397): object-space min/max (max starts at FLT_MIN, :1292)
+// then Bounds3::Transform (Shapes.h:60-98, same FLT_MIN quirk) — and the coherence sorts' quantisation over it.
+static void scene_root_box(rt_ctx* c, const rt_scene_desc* s, F3& rmn, F3& rmx) {
     const float FMAX = std::numeric_limits<float>::max(), FMIN = std::numeric_limits<float>::min();
     F3 omn = {FMAX, FMAX, FMAX}, omx = {FMIN, FMIN, FMIN};
-    for (int i = 0; i < nv; ++i) {
+    for (int i = 0; i < s->n_vertices; ++i) {
         const float* p = s->positions + 3 * i;
         omn = {std::min(omn.x, p[0]), std::min(omn.y, p[1]), std::min(omn.z, p[2])};
         omx = {std::max(omx.x, p[0]), std::max(omx.y, p[1]), std::max(omx.z, p[2])};
     }
     const F3 corners[8] = {{omn.x, omn.y, omn.z}, {omn.x, omx.y, omn.z}, {omn.x, omx.y, omx.z}, {omn.x, omn.y, omx.z},
                            {omx.x, omx.y, omx.z}, {omx.x, omn.y, omx.z}, {omx.x, omn.y, omn.z}, {omx.x, omx.y, omn.z}};
-    F3 rmn = {FMAX, FMAX, FMAX}, rmx = {FMIN, FMIN, FMIN};
+    rmn = {FMAX, FMAX, FMAX};
+    rmx = {FMIN, FMIN, FMIN};
     for (const F3& q : corners) {
         float o[4];
         m4v(s->object_to_render, q.x, q.y, q.z, 1.f, o);
         rmn = {std::min(rmn.x, o[0]), std::min(rmn.y, o[1]), std::min(rmn.z, o[2])};
         rmx = {std::max(rmx.x, o[0]), std::max(rmx.y, o[1]), std::max(rmx.z, o[2])};
     }
-    {  // ray coherence sort: origins quantised to 9 bits per axis over the root box
-        F3 e = f3sub(rmx, rmn);
-        auto sc = [](float x) { return x > 0 ? 512.0f / x : 0.0f; };
-        c->sort_lo = make_float4(rmn.x, rmn.y, rmn.z, 0.f);
-        c->sort_scale = make_float4(sc(e.x), sc(e.y), sc(e.z), 0.f);
-    }
-    // octree build (all triangles, culled and degenerate included — the reference inserts every triangle)
-    OctBuild ob;
-    ob.tri3 = &tri3;
-    ob.capacity = s->octree_capacity > 0 ? s->octree_capacity : 40;
-    OctBuild::Node root;
-    root.mn = rmn;
-    root.mx = rmx;
-    ob.nodes.push_back(root);
-    if (c->octree_build == RT_OCTREE_BUILD_HOST) {
-        for (int t = 0; t < nt; ++t) ob.add(t);
-    } else {
-        std::string err;
-        int brc = octree_build_device(c->stream, ob, nt, err);
-        if (brc) return fail(c, brc, err);
-    }
+    // ray coherence sort: origins quantised to 9 bits per axis over the root box
+    F3 e = f3sub(rmx, rmn);
+    auto sc = [](float x) { return x > 0 ? 512.0f / x : 0.0f; };
+    c->sort_lo = make_float4(rmn.x, rmn.y, rmn.z, 0.f);
+    c->sort_scale = make_float4(sc(e.x), sc(e.y), sc(e.z), 0.f);
+}
+
+// The octree in the HBM layout of rt_internal.h: node SoA + the leaf tiles of the two tile sets (set 0: the
+// non-degenerate triangles, set 1: without the back-facing ones).
+struct FlatOctree {
+    std::vector<float4> nA, nB;
+    std::vector<int2> lr[2];
+    std::vector<float4> tiles[2];
+};
+// (also fills the context's host mirrors of the tree, h_*)
+static void flatten_octree(rt_ctx* c, const OctBuild& ob, const SceneWorld& sw, FlatOctree& f) {
     const int nn = (int)ob.nodes.size();
-    // flatten: node SoA + two tile sets
-    std::vector<float4> nA(nn), nB(nn);
-    std::vector<int2> lr0(nn), lr1(nn);
-    std::vector<float4> tiles0, tiles1;
+    f.nA.resize(nn); f.nB.resize(nn);
+    f.lr[0].resize(nn); f.lr[1].resize(nn);
     c->h_bounds.assign(6 * (size_t)nn, 0.f);
     c->h_child.assign(nn, -1);
     c->h_leaf_first.assign(nn, 0);
     c->h_leaf_count.assign(nn, 0);
     c->h_refs.clear();
     auto push_tile = [&](std::vector<float4>& v, int t) {
-        const F3* p = &tri3[3 * (size_t)t];
+        const F3* p = &sw.tri3[3 * (size_t)t];
         int bits = t;
         float fid;
         std::memcpy(&fid, &bits, 4);
@@ -1936,37 +1821,46 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
         int child = N.first_child;
         float fc;
         std::memcpy(&fc, &child, 4);
-        nA[i] = make_float4(N.mn.x, N.mn.y, N.mn.z, fc);
-        nB[i] = make_float4(N.mx.x, N.mx.y, N.mx.z, 0.f);
+        f.nA[i] = make_float4(N.mn.x, N.mn.y, N.mn.z, fc);
+        f.nB[i] = make_float4(N.mx.x, N.mx.y, N.mx.z, 0.f);
         float* b = &c->h_bounds[6 * (size_t)i];
         b[0] = N.mn.x; b[1] = N.mn.y; b[2] = N.mn.z; b[3] = N.mx.x; b[4] = N.mx.y; b[5] = N.mx.z;
         c->h_child[i] = child;
         c->h_leaf_first[i] = (int)c->h_refs.size();
         c->h_leaf_count[i] = (int)N.tris.size();
-        lr0[i] = make_int2((int)tiles0.size() / 3, 0);
-        lr1[i] = make_int2((int)tiles1.size() / 3, 0);
+        f.lr[0][i] = make_int2((int)f.tiles[0].size() / 3, 0);
+        f.lr[1][i] = make_int2((int)f.tiles[1].size() / 3, 0);
         for (int t : N.tris) {
             c->h_refs.push_back(t);
-            if (degen[t]) continue;
-            push_tile(tiles0, t);
-            lr0[i].y++;
-            if (!back[t]) { push_tile(tiles1, t); lr1[i].y++; }
+            if (sw.degen[t]) continue;
+            push_tile(f.tiles[0], t);
+            f.lr[0][i].y++;
+            if (!sw.back[t]) { push_tile(f.tiles[1], t); f.lr[1][i].y++; }
         }
     }
-    // BFS group-queue bound: max over depth d of (#internal nodes at d-1 + #internal nodes at d)
-    std::vector<int> depth(nn, 0), internal_at;
-    int maxd = 0;
+}
+
+// What the traversal kernels need to know about the octree's shape.
+struct OctLimits {
+    int depth = 0;       // of the deepest node
+    int bound = 0;       // exact worst case of the kernels' BFS group FIFO
+    int qcap = 1;        // 1: single leaf; 16: register FIFO; 0: the LDS + HBM-spill FIFO
+    bool ids16 = true;   // every group id (first child = 1 + 8 g) fits 16 bits
+};
+static int octree_limits(rt_ctx* c, const OctBuild& ob, OctLimits& L) {
+    const int nn = (int)ob.nodes.size();
+    std::vector<int> depth(nn, 0);
     for (int i = 0; i < nn; ++i) {
-        if (ob.nodes[i].first_child >= 0)
-            for (int k = 0; k < 8; ++k) depth[ob.nodes[i].first_child + k] = depth[i] + 1;
-        maxd = std::max(maxd, depth[i]);
+        const int fc = ob.nodes[i].first_child;
+        if (fc >= 0) {
+            for (int k = 0; k < 8; ++k) depth[fc + k] = depth[i] + 1;
+            // children are created 8 at a time after the root (node 1 + 8 g)
+            if ((fc - 1) % 8 != 0 || (fc - 1) / 8 > 65535) L.ids16 = false;
+        }
+        L.depth = std::max(L.depth, depth[i]);
     }
-    internal_at.assign(maxd + 2, 0);
-    for (int i = 0; i < nn; ++i)
-        if (ob.nodes[i].first_child >= 0) internal_at[depth[i]]++;
     // Exact worst case of the kernel's group FIFO: replay the BFS with every box test passing (any real ray
     // pushes a subset of these groups, in the same order, so its queue is never longer at the same point).
-    int bound = 0;
     {
         std::vector<int> fifo;
         fifo.reserve(nn);
@@ -1976,7 +1870,7 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
             int fc = ob.nodes[cur].first_child;
             if (fc >= 0) {
                 fifo.push_back(fc);
-                bound = std::max(bound, (int)(fifo.size() - head));
+                L.bound = std::max(L.bound, (int)(fifo.size() - head));
             }
             if (--left > 0) { ++cur; continue; }
             if (head == fifo.size()) break;
@@ -1984,65 +1878,75 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
             left = 8;
         }
     }
-    int qcap = 1;
     if (ob.nodes[0].first_child >= 0) {
         const int caps[] = {16};  // register FIFO; larger bounds use the LDS + HBM-spill FIFO (qcap 0)
-        qcap = 0;
+        L.qcap = 0;
         for (int cp : caps)
-            if (cp >= bound) { qcap = cp; break; }
-        if (!qcap && bound > kRingMax)
-            return fail(c, RT_E_LIMIT, "octree BFS frontier bound " + std::to_string(bound) + " exceeds " +
+            if (cp >= L.bound) { L.qcap = cp; break; }
+        if (!L.qcap && L.bound > kRingMax)
+            return fail(c, RT_E_LIMIT, "octree BFS frontier bound " + std::to_string(L.bound) + " exceeds " +
                                            std::to_string(kRingMax) + " groups");
-        // the LDS FIFO stores 16-bit group ids: children are created 8 at a time after the root (node 1 + 8 g)
-        for (int i = 0; i < nn && !qcap; ++i) {
-            int fc = ob.nodes[i].first_child;
-            if (fc >= 0 && ((fc - 1) % 8 != 0 || (fc - 1) / 8 > 65535))
-                return fail(c, RT_E_LIMIT, "octree too large for 16-bit BFS group ids");
-        }
+        // the LDS FIFO stores 16-bit group ids
+        if (!L.qcap && !L.ids16) return fail(c, RT_E_LIMIT, "octree too large for 16-bit BFS group ids");
     }
-    // multi-level octrees: the fast traversal's BVH per tile set (non-degenerate triangles; set 1 without the
-    // back-facing ones) and the canonical-rule window (rt_bvh.cpp)
-    // [kBvhAny]: the any-hit BVH of the shadow rays (set 0), built with its own SAH cost and leaf size
-    BvhData bvh[3];
-    float wabs = 0.f, oguard = 0.f;
+    return RT_OK;
+}
+
+// multi-level octrees: the fast traversal's BVH per tile set (non-degenerate triangles; set 1 without the
+// back-facing ones) and the canonical-rule window (rt_bvh.cpp)
+// [kBvhAny]: the any-hit BVH of the shadow rays (set 0), built with its own SAH cost and leaf size
+static int scene_bvhs(rt_ctx* c, const SceneWorld& sw, int qcap, BvhData bvh[3], float& wabs, float& oguard) {
+    const Knobs& kn = c->knobs;
     if (qcap != 1) {
         // a BVH leaf word holds its first tile in 27 bits (rt_kernels.hip decode_leaf): one tile per triangle
         if (sw.tri3.size() / 3 >= ((size_t)1 << 27))
             return fail(c, RT_E_LIMIT, "more than 2^27 triangles: the BVH leaf words hold 27-bit tile offsets");
         for (int st = 0; st < (c->cull ? 2 : 1); ++st)
-            scene_bvh(sw, st, c->bvh_node_cost, c->bvh_max_leaf, bvh[st], wabs, oguard);
-        if (c->bvh_any_cost > 0) scene_bvh(sw, 0, c->bvh_any_cost, c->bvh_any_leaf, bvh[kBvhAny], wabs, oguard);
+            scene_bvh(sw, st, kn.bvh_node_cost, kn.bvh_max_leaf, bvh[st], wabs, oguard);
+        if (kn.bvh_any_cost > 0) scene_bvh(sw, 0, kn.bvh_any_cost, kn.bvh_any_leaf, bvh[kBvhAny], wabs, oguard);
     } else {
         // single leaf: the same window for the closest-hit pass 2's nearest-first order (rt_kernels.hip traverse)
         float mc = 0.f;
         for (const F3& p : sw.wv) mc = std::max(mc, std::max(std::fabs(p.x), std::max(std::fabs(p.y), std::fabs(p.z))));
         wabs = mc * 0x1p-20f;
     }
-    c->info.n_nodes = nn;
-    c->info.n_leaf_refs = (int)c->h_refs.size();
-    c->info.max_queue_groups = bound;
-    c->info.depth = maxd;
-    c->n_tris = nt;
-    // per-triangle shading data
-    std::vector<float4> tw(3 * (size_t)nt), tn(3 * (size_t)nt);
+    return RT_OK;
+}
+
+// Per-triangle shading data, materials, analytic shapes and lights as the kernels read them.
+struct ShadingArrays {
+    std::vector<float4> tw, tn;     // world vertices and vertex normals, 3 per triangle
+    std::vector<int> tm;            // material per triangle
+    std::vector<DevMaterial> mats;
+    std::vector<DevShape> shapes;
+    std::vector<DevLight> lights;
+    // the emissive surfaces, for the last depth's emitter filter (EmitIO): non-degenerate triangles and shapes whose
+    // material emits
+    std::vector<int> etris, eshapes;
+    bool full = false;              // the scene needs the general path-shade kernel
+};
+static void shading_arrays(const rt_scene_desc* s, const SceneWorld& sw, ShadingArrays& a) {
+    const int nt = s->n_triangles;
+    a.tw.resize(3 * (size_t)nt); a.tn.resize(3 * (size_t)nt);
     for (int t = 0; t < nt; ++t)
         for (int k = 0; k < 3; ++k) {
-            const F3& p = tri3[3 * (size_t)t + k];
-            tw[3 * (size_t)t + k] = make_float4(p.x, p.y, p.z, 0.f);
+            const F3& p = sw.tri3[3 * (size_t)t + k];
+            a.tw[3 * (size_t)t + k] = make_float4(p.x, p.y, p.z, 0.f);
             uint32_t v = s->indices[3 * t + k];
-            tn[3 * (size_t)t + k] = s->normals ? make_float4(s->normals[3 * v], s->normals[3 * v + 1], s->normals[3 * v + 2], 0.f)
-                                               : make_float4(0.f, 0.f, 1.f, 0.f);
+            a.tn[3 * (size_t)t + k] = s->normals ? make_float4(s->normals[3 * v], s->normals[3 * v + 1], s->normals[3 * v + 2], 0.f)
+                                                 : make_float4(0.f, 0.f, 1.f, 0.f);
         }
-    std::vector<int> tm(nt, 0);
-    if (s->tri_material) tm.assign(s->tri_material, s->tri_material + nt);
-    std::vector<DevMaterial> mats;
+    a.tm.assign(nt, 0);
+    if (s->tri_material) a.tm.assign(s->tri_material, s->tri_material + nt);
+    std::vector<DevMaterial>& mats = a.mats;
     for (int i = 0; i < s->n_materials; ++i) {
         const rt_material& m = s->materials[i];
         const int cls = m.emission_scale > 0 || m.type == RT_MAT_DIFFUSE ? 0 : 1;  // material bin (kMatClasses)
         mats.push_back(DevMaterial{m.sigmoid[0], m.sigmoid[1], m.sigmoid[2], m.emission_scale, m.type, m.eta, -1, cls});
     }
     if (mats.empty()) mats.push_back(DevMaterial{0.f, 0.f, 0.f, 0.f, RT_MAT_DIFFUSE, 0.f, -1, 0});
-    std::vector<DevShape> shapes(s->n_shapes);
+    std::vector<DevShape>& shapes = a.shapes;
+    shapes.resize(s->n_shapes);
     for (int i = 0; i < s->n_shapes; ++i) {
         const rt_shape& h = s->shapes[i];
         DevShape& d = shapes[i];
@@ -2057,12 +1961,12 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
         std::memcpy(d.p1, h.p, 12); std::memcpy(d.p2, h.p + 3, 12); std::memcpy(d.p3, h.p + 6, 12);
         shape_bound(d);
     }
-    std::vector<DevLight> lights(s->n_lights);
+    a.lights.resize(s->n_lights);
     bool full = s->n_shapes > 0 || s->n_lights != 1;
     for (const DevMaterial& m : mats) full = full || m.type != RT_MAT_DIFFUSE;
     for (int i = 0; i < s->n_lights; ++i) {
         const rt_light& q = s->lights[i];
-        DevLight& L = lights[i];
+        DevLight& L = a.lights[i];
         L = DevLight{};
         L.type = q.type; L.shape = q.shape; L.material = q.material; L.scale = q.scale;
         for (int k = 0; k < 3; ++k) { L.p[k] = q.p[k]; L.e1[k] = q.e1[k]; L.e2[k] = q.e2[k]; L.n[k] = q.n[k]; }
@@ -2085,70 +1989,87 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
         }
         if (q.type != RT_LIGHT_QUAD) full = true;
     }
-    // upload
-    auto up = [&](const void* src, size_t bytes, void** dst) -> int {
-        void* p = nullptr;
-        HIPCHK(c, hipMalloc(&p, std::max<size_t>(bytes, 16)));
-        c->scene_allocs.push_back(p);
-        if (bytes) HIPCHK(c, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-        *dst = p;
-        return RT_OK;
-    };
-    void *pA, *pB, *pl0, *pl1, *pt0, *pt1 = nullptr, *ptw, *ptn, *ptm, *pm, *psh, *plt;
-    int rc;
-    if ((rc = up(nA.data(), nA.size() * 16, &pA)) || (rc = up(nB.data(), nB.size() * 16, &pB)) ||
-        (rc = up(lr0.data(), lr0.size() * 8, &pl0)) || (rc = up(lr1.data(), lr1.size() * 8, &pl1)) ||
-        (rc = up(tiles0.data(), tiles0.size() * 16, &pt0)) || (rc = up(tiles1.data(), tiles1.size() * 16, &pt1)) ||
-        (rc = up(tw.data(), tw.size() * 16, &ptw)) || (rc = up(tn.data(), tn.size() * 16, &ptn)) ||
-        (rc = up(tm.data(), tm.size() * 4, &ptm)) || (rc = up(mats.data(), mats.size() * sizeof(DevMaterial), &pm)) ||
-        (rc = up(shapes.data(), shapes.size() * sizeof(DevShape), &psh)) ||
-        (rc = up(lights.data(), lights.size() * sizeof(DevLight), &plt)))
-        return rc;
-    // single-leaf octree: conservative boxes of runs of kClusterTris leaf tiles (pass-1 culling in the kernel); a
-    // box miss means none of its triangles can pass the watertight test's tMax-independent checks, so the
-    // inflation only has to cover those checks' rounding.  In the sheared frame every vertex coordinate carries
-    // at most ~4 ulp(M) of error, M = the largest |vertex - origin|; with origins inside 8 extents of the scene
-    // centre (cl_guard; farther rays never skip) M <= 9.8 ext, i.e. <= 2.4e-6 ext, and the pad is 1e-5 ext +
-    // 1e-3 — small enough that a wave of rays leaving one wall (origin offset 1e-4 (1 + max|p|)) skips it.
-    std::vector<float4> clus[2];
-    if (qcap == 1) {
-        const std::vector<float4>* tl[2] = {&tiles0, &tiles1};
-        const auto& R = ob.nodes[0];
-        float ext = std::max(std::max(R.mx.x - R.mn.x, R.mx.y - R.mn.y), R.mx.z - R.mn.z);
-        float pad = kClusterPadRel * ext + 1e-3f;
-        c->dsc.cl_guard = make_float4(.5f * (R.mn.x + R.mx.x), .5f * (R.mn.y + R.mx.y), .5f * (R.mn.z + R.mx.z),
-                                      64.f * ext * ext);
-        for (int st = 0; st < 2; ++st) {
-            int nt_leaf = (int)tl[st]->size() / 3;
-            for (int k0 = 0; k0 < nt_leaf; k0 += kClusterTris) {
-                float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-                for (int k = k0; k < std::min(nt_leaf, k0 + kClusterTris); ++k) {
-                    const float4* q = tl[st]->data() + 3 * k;
-                    float v[9] = {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w, q[2].x};
-                    for (int j = 0; j < 3; ++j)
-                        for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], v[3 * j + a]); mx[a] = std::max(mx[a], v[3 * j + a]); }
-                }
-                clus[st].push_back(make_float4(mn[0] - pad, mn[1] - pad, mn[2] - pad, 0.f));
-                clus[st].push_back(make_float4(mx[0] + pad, mx[1] + pad, mx[2] + pad, 0.f));
-            }
-            c->dsc.n_clusters[st] = (int)clus[st].size() / 2;
-            // fan pairs: tile k+1 = (a, c, d) after tile k = (a, b, c), bit for bit (_quad / OBJ fan triangulation)
-            unsigned long long fp = 0;
-            for (int k = 0; k + 1 < std::min(nt_leaf, 64); k += 2) {
-                const float4* q = tl[st]->data() + 3 * k;
+    a.full = full;
+    for (int t = 0; t < nt; ++t)
+        if (!sw.degen[t] && mats[a.tm[t]].emit > 0) a.etris.push_back(t);
+    for (int i = 0; i < s->n_shapes; ++i)
+        if (mats[shapes[i].material].emit > 0) a.eshapes.push_back(i);
+}
+
+// single-leaf octree: conservative boxes of runs of kClusterTris leaf tiles (pass-1 culling in the kernel); a
+// box miss means none of its triangles can pass the watertight test's tMax-independent checks, so the
+// inflation only has to cover those checks' rounding.  In the sheared frame every vertex coordinate carries
+// at most ~4 ulp(M) of error, M = the largest |vertex - origin|; with origins inside 8 extents of the scene
+// centre (cl_guard; farther rays never skip) M <= 9.8 ext, i.e. <= 2.4e-6 ext, and the pad is 1e-5 ext +
+// 1e-3 — small enough that a wave of rays leaving one wall (origin offset 1e-4 (1 + max|p|)) skips it.
+struct LeafClusters {
+    std::vector<float4> box[2];     // per tile set: (min, max) per cluster; empty for multi-level octrees
+    unsigned long long fan_pairs[2] = {0, 0};
+    float4 guard{};
+};
+static void leaf_clusters(const OctBuild::Node& R, const FlatOctree& f, LeafClusters& cl) {
+    float ext = std::max(std::max(R.mx.x - R.mn.x, R.mx.y - R.mn.y), R.mx.z - R.mn.z);
+    float pad = kClusterPadRel * ext + 1e-3f;
+    cl.guard = make_float4(.5f * (R.mn.x + R.mx.x), .5f * (R.mn.y + R.mx.y), .5f * (R.mn.z + R.mx.z), 64.f * ext * ext);
+    for (int st = 0; st < 2; ++st) {
+        const std::vector<float4>& tl = f.tiles[st];
+        int nt_leaf = (int)tl.size() / 3;
+        for (int k0 = 0; k0 < nt_leaf; k0 += kClusterTris) {
+            float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+            for (int k = k0; k < std::min(nt_leaf, k0 + kClusterTris); ++k) {
+                const float4* q = tl.data() + 3 * k;
                 float v[9] = {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w, q[2].x};
-                float w[9] = {q[3].x, q[3].y, q[3].z, q[3].w, q[4].x, q[4].y, q[4].z, q[4].w, q[5].x};
-                if (!std::memcmp(w, v, 12) && !std::memcmp(w + 3, v + 6, 12)) fp |= 1ull << k;
+                for (int j = 0; j < 3; ++j)
+                    for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], v[3 * j + a]); mx[a] = std::max(mx[a], v[3 * j + a]); }
             }
-            c->dsc.fan_pairs[st] = fp;
+            cl.box[st].push_back(make_float4(mn[0] - pad, mn[1] - pad, mn[2] - pad, 0.f));
+            cl.box[st].push_back(make_float4(mx[0] + pad, mx[1] + pad, mx[2] + pad, 0.f));
+        }
+        // fan pairs: tile k+1 = (a, c, d) after tile k = (a, b, c), bit for bit (_quad / OBJ fan triangulation)
+        unsigned long long fp = 0;
+        for (int k = 0; k + 1 < std::min(nt_leaf, 64); k += 2) {
+            const float4* q = tl.data() + 3 * k;
+            float v[9] = {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w, q[2].x};
+            float w[9] = {q[3].x, q[3].y, q[3].z, q[3].w, q[4].x, q[4].y, q[4].z, q[4].w, q[5].x};
+            if (!std::memcmp(w, v, 12) && !std::memcmp(w + 3, v + 6, 12)) fp |= 1ull << k;
+        }
+        cl.fan_pairs[st] = fp;
+    }
+}
+
+// one host array on the device, owned by the context's scene (at least 16 bytes, so empty arrays have a pointer too)
+extern "C++" template <class T>
+static int upload_array(rt_ctx* c, const std::vector<T>& v, const T*& dst) {
+    const size_t bytes = v.size() * sizeof(T);
+    DevBuf<unsigned char> b;
+    HIPCHK(c, b.reserve(std::max<size_t>(bytes, 16)));
+    dst = reinterpret_cast<const T*>(b.get());
+    c->scene_allocs.push_back(std::move(b));
+    if (bytes) HIPCHK(c, hipMemcpy(c->scene_allocs.back().get(), v.data(), bytes, hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// Everything on the device and the DevScene that points to it.
+static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, const OctLimits& lim,
+                        const ShadingArrays& a, const LeafClusters& cl, BvhData bvh[3], float wabs, float oguard) {
+    DevScene& d = c->dsc;
+    const int qcap = lim.qcap;
+    int rc;
+    if ((rc = upload_array(c, f.nA, d.nodeA)) || (rc = upload_array(c, f.nB, d.nodeB)) ||
+        (rc = upload_array(c, f.lr[0], d.leafRange[0])) || (rc = upload_array(c, f.lr[1], d.leafRange[1])) ||
+        (rc = upload_array(c, f.tiles[0], d.tiles[0])) || (rc = upload_array(c, f.tiles[1], d.tiles[1])) ||
+        (rc = upload_array(c, a.tw, d.triWorld)) || (rc = upload_array(c, a.tn, d.triNormal)) ||
+        (rc = upload_array(c, a.tm, d.triMaterial)) || (rc = upload_array(c, a.mats, d.materials)) ||
+        (rc = upload_array(c, a.shapes, d.shapes)) || (rc = upload_array(c, a.lights, d.lights)))
+        return rc;
+    if (qcap == 1) {
+        d.cl_guard = cl.guard;
+        for (int st = 0; st < 2; ++st) {
+            d.n_clusters[st] = (int)cl.box[st].size() / 2;
+            d.fan_pairs[st] = cl.fan_pairs[st];
         }
     }
-    void *pc0 = nullptr, *pc1 = nullptr;
-    if ((rc = up(clus[0].data(), clus[0].size() * 16, &pc0)) || (rc = up(clus[1].data(), clus[1].size() * 16, &pc1)))
-        return rc;
-    void* pbv[3] = {nullptr, nullptr, nullptr};
-    void* pbt[3] = {nullptr, nullptr, nullptr};
-    void* pbi[3] = {nullptr, nullptr, nullptr};
+    if ((rc = upload_array(c, cl.box[0], d.clusters[0])) || (rc = upload_array(c, cl.box[1], d.clusters[1]))) return rc;
     const int bvh_nodes0 = (int)(bvh[0].nodes.size() / kBvhNodeF4);
     for (int st = 0; st < 3; ++st) {
         // a BVH not built here (no culled set; the any-hit walks on the closest-hit BVH of set 0) uses set 0's arrays
@@ -2157,76 +2078,93 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
         c->bvh_count[st][1] = (int)bvh[src].tid.size();
     }
     for (int st = 0; st < 3; ++st) {
+        d.bvh[st] = nullptr; d.btiles[st] = nullptr; d.btid[st] = nullptr;
         if (bvh[st].nodes.empty()) continue;
         // the kernels stage nodes [0, kBvhTopNodes) in LDS unconditionally: pad with empty nodes
         if (bvh[st].nodes.size() < kBvhNodeF4 * (size_t)kBvhTopNodes)
             bvh[st].nodes.resize(kBvhNodeF4 * (size_t)kBvhTopNodes, make_float4(0.f, 0.f, 0.f, 0.f));
         bvh[st].tiles.resize(bvh[st].tiles.size() + 4, 0.f);  // (an empty BVH still gets a buffer)
         bvh[st].tid.push_back(-1);
-        if ((rc = up(bvh[st].nodes.data(), bvh[st].nodes.size() * 16, &pbv[st])) ||
-            (rc = up(bvh[st].tiles.data(), bvh[st].tiles.size() * 4, &pbt[st])) ||
-            (rc = up(bvh[st].tid.data(), bvh[st].tid.size() * 4, &pbi[st])))
+        if ((rc = upload_array(c, bvh[st].nodes, d.bvh[st])) || (rc = upload_array(c, bvh[st].tiles, d.btiles[st])) ||
+            (rc = upload_array(c, bvh[st].tid, d.btid[st])))
             return rc;
     }
-    DevScene& d = c->dsc;
-    for (int st = 0; st < 3; ++st) {
-        d.bvh[st] = (const float4*)(pbv[st] ? pbv[st] : pbv[0]);
-        d.btiles[st] = (const float*)(pbt[st] ? pbt[st] : pbt[0]);
-        d.btid[st] = (const int*)(pbi[st] ? pbi[st] : pbi[0]);
-    }
+    for (int st = 1; st < 3; ++st)
+        if (!d.bvh[st]) { d.bvh[st] = d.bvh[0]; d.btiles[st] = d.btiles[0]; d.btid[st] = d.btid[0]; }
     d.wabs = wabs;
     d.oguard = oguard;
-    d.amb_force = c->force_amb >= 0;
-    d.amb_mask = c->force_amb > 0 ? (1u << c->force_amb) - 1u : 0u;
+    d.amb_force = c->knobs.force_amb >= 0;
+    d.amb_mask = c->knobs.force_amb > 0 ? (1u << c->knobs.force_amb) - 1u : 0u;
     c->info.bvh_nodes = bvh_nodes0;
     c->info.bvh_depth = bvh[0].depth;
-    d.clusters[0] = (const float4*)pc0; d.clusters[1] = (const float4*)pc1;
     if (qcap != 1) d.n_clusters[0] = d.n_clusters[1] = 0;
-    d.nodeA = (const float4*)pA; d.nodeB = (const float4*)pB;
-    d.leafRange[0] = (const int2*)pl0; d.leafRange[1] = (const int2*)pl1;
-    d.tiles[0] = (const float4*)pt0; d.tiles[1] = (const float4*)pt1;
-    d.triWorld = (const float4*)ptw; d.triNormal = (const float4*)ptn;
-    d.triMaterial = (const int*)ptm; d.materials = (const DevMaterial*)pm;
-    d.shapes = (const DevShape*)psh; d.lights = (const DevLight*)plt;
-    d.n_nodes = nn;
-    d.n_tris = nt;
+    d.n_nodes = (int)f.nA.size();
+    d.n_tris = s->n_triangles;
     d.n_shapes = s->n_shapes;
-    d.n_materials = (int)mats.size();
-    c->scene_full = full;
+    d.n_materials = (int)a.mats.size();
+    c->scene_full = a.full;
     d.qcap = qcap;
-    {  // the cooperative BFS's FIFO holds 16-bit group ids (first child = 1 + 8 g) and kCoopFifo of them
-        bool ids16 = true;
-        for (int i = 0; i < nn && ids16; ++i) {
-            const int fc = ob.nodes[i].first_child;
-            if (fc >= 0 && ((fc - 1) % 8 != 0 || (fc - 1) / 8 > 65535)) ids16 = false;
-        }
-        d.coop_ok = c->coop && qcap != 1 && bound <= kCoopFifo && ids16 ? 1 : 0;
-    }
-    d.depth = nn < (1 << 24) ? maxd : 1 << 30;  // DFS stack entries hold 24-bit group ids
+    // the cooperative BFS's FIFO holds 16-bit group ids (first child = 1 + 8 g) and kCoopFifo of them
+    d.coop_ok = c->knobs.coop && qcap != 1 && lim.bound <= kCoopFifo && lim.ids16 ? 1 : 0;
+    d.depth = d.n_nodes < (1 << 24) ? lim.depth : 1 << 30;  // DFS stack entries hold 24-bit group ids
     if (qcap == 0) {  // each lane allocates its ring of ring_threads x rs ints (ensure_ring)
         int rs = 1;
-        while (rs < bound) rs <<= 1;
+        while (rs < lim.bound) rs <<= 1;
         d.ring_threads = c->grid * kBlockThreads;
         d.ring_mask = rs - 1;
     }
     d.n_lights = s->n_lights;
-    if (s->n_lights >= 1) d.light0 = lights[0];
-    // the emissive surfaces, for the last depth's emitter filter (EmitIO): non-degenerate triangles and shapes whose
-    // material emits; more than kMaxEmitTris emissive triangles turn the filter off
-    std::vector<int> etris, eshapes;
-    for (int t = 0; t < nt; ++t)
-        if (!degen[t] && mats[tm[t]].emit > 0) etris.push_back(t);
-    for (int i = 0; i < s->n_shapes; ++i)
-        if (mats[shapes[i].material].emit > 0) eshapes.push_back(i);
-    void *pet = nullptr, *pes = nullptr;
-    if ((rc = up(etris.data(), etris.size() * 4, &pet)) || (rc = up(eshapes.data(), eshapes.size() * 4, &pes)))
-        return rc;
-    d.emit_tris = (const int*)pet;
-    d.n_emit_tris = (int)etris.size() <= kMaxEmitTris ? (int)etris.size() : -1;
-    d.emit_shapes = (const int*)pes;
-    d.n_emit_shapes = (int)eshapes.size();
+    if (s->n_lights >= 1) d.light0 = a.lights[0];
+    // more than kMaxEmitTris emissive triangles turn the emitter filter off
+    if ((rc = upload_array(c, a.etris, d.emit_tris)) || (rc = upload_array(c, a.eshapes, d.emit_shapes))) return rc;
+    d.n_emit_tris = (int)a.etris.size() <= kMaxEmitTris ? (int)a.etris.size() : -1;
+    d.n_emit_shapes = (int)a.eshapes.size();
     c->have_scene = true;
     return RT_OK;
+}
+
+static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
+    if (!c || !s) return RT_E_ARG;
+    const std::string bad = validate_scene(s);
+    if (!bad.empty()) return fail(c, RT_E_ARG, bad);
+    hipSetDevice(c->device);
+    hipStreamSynchronize(c->stream);
+    free_scene(c);
+    SceneWorld sw;
+    scene_world(s, sw);
+    c->cull = s->cull_backfaces != 0;
+    // octree build (all triangles, culled and degenerate included — the reference inserts every triangle)
+    OctBuild ob;
+    ob.tri3 = &sw.tri3;
+    ob.capacity = s->octree_capacity > 0 ? s->octree_capacity : 40;
+    OctBuild::Node root;
+    scene_root_box(c, s, root.mn, root.mx);
+    ob.nodes.push_back(root);
+    if (c->octree_build == RT_OCTREE_BUILD_HOST) {
+        for (int t = 0; t < s->n_triangles; ++t) ob.add(t);
+    } else {
+        std::string err;
+        int brc = octree_build_device(c->stream, ob, s->n_triangles, err);
+        if (brc) return fail(c, brc, err);
+    }
+    int rc;
+    FlatOctree flat;
+    flatten_octree(c, ob, sw, flat);
+    OctLimits lim;
+    if ((rc = octree_limits(c, ob, lim))) return rc;
+    BvhData bvh[3];
+    float wabs = 0.f, oguard = 0.f;
+    if ((rc = scene_bvhs(c, sw, lim.qcap, bvh, wabs, oguard))) return rc;
+    c->info.n_nodes = (int)ob.nodes.size();
+    c->info.n_leaf_refs = (int)c->h_refs.size();
+    c->info.max_queue_groups = lim.bound;
+    c->info.depth = lim.depth;
+    c->n_tris = s->n_triangles;
+    ShadingArrays shade;
+    shading_arrays(s, sw, shade);
+    LeafClusters clus;
+    if (lim.qcap == 1) leaf_clusters(ob.nodes[0], flat, clus);
+    return upload_scene(c, s, flat, lim, shade, clus, bvh, wabs, oguard);
 }
 
 static int camera_set_one(rt_ctx* c, const rt_camera_desc* d) {
@@ -2267,13 +2205,14 @@ static int film_set_one(rt_ctx* c, const rt_film_desc* d) {
     }
     int rc = setup_sensor(c, *d);
     if (rc) return rc;
-    if (c->d_cdf) { hipFree(c->d_cdf); c->d_cdf = nullptr; c->cdf_n = 0; }
+    c->d_cdf.reset();
+    c->cdf_n = 0;
     if (d->filter == RT_FILTER_GAUSSIAN || d->filter == RT_FILTER_LANCZOS) {
         std::vector<float> tx, ty;
         int n = build_filter_tables(*d, tx, ty);
-        if (hipMalloc(&c->d_cdf, sizeof(float) * 2 * (n + 1)) != hipSuccess) return fail(c, RT_E_OOM, "filter tables");
-        hipMemcpy(c->d_cdf, tx.data(), sizeof(float) * (n + 1), hipMemcpyHostToDevice);
-        hipMemcpy(c->d_cdf + (n + 1), ty.data(), sizeof(float) * (n + 1), hipMemcpyHostToDevice);
+        if (c->d_cdf.reserve(2 * (size_t)(n + 1)) != hipSuccess) return fail(c, RT_E_OOM, "filter tables");
+        hipMemcpy(c->d_cdf.get(), tx.data(), sizeof(float) * (n + 1), hipMemcpyHostToDevice);
+        hipMemcpy(c->d_cdf.get() + (n + 1), ty.data(), sizeof(float) * (n + 1), hipMemcpyHostToDevice);
         c->cdf_n = n;
     }
     c->film = *d;
@@ -2336,15 +2275,10 @@ static int impl_rt_render_pass(rt_ctx* c, int ib, int ie, rt_pixel* film) {
     if (rc) return rc;
     hipSetDevice(c->device);
     size_t n = (size_t)c->film.res_x * c->film.res_y;
-    if (c->film_cap < n) {
-        if (c->d_film) hipFree(c->d_film);
-        c->d_film = nullptr;
-        HIPCHK(c, dalloc(&c->d_film, n));
-        c->film_cap = n;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_film, film, n * 16, hipMemcpyHostToDevice, c->stream));
-    if ((rc = render_multi(c, ib, ie, c->d_film, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(film, c->d_film, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, c->d_film.reserve(n));
+    HIPCHK(c, hipMemcpyAsync(c->d_film.get(), film, n * 16, hipMemcpyHostToDevice, c->stream));
+    if ((rc = render_multi(c, ib, ie, c->d_film.get(), c->stream))) return rc;
+    HIPCHK(c, hipMemcpyAsync(film, c->d_film.get(), n * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RT_OK;
 }
@@ -2355,19 +2289,17 @@ int film_resolve(rt_ctx* c, const rt_pixel* film, uint8_t* out, int srgb) {
     if (!c->have_film) return fail(c, RT_E_STATE, "film not set");
     hipSetDevice(c->device);
     size_t n = (size_t)c->film.res_x * c->film.res_y;
-    float4* df = nullptr;
-    unsigned char* dout = nullptr;
-    HIPCHK(c, dalloc(&df, n));
-    if (dalloc(&dout, 3 * n) != hipSuccess) { hipFree(df); return fail(c, RT_E_OOM, "resolve buffer"); }
-    int rc = RT_OK;
-    if (hipMemcpy(df, film, n * 16, hipMemcpyHostToDevice) != hipSuccess ||
-        launch_resolve(c->stream, (int)n, df, c->d_resolve, c->d_resolve + 9, dout, srgb) != hipSuccess ||
-        hipMemcpyAsync(out, dout, 3 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+    DevBuf<float4> df;
+    DevBuf<unsigned char> dout;
+    HIPCHK(c, df.reserve(n));
+    if (dout.reserve(3 * n) != hipSuccess) return fail(c, RT_E_OOM, "resolve buffer");
+    const float* const m = c->d_resolve.get();
+    if (hipMemcpy(df.get(), film, n * 16, hipMemcpyHostToDevice) != hipSuccess ||
+        launch_resolve(c->stream, (int)n, df.get(), m, m + 9, dout.get(), srgb) != hipSuccess ||
+        hipMemcpyAsync(out, dout.get(), 3 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
-        rc = fail(c, RT_E_HIP, "resolve failed");
-    hipFree(df);
-    hipFree(dout);
-    return rc;
+        return fail(c, RT_E_HIP, "resolve failed");
+    return RT_OK;
 }
 }  // namespace
 
@@ -2381,7 +2313,7 @@ static int get_stats_one(rt_ctx* c, rt_stats* out) {
     HIPCHK(c, hipDeviceSynchronize());
     harvest(c);
     std::vector<unsigned long long> raw(kCtrWords);
-    HIPCHK(c, hipMemcpy(raw.data(), c->d_ctr, kCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(raw.data(), c->d_ctr.get(), kCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     unsigned long long h[C_NCOUNTERS] = {};
     for (int k = 0; k < C_NCOUNTERS; ++k)
         for (int u = 0; u < kCtrSubs; ++u) h[k] += raw[ctr_word(k, u)];
@@ -2415,7 +2347,7 @@ static int reset_stats_one(rt_ctx* c) {
     HIPCHK(c, hipDeviceSynchronize());
     harvest(c);
     c->stats = rt_stats{};
-    HIPCHK(c, hipMemset(c->d_ctr, 0, sizeof(unsigned long long) * kCtrWords));
+    HIPCHK(c, hipMemset(c->d_ctr.get(), 0, sizeof(unsigned long long) * kCtrWords));
     return RT_OK;
 }
 
@@ -2460,23 +2392,16 @@ static int impl_rt_bvh_export(rt_ctx* c, int set, int* n_nodes, int* n_tiles, fl
 }
 
 // The same BVH built on the host alone (no device): the upload's world transform, tile-set filter, padding and
-// build parameters (RTMI_BVH_CI / RTMI_BVH_LEAF as rt_create reads them).  For CPU tests of the traversal.
+// build parameters (read_knobs, as rt_create).  For CPU tests of the traversal.
 static int impl_rt_debug_bvh_build(const rt_scene_desc* s, int set, int* n_nodes, int* n_tiles, float* consts,
                                    float* nodes, float* tiles) {
-    if (!s || set < 0 || set > 2 || s->n_triangles <= 0 || s->n_vertices <= 0 || !s->positions || !s->indices)
-        return RT_E_ARG;
-    if (s->cull_backfaces && !s->normals) return RT_E_ARG;
-    for (int t = 0; t < 3 * s->n_triangles; ++t)
-        if (s->indices[t] >= (uint32_t)s->n_vertices) return RT_E_ARG;
-    float cost = 2.5f;
-    int leaf = kBvhMaxLeaf;
-    if (const char* e = std::getenv("RTMI_BVH_CI")) cost = (float)std::atof(e);
-    if (const char* e = std::getenv("RTMI_BVH_LEAF")) leaf = std::max(1, std::min(15, std::atoi(e)));
-    if (set == kBvhAny) {  // rt_create's default (cost 2, leaves <= 4) / RTMI_BVH_ANY ("0/..": set 0's closest-hit BVH)
-        float ac = 2.f;
-        int al = 4;
-        parse_bvh_any(ac, al);
-        if (ac > 0) { cost = ac; leaf = al; }
+    if (!s || set < 0 || set > 2 || !validate_scene(s, /*geometry_only=*/true).empty()) return RT_E_ARG;
+    const Knobs kn = read_knobs();
+    float cost = kn.bvh_node_cost;
+    int leaf = kn.bvh_max_leaf;
+    if (set == kBvhAny && kn.bvh_any_cost > 0) {  // (RTMI_BVH_ANY "0/..": the any-hit walks use set 0's closest-hit BVH)
+        cost = kn.bvh_any_cost;
+        leaf = kn.bvh_any_leaf;
     }
     SceneWorld sw;
     scene_world(s, sw);
@@ -2491,49 +2416,53 @@ static int impl_rt_debug_bvh_build(const rt_scene_desc* s, int set, int* n_nodes
     return RT_OK;
 }
 
+// n rays given as float[3n] origins / directions, on the device as float4[n] each; the direction's w = tmax[i] or 0
+static hipError_t upload_rays(int n, const float* ro, const float* rd, const float* tmax, float4* dO, float4* dD) {
+    std::vector<float4> o(n), d(n);
+    for (int i = 0; i < n; ++i) {
+        o[i] = make_float4(ro[3 * i], ro[3 * i + 1], ro[3 * i + 2], 0.f);
+        d[i] = make_float4(rd[3 * i], rd[3 * i + 1], rd[3 * i + 2], tmax ? tmax[i] : 0.f);
+    }
+    hipError_t e = hipMemcpy(dO, o.data(), 16 * (size_t)n, hipMemcpyHostToDevice);
+    return e != hipSuccess ? e : hipMemcpy(dD, d.data(), 16 * (size_t)n, hipMemcpyHostToDevice);
+}
+
 static int impl_rt_debug_trace(rt_ctx* c, int n, const float* ro, const float* rd, int use_cull, int32_t* prim, float* bt) {
     if (!c || n < 0 || (n && (!ro || !rd || !prim || !bt))) return RT_E_ARG;
     if (!c->have_scene) return fail(c, RT_E_STATE, "no scene");
     if (n == 0) return RT_OK;
     hipSetDevice(c->device);
-    std::vector<float4> o(n), d(n);
-    for (int i = 0; i < n; ++i) {
-        o[i] = make_float4(ro[3 * i], ro[3 * i + 1], ro[3 * i + 2], 0.f);
-        d[i] = make_float4(rd[3 * i], rd[3 * i + 1], rd[3 * i + 2], 0.f);
-    }
-    float4 *dO = nullptr, *dD = nullptr, *dH = nullptr;
-    int *dP = nullptr, *dT = nullptr, *dF = nullptr;
     // RTMI_DEBUG_PATH_KERNELS (multi-level scenes): the kernel path mode launches — wave tickets, the BVH walk, the
     // cooperative BFS for the undecided rays (or k_trace_fallback without coop_ok) — instead of the per-thread one
-    const bool path_kernel = c->debug_path && c->dsc.qcap != 1;
+    const bool path_kernel = c->knobs.debug_path && c->dsc.qcap != 1;
     int rc = ensure_ring(c, c->ws[0]);
     if (!rc) rc = order_after_previous(c, c->stream);
-    if (!rc && (dalloc(&dO, n) || dalloc(&dD, n) || dalloc(&dH, n) || dalloc(&dP, n) ||
-                (path_kernel && (dalloc(&dT, 2 * kQStride) || dalloc(&dF, n)))))
-        rc = fail(c, RT_E_OOM, "debug trace buffers");
-    if (!rc) {
-        TraceIO io{dO, dD, QueueView{nullptr, shard_stride(n, 1), n, 1}, (use_cull && c->cull) ? 1 : 0, dH, dP};
-        if (path_kernel) {  // (ticket counter at dT[0], fallback list length at dT[kQStride])
-            io.ticket = dT;
-            io.fb_pos = dF;
-            io.fb_len = dT + kQStride;
-        }
-        const DevScene& ls = lane_scene(c, c->ws[0]);
-        if ((path_kernel && hipMemsetAsync(dT, 0, 2 * kQStride * sizeof(int), c->stream) != hipSuccess) ||
-            hipMemcpy(dO, o.data(), 16 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dD, d.data(), 16 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
-            launch_trace_closest(c->stream, 0, c->dsc.qcap, ls, io, c->d_ctr) != hipSuccess ||
-            (path_kernel && !c->dsc.coop_ok &&
-             launch_trace_fallback(c->stream, 64, c->dsc.qcap, ls, io, c->d_ctr) != hipSuccess) ||
-            hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(prim, dP, 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(bt, dH, 16 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(c, RT_E_HIP, std::string("debug trace: ") + hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
+    DevBuf<float4> dO, dD, dH;
+    DevBuf<int> dP, dT, dF;
+    if (dO.reserve(n) || dD.reserve(n) || dH.reserve(n) || dP.reserve(n) ||
+        (path_kernel && (dT.reserve(2 * kQStride) || dF.reserve(n))))
+        return fail(c, RT_E_OOM, "debug trace buffers");
+    TraceIO io{dO.get(), dD.get(), QueueView{nullptr, shard_stride(n, 1), n, 1}, (use_cull && c->cull) ? 1 : 0, dH.get(),
+               dP.get()};
+    if (path_kernel) {  // (ticket counter at dT[0], fallback list length at dT[kQStride])
+        io.ticket = dT.get();
+        io.fb_pos = dF.get();
+        io.fb_len = dT.get() + kQStride;
     }
-    hipFree(dO); hipFree(dD); hipFree(dH); hipFree(dP); hipFree(dT); hipFree(dF);
-    if (!rc)
-        for (int i = 0; i < n; ++i)
-            if (prim[i] < 0) bt[4 * i] = bt[4 * i + 1] = bt[4 * i + 2] = bt[4 * i + 3] = 0.f;
-    return rc;
+    const DevScene ls = lane_scene(c, c->ws[0]);
+    if ((path_kernel && hipMemsetAsync(dT.get(), 0, 2 * kQStride * sizeof(int), c->stream) != hipSuccess) ||
+        upload_rays(n, ro, rd, nullptr, dO.get(), dD.get()) != hipSuccess ||
+        launch_trace_closest(c->stream, 0, c->dsc.qcap, ls, io, c->d_ctr.get()) != hipSuccess ||
+        (path_kernel && !c->dsc.coop_ok &&
+         launch_trace_fallback(c->stream, 64, c->dsc.qcap, ls, io, c->d_ctr.get()) != hipSuccess) ||
+        hipStreamSynchronize(c->stream) != hipSuccess ||
+        hipMemcpy(prim, dP.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(bt, dH.get(), 16 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RT_E_HIP, std::string("debug trace: ") + hipGetErrorString(hipGetLastError()));
+    for (int i = 0; i < n; ++i)
+        if (prim[i] < 0) bt[4 * i] = bt[4 * i + 1] = bt[4 * i + 2] = bt[4 * i + 3] = 0.f;
+    return RT_OK;
 }
 
 static int impl_rt_debug_occluded(rt_ctx* c, int n, const float* ro, const float* rd, const float* tmax, int32_t* occluded) {
@@ -2541,26 +2470,19 @@ static int impl_rt_debug_occluded(rt_ctx* c, int n, const float* ro, const float
     if (!c->have_scene) return fail(c, RT_E_STATE, "no scene");
     if (n == 0) return RT_OK;
     hipSetDevice(c->device);
-    std::vector<float4> o(n), d(n);
-    for (int i = 0; i < n; ++i) {
-        o[i] = make_float4(ro[3 * i], ro[3 * i + 1], ro[3 * i + 2], 0.f);
-        d[i] = make_float4(rd[3 * i], rd[3 * i + 1], rd[3 * i + 2], tmax[i]);
-    }
-    float4 *dO = nullptr, *dD = nullptr;
-    int* dP = nullptr;
     int rc = ensure_ring(c, c->ws[0]);
     if (!rc) rc = order_after_previous(c, c->stream);
-    if (!rc && (dalloc(&dO, n) || dalloc(&dD, n) || dalloc(&dP, n))) rc = fail(c, RT_E_OOM, "debug occlusion buffers");
-    if (!rc &&
-        (hipMemcpy(dO, o.data(), 16 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(dD, d.data(), 16 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
-         launch_occluded(c->stream, c->dsc.qcap, lane_scene(c, c->ws[0]), n, dO, dD, dP, c->d_ctr,
-                         c->debug_path && c->dsc.coop_ok) != hipSuccess ||
-         hipStreamSynchronize(c->stream) != hipSuccess ||
-         hipMemcpy(occluded, dP, 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess))
-        rc = fail(c, RT_E_HIP, std::string("debug occlusion: ") + hipGetErrorString(hipGetLastError()));
-    hipFree(dO); hipFree(dD); hipFree(dP);
-    return rc;
+    if (rc) return rc;
+    DevBuf<float4> dO, dD;
+    DevBuf<int> dP;
+    if (dO.reserve(n) || dD.reserve(n) || dP.reserve(n)) return fail(c, RT_E_OOM, "debug occlusion buffers");
+    if (upload_rays(n, ro, rd, tmax, dO.get(), dD.get()) != hipSuccess ||
+        launch_occluded(c->stream, c->dsc.qcap, lane_scene(c, c->ws[0]), n, dO.get(), dD.get(), dP.get(), c->d_ctr.get(),
+                        c->knobs.debug_path && c->dsc.coop_ok) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess ||
+        hipMemcpy(occluded, dP.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RT_E_HIP, std::string("debug occlusion: ") + hipGetErrorString(hipGetLastError()));
+    return RT_OK;
 }
 
 // The coherence sorts alone (rt_sort.hip) on a synthetic sharded queue: kShards shards of stride S, shard j holding
@@ -2582,42 +2504,36 @@ static int impl_rt_debug_sort(rt_ctx* c, int which, int S, const int32_t* shard_
     int rc = order_after_previous(c, c->stream);
     if (rc) return rc;
     const size_t cap = (size_t)kShards * S;
-    unsigned *dkey = nullptr, *k0 = nullptr, *k1 = nullptr;
-    int *dslot = nullptr, *dlen = nullptr, *dout = nullptr, *v0 = nullptr, *v1 = nullptr;
-    void* temp = nullptr;
-    if (dalloc(&dkey, cap) || dalloc(&dslot, cap) || dalloc(&dlen, (size_t)kShards * kQStride) || dalloc(&dout, cap) ||
-        dalloc(&k0, cap) || dalloc(&k1, cap) || dalloc(&v0, cap) || dalloc(&v1, cap) ||
-        hipMalloc(&temp, sort_temp_bytes()) != hipSuccess)
-        rc = fail(c, RT_E_OOM, "debug sort buffers");
-    if (!rc) {
-        std::vector<int> hlen((size_t)kShards * kQStride, 0);
-        for (int j = 0; j < kShards; ++j) hlen[(size_t)j * kQStride] = shard_len[j];
-        std::vector<int> hs(cap, -1);
-        if (which == 1) std::memcpy(hs.data(), slots, cap * 4);
-        hipError_t e = hipMemcpy(dkey, keys, cap * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dslot, hs.data(), cap * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dlen, hlen.data(), hlen.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(dout, 0xff, cap * 4);
-        if (e == hipSuccess) {
-            if (which == 0) {
-                SortRaysIO so{dkey, dout, k0, k1, v0, v1, temp, bits_a, bits_b, dlen, S};
-                e = launch_sort_rays(c->stream, so);
-            } else {
-                SortNeeIO so{dslot, dlen, S, dkey, k0, k1, v0, v1, temp, bits_a};
-                e = launch_sort_nee(c->stream, so);
-            }
+    DevBuf<unsigned> dkey, k0, k1;
+    DevBuf<int> dslot, dlen, dout, v0, v1;
+    DevBuf<unsigned char> temp;
+    if (dkey.reserve(cap) || dslot.reserve(cap) || dlen.reserve((size_t)kShards * kQStride) || dout.reserve(cap) ||
+        k0.reserve(cap) || k1.reserve(cap) || v0.reserve(cap) || v1.reserve(cap) || temp.reserve(sort_temp_bytes()))
+        return fail(c, RT_E_OOM, "debug sort buffers");
+    std::vector<int> hlen((size_t)kShards * kQStride, 0);
+    for (int j = 0; j < kShards; ++j) hlen[(size_t)j * kQStride] = shard_len[j];
+    std::vector<int> hs(cap, -1);
+    if (which == 1) std::memcpy(hs.data(), slots, cap * 4);
+    hipError_t e = hipMemcpy(dkey.get(), keys, cap * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dslot.get(), hs.data(), cap * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dlen.get(), hlen.data(), hlen.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dout.get(), 0xff, cap * 4);
+    if (e == hipSuccess) {
+        if (which == 0) {
+            SortRaysIO so{dkey.get(), dout.get(), k0.get(), k1.get(), v0.get(), v1.get(), temp.get(), bits_a, bits_b,
+                          dlen.get(), S};
+            e = launch_sort_rays(c->stream, so);
+        } else {
+            SortNeeIO so{dslot.get(), dlen.get(), S, dkey.get(), k0.get(), k1.get(), v0.get(), v1.get(), temp.get(), bits_a};
+            e = launch_sort_nee(c->stream, so);
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, which == 0 ? dout : dslot, cap * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(hlen.data(), dlen, hlen.size() * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(c, RT_E_HIP, std::string("debug sort: ") + hipGetErrorString(e));
-        else
-            for (int j = 0; j < kShards; ++j) out_len[j] = hlen[(size_t)j * kQStride];
     }
-    hipFree(dkey); hipFree(dslot); hipFree(dlen); hipFree(dout);
-    hipFree(k0); hipFree(k1); hipFree(v0); hipFree(v1); hipFree(temp);
-    if (!rc) rc = mark_done(c, c->stream);
-    return rc;
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, which == 0 ? dout.get() : dslot.get(), cap * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(hlen.data(), dlen.get(), hlen.size() * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(c, RT_E_HIP, std::string("debug sort: ") + hipGetErrorString(e));
+    for (int j = 0; j < kShards; ++j) out_len[j] = hlen[(size_t)j * kQStride];
+    return mark_done(c, c->stream);
 }
 
 static int impl_rt_debug_samples(rt_ctx* c, int n, const int32_t* pixel_ids, const int32_t* indices, rt_sample_record* out) {
@@ -2635,34 +2551,27 @@ static int impl_rt_debug_samples(rt_ctx* c, int n, const int32_t* pixel_ids, con
             return fail(c, RT_E_ARG, "StratifiedSampler without jitter supports indices < SamplesPerPixel");
     }
     hipSetDevice(c->device);
-    if ((rc = ensure_workspace(c, (size_t)n, false))) return rc;
+    Work& w = c->ws[0];
+    if ((rc = ensure_workspace(c, w, (size_t)n, false))) return rc;
     if ((rc = order_after_previous(c, c->stream))) return rc;
-    int *dp = nullptr, *di = nullptr;
-    float* dout = nullptr;
+    DevBuf<int> dp, di;
+    DevBuf<float> dout;
     static_assert(sizeof(rt_sample_record) == 39 * 4, "record layout");
-    if (dalloc(&dp, n) || dalloc(&di, n) || dalloc(&dout, (size_t)n * 39)) rc = fail(c, RT_E_OOM, "record buffers");
-    if (!rc) {
-        hipMemcpy(dp, pixel_ids, 4 * (size_t)n, hipMemcpyHostToDevice);
-        hipMemcpy(di, indices, 4 * (size_t)n, hipMemcpyHostToDevice);
-        SampleIds ids{nullptr, 1, 0, dp, di};
-        GenOut go{c->ws[0].rayO, c->ws[0].rayD, c->ws[0].lamA, c->ws[0].lamB, c->ws[0].pdfA,
-                  c->ws[0].pdfB, RecView{nullptr, 0, 0}, 0, 1};
-        DevFilm fd = dev_film(c);
-        TraceIO tio{c->ws[0].rayO, c->ws[0].rayD, QueueView{nullptr, shard_stride(n, 1), n, 1}, c->cull ? 1 : 0, c->ws[0].hitB,
-                    c->ws[0].hitPrim, nullptr, 1};
-        ShadeRefIO sio = shade_ref_io(c);
-        sio.rayD = c->ws[0].rayD; sio.lamA = c->ws[0].lamA; sio.lamB = c->ws[0].lamB; sio.pdfA = c->ws[0].pdfA; sio.pdfB = c->ws[0].pdfB;
-        sio.hitB = c->ws[0].hitB; sio.hitPrim = c->ws[0].hitPrim;
-        RecordIO rio{n, c->ws[0].rayO, c->ws[0].rayD, c->ws[0].lamA, c->ws[0].lamB, c->ws[0].pdfA, c->ws[0].pdfB, c->ws[0].hitB, c->ws[0].hitPrim, dout, 39, 1};
-        if (launch_generate(c->stream, 0, n, ids, dev_camera(c->cam), smp, fd, go) != hipSuccess ||
-            launch_trace_closest(c->stream, 0, c->dsc.qcap, lane_scene(c, c->ws[0]), tio, c->d_ctr) != hipSuccess ||
-            launch_records(c->stream, c->dsc, c->d_spec, fd, sio, rio) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess ||
-            hipMemcpy(out, dout, sizeof(rt_sample_record) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(c, RT_E_HIP, std::string("debug samples: ") + hipGetErrorString(hipGetLastError()));
-    }
-    hipFree(dp); hipFree(di); hipFree(dout);
-    return rc;
+    if (dp.reserve(n) || di.reserve(n) || dout.reserve((size_t)n * 39)) return fail(c, RT_E_OOM, "record buffers");
+    hipMemcpy(dp.get(), pixel_ids, 4 * (size_t)n, hipMemcpyHostToDevice);
+    hipMemcpy(di.get(), indices, 4 * (size_t)n, hipMemcpyHostToDevice);
+    SampleIds ids{nullptr, 1, 0, dp.get(), di.get()};
+    const RefIO r = ref_io(c, w.b, n, 1);
+    DevFilm fd = dev_film(c);
+    RecordIO rio{n, r.go.rayO, r.go.rayD, r.go.lamA, r.go.lamB, r.go.pdfA, r.go.pdfB, r.tio.hitB, r.tio.hitPrim, dout.get(),
+                 39, 1};
+    if (launch_generate(c->stream, 0, n, ids, dev_camera(c->cam), smp, fd, r.go) != hipSuccess ||
+        launch_trace_closest(c->stream, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()) != hipSuccess ||
+        launch_records(c->stream, c->dsc, c->d_spec.get(), fd, r.sio, rio) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess ||
+        hipMemcpy(out, dout.get(), sizeof(rt_sample_record) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, RT_E_HIP, std::string("debug samples: ") + hipGetErrorString(hipGetLastError()));
+    return RT_OK;
 }
 
 // ---- multi-device wrappers: configuration goes to every device of the context -------------------------------
@@ -2717,22 +2626,8 @@ static int impl_rt_create(const rt_options* opt, rt_ctx** out) {
 
 static void impl_rt_destroy(rt_ctx* c) {
     if (!c) return;
-    for (size_t j = 0; j < c->peers.size(); ++j) {
-        rt_ctx* p = c->peers[j];
-        hipSetDevice(p->device);
-        if (p->stream) hipStreamSynchronize(p->stream);
-        if (p->xfer) hipFree(p->xfer);
-        if (p->gathered) hipEventDestroy(p->gathered);
-        destroy_one(p);
-    }
-    hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    for (rt_ctx::PeerLink& L : c->links) {
-        if (L.work0) hipFree(L.work0);
-        if (L.xfer0) hipFree(L.xfer0);
-    }
-    if (c->gathered) hipEventDestroy(c->gathered);
-    destroy_one(c);
+    for (rt_ctx* p : c->peers) destroy_one(p);  // (each on its own device; its exchange buffer with it)
+    destroy_one(c);                             // the peer links' buffers live on c's device
 }
 
 static int impl_rt_scene_upload(rt_ctx* c, const rt_scene_desc* s) {

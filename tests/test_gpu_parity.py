@@ -145,6 +145,35 @@ def test_concurrent_batches_film_bitexact(oracle_lib, monkeypatch, lanes, scene_
     assert np.array_equal(bits(f2), bits(fo))
 
 
+def test_context_reconfigure_film_bitexact(oracle_lib, monkeypatch):
+    """One context configured six times in a row: the lanes' batch buffers are released and re-allocated whenever the
+    pass flips between the reference and the path layout or a batch outgrows them, and the sort, fallback, shadow and
+    NEE groups come and go with the scenes.  Every film is the oracle's bit for bit (tolerance 0)."""
+    monkeypatch.setenv("RTMI_BATCH_SAMPLES", str(16 * 16 * 2))   # every path pass here: >= 2 batches, two lanes
+    monkeypatch.setenv("RTMI_LANES", "2")
+    steps = [
+        scene.cfg0_reference(res=(32, 32), frequency=16, n_index=3),          # reference layout
+        scene.cfg_cornell(res=(48, 40), spp_side=2),                          # flip to path, growth
+        scene.cfg3_blob(res=(48, 40), spp_side=2, max_depth=3, frequency=20),  # sort, fallback and shadow groups
+        scene.cfg4_mixed(res=(40, 24), spp=(2, 2), frequency=16),             # NEE workspace, material bins
+        scene.cfg0_reference(res=(64, 64), frequency=16, n_index=3),          # flip back, growth
+        scene.cfg_cornell(res=(16, 16), spp_side=2),                          # path again, smaller than before
+    ]
+    g = Renderer()
+    for k, cfg in enumerate(steps):
+        g.configure(cfg)
+        o = oracle_lib.OracleScene(cfg)
+        fg = g.render_pass(cfg.index_begin, cfg.index_end)
+        fo = o.render(cfg.index_begin, cfg.index_end)
+        bad = np.any(bits(fg) != bits(fo), axis=1)
+        assert bad.sum() == 0, f"step {k} ({cfg.name}): {bad.sum()} pixels differ"
+        if k == 0:
+            pix, idx = np.array([0, 33, 500, 1023]), np.array([0, 2, 1, 2])
+            rg, ro_ = records_to_arrays(g.samples(pix, idx)), records_to_arrays(o.samples(pix, idx))
+            for key in ("lam", "pdf", "ro", "rd", "prim", "b", "L", "rgb", "weight"):
+                assert np.array_equal(bits(rg[key]), bits(ro_[key])), key
+
+
 @pytest.mark.parametrize("dfs", [0, 1])
 def test_shadow_queue_film_bitexact(oracle_lib, monkeypatch, dfs):
     """Multi-level octree with the NEE shadow rays queued and traced by k_path_shadow (RTMI_SHADOW_QUEUE=1), BFS
