@@ -465,6 +465,7 @@ struct Batch {
     DevBuf<float4> pdfA, pdfB, hitB;
     DevBuf<float4> rec;           // path mode: one 128-B record per slot (rt_internal.h R_*)
     DevBuf<int> hitPrim;
+    DevBuf<float4> hitD;          // path mode: (direction, prim) per compacted hit record (TraceIO hq_d)
     // coherence sort of path queues (multi-level octrees): side queue (interleaved pairs like ray), radix-sort buffers
     DevBuf<float4> sRay;
     DevBuf<int> sS, sVals, sValsAlt;       // sS: the sort permutation (TraceIO perm)
@@ -533,6 +534,9 @@ struct Knobs {
     // Morton sort of the NEE queue (mixed multi-level scenes; RTMI_SORT_NEE="on[/bits]"): CFG4 337 -> 364 at 9 bits
     // per axis (6 / 7 bits: 353 / 356; CFG5 334 -> 355 at 7)
     int sort_nee = 1, sort_nee_bits = 8;  // (r03, device radix sort: 8 bits = 3 passes, CFG4 +1.5 % over 9 bits = 4 passes)
+    // single-leaf simple path, depths >= 1: the trace appends its hits to a dense hit queue and the shade runs only
+    // those (TraceIO hq_d; Cornell +4.2 %, r07_ab4).  RTMI_HIT_COMPACT=0: every queue position is shaded (A/B)
+    int hit_compact = 1;
     size_t batch_samples = 0;  // samples in flight per batch (0: 16 Mi single leaf, 32 Mi multi-level; RTMI_BATCH_SAMPLES)
 };
 
@@ -570,6 +574,7 @@ static Knobs read_knobs() {
     }
     if (const char* e = std::getenv("RTMI_SORT_NEE")) std::sscanf(e, "%d/%d", &k.sort_nee, &k.sort_nee_bits);
     k.sort_nee_bits = std::max(1, std::min(9, k.sort_nee_bits));
+    if (const char* e = std::getenv("RTMI_HIT_COMPACT")) k.hit_compact = std::atoi(e) != 0;
     if (const char* e = std::getenv("RTMI_BATCH_SAMPLES")) k.batch_samples = (size_t)std::max(0L, std::atol(e));
     return k;
 }
@@ -709,7 +714,13 @@ int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path) {
     if (!w.film_done) HIPCHK(c, hipEventCreateWithFlags(&w.film_done, hipEventDisableTiming));
     if ((rc = ensure_ring(c, w))) return rc;
     Batch& b = w.b;
-    if (b.capacity(path) >= n) return RT_OK;
+    // the compacted hit records' (direction, prim) stream, sized like hitB (RTMI_HIT_COMPACT: the single-leaf
+    // simple path; the scene may have changed since the batch buffers were allocated)
+    const bool hit_d = path && c->knobs.hit_compact && c->dsc.qcap == 1 && !c->dsc.full;
+    if (b.capacity(path) >= n) {
+        if (hit_d) HIPCHK(c, b.hitD.reserve(n));
+        return RT_OK;
+    }
     b = Batch{};  // every batch buffer of the lane, the sort, shadow and NEE groups included
     // path mode: queue arrays hold 2 ping-pong queues of n entries each
     size_t nq = path ? 2 * n : n;
@@ -720,6 +731,7 @@ int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path) {
     HIPCHK(c, b.hitB.reserve(n)); HIPCHK(c, b.hitPrim.reserve(n));
     if (path) {
         HIPCHK(c, b.rec.reserve((size_t)kRecF4 * n));
+        if (hit_d) HIPCHK(c, b.hitD.reserve(n));
     } else {
         HIPCHK(c, b.lamA.reserve(n)); HIPCHK(c, b.lamB.reserve(n));
     }
@@ -1226,6 +1238,15 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
                 }
                 TraceIO tio{cO, cD, qv, 0, b.hitB.get(), b.hitPrim.get(), dyn ? qc_cur + kQTraceTicket : nullptr, 1};
                 if (depth > 0 && !efilter) tio.zero = qc_nxt;
+                // single-leaf simple path, bounce depths: the trace appends its hits to a dense hit queue and the shade
+                // runs only those.  The length word is this queue's shadow-queue length, which single-leaf scenes
+                // never use (zero before the launch like the rest of the region).  Depth 0 keeps its dense queue:
+                // slot = position, and the lean path writes L = 0 for the camera misses there.
+                const bool hitc = kn.hit_compact && c->dsc.qcap == 1 && !c->dsc.full && depth > 0;
+                if (hitc) {
+                    tio.hq_d = b.hitD.get();
+                    tio.hq_len = qc_cur + kQShadowLen;
+                }
                 if (c->dsc.qcap != 1) {  // ambiguous rays listed for k_trace_fallback (the trace holds no BFS)
                     tio.fb_pos = w.tfb.get();
                     tio.fb_len = qc_cur + kQTraceFallback;
@@ -1257,7 +1278,11 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
                 pio.lean = lean;
                 pio.rayO = cO; pio.rayD = cD; pio.q = qv;
                 pio.hitB = b.hitB.get(); pio.hitPrim = b.hitPrim.get();
-                pio.nO = b.rayO() + 2 * (size_t)nxt * qs; pio.nD = pio.nO + 1;
+                if (hitc) {  // items = the hit records (PathIO hq_d)
+                    pio.q = QueueView{tio.hq_len, Sq[l], 0, nsh};
+                    pio.hq_d = tio.hq_d;
+                }
+                pio.nO =b.rayO() + 2 * (size_t)nxt * qs; pio.nD = pio.nO + 1;
                 pio.nCount = qc_nxt + kQLen;
                 pio.rec = rv; pio.pdfA = b.pdfA.get(); pio.pdfB = b.pdfB.get();
                 pio.depth = depth; pio.max_depth = c->integ.max_depth;

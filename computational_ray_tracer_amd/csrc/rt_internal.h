@@ -301,6 +301,12 @@ struct TraceIO {
     // path mode, depths >= 1: the next queue's counter region (kQRegion ints), zeroed by block 0 of this kernel
     // instead of a memset launch (no kernel of the depth touches it before the shade that appends to it)
     int* zero = nullptr;
+    // single-leaf simple path, depths >= 1 (RTMI_HIT_COMPACT): the hits alone are appended to a dense hit queue — one
+    // record per hit, (b0, b1, b2, bits(slot)) at hitB[h] and (d.xyz, bits(prim)) at hq_d[h], h < *hq_len (zero
+    // before the launch) — and nothing is stored at the ray's own position, so the shade kernel runs no item for a
+    // miss and does not read the ray queue.  nullptr: hitB / hitPrim at the ray's queue position.
+    float4* hq_d = nullptr;
+    int* hq_len = nullptr;
 };
 
 // Material binning of a mixed multi-level scene's bounce (k_bin_materials, after the trace): every hit's queue
@@ -360,6 +366,9 @@ struct PathIO {
     int* ticket;  // per-shard chunk tickets (zeroed before the launch) or nullptr: static chunks
     RayKeyIO nkey;  // multi-level scenes: the coherence-sort key of every appended ray (rt_sort.hip)
     const int* bin_idx = nullptr;  // material-binned shade: item i of q is queue position bin_idx[i] (BinIO)
+    // compacted hits (TraceIO hq_d; k_path_shade<1, true>): q is the hit queue, item h's record is hitB[h] = (b0, b1,
+    // b2, bits(slot)) and hq_d[h] = (the ray's direction, bits(prim >= 0)); rayO, rayD and hitPrim are not read
+    const float4* hq_d = nullptr;
 };
 
 // Shadow queue (multi-level octrees): the shade kernel appends NEE shadow rays {o, tMax}, {d, slot} and their

@@ -965,7 +965,10 @@ __device__ __forceinline__ int traverse(const DevScene& sc, int set, V3 o, V3 d,
                         const int c = __builtin_ctzll(cm) >> 1;
                         if (!(entry(c) > cut)) test_cluster(c);
                     }
-                    if (!(t2 <= t1 + (t1 * 0x1p-16f + sc.wabs))) {  // decided (t1 = inf: no hit at all)
+                    // decided.  (No hit at all: t1 = t2 = inf, inf <= inf, so such a ray is not decided here but
+                    // takes the leaf-order pass, which rejects the same candidates again; an exact early-out
+                    // `if (w1 < 0) return -1` measured no gain on the Cornell box, r07_ab2)
+                    if (!(t2 <= t1 + (t1 * 0x1p-16f + sc.wabs))) {
                         if (w1 >= 0) {
                             rb0 = c0; rb1 = c1; rb2 = c2; rt = t1;
                             return __float_as_int(RT_LEAF1(tiles, r.x, w1)[2].y);
@@ -1619,8 +1622,8 @@ __device__ __forceinline__ int traverse_bvh(const DevScene& sc, int set, V3 o, V
 // The analytic shapes after the octree's closest hit, with the running tMax (hitB = the object-space
 // point for a shape), then the hit record at queue position p.
 template <bool CULL>
-__device__ __forceinline__ int finish_closest(const DevScene& sc, const TraceIO& io, int p, float4 o4, float4 d4,
-                                              int prim, float b0, float b1, float b2, float t) {
+__device__ __forceinline__ void closest_shapes(const DevScene& sc, float4 o4, float4 d4, int& prim, float& b0,
+                                               float& b1, float& b2, float& t) {
     if (sc.n_shapes) {
         float tm = prim >= 0 ? t : 3.402823466e+38f;
         for (int si = 0; si < sc.n_shapes; ++si) {
@@ -1632,6 +1635,11 @@ __device__ __forceinline__ int finish_closest(const DevScene& sc, const TraceIO&
             }
         }
     }
+}
+template <bool CULL>
+__device__ __forceinline__ int finish_closest(const DevScene& sc, const TraceIO& io, int p, float4 o4, float4 d4,
+                                              int prim, float b0, float b1, float b2, float t) {
+    closest_shapes<CULL>(sc, o4, d4, prim, b0, b1, b2, t);
     io.hitB[p] = make_float4(b0, b1, b2, t);
     io.hitPrim[p] = prim;
     return prim;
@@ -1645,7 +1653,8 @@ __device__ __forceinline__ int finish_closest(const DevScene& sc, const TraceIO&
 
 // FBL (multi-level scenes, path mode: io.fb_pos): the BVH walk alone, the ambiguous rays listed for k_trace_fallback;
 // otherwise the reference BFS runs inline for them.
-template <int QCAP, bool FBL>
+// HQ (single leaf, TraceIO hq_d): the hits are appended to the dense hit queue.
+template <int QCAP, bool FBL, bool HQ = false>
 __global__ void __launch_bounds__(kBlock) RT_WAVES_ATTR(QCAP) k_trace_closest(DevScene sc, TraceIO io, unsigned long long* ctr) {
     stage_scene<QCAP, false>(sc, io.set);
     if (io.zero && blockIdx.x == 0)
@@ -1675,7 +1684,50 @@ __global__ void __launch_bounds__(kBlock) RT_WAVES_ATTR(QCAP) k_trace_closest(De
     // no block-level synchronisation here.  Static chunks (single leaf, dense queues) or per-wave tickets.  One shard
     // (single leaf): a thread's items are k(i) = (block + (i / S) grid) S kBlock + (i % S) kBlock + thread,
     // S = kStaticItems, and the next item's ray is loaded while the current one is traced.
-    if (!io.ticket && io.q.ns == 1) {
+    if constexpr (HQ) {
+        // Compacted hits (TraceIO hq_d; one shard, static chunks): the same items in the same order, but every thread
+        // of the block walks the block's chunks to their end (block-uniform, dead lanes idle); a chunk's first hit
+        // record waits in registers and both are appended after the second (one atomic and one round of barriers
+        // per chunk, as the shade's bounce rays; no LDS beyond the append's: in two-lane mode the trace's LDS
+        // footprint decides how many shade blocks share its CU).  The record carries what the shade reads of the
+        // ray: its direction and its slot (the origin's w).
+        static_assert(QCAP == 1 && kStaticItems == 2, "a chunk's first record is parked, its second appends both");
+        __shared__ int hq_lds[2 * (kBlock / 64) + 1];
+        const int n = q_len(io.q, 0);
+        int k = blockIdx.x * kChunk + (int)threadIdx.x;
+        float4 o4 = make_float4(0, 0, 0, 0), d4 = o4;
+        if (k < n) { o4 = io.rayO[k << io.rsh]; d4 = io.rayD[k << io.rsh]; }
+        float4 rb0 = o4, rd0 = o4;
+        for (int c = blockIdx.x; c * kChunk < n; c += gridDim.x) {
+#pragma unroll 1
+            for (int r = 0; r < kStaticItems; ++r) {  // (one copy of the traversal: no unrolling)
+                const int kn = r + 1 < kStaticItems ? k + kBlock : (c + (int)gridDim.x) * kChunk + (int)threadIdx.x;
+                float4 on = o4, dn = d4;
+                if (kn < n) { on = io.rayO[kn << io.rsh]; dn = io.rayD[kn << io.rsh]; }
+                float b0 = 0, b1 = 0, b2 = 0, t = 0;
+                int prim = -1;
+                if (k < n) {
+                    prim = traverse_any<QCAP, false>(sc, io.set, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z),
+                                                     3.402823466e+38f, b0, b1, b2, t, nn, nt, nfb);
+                    closest_shapes<false>(sc, o4, d4, prim, b0, b1, b2, t);
+                    nh += prim >= 0;
+                    nr += 1;
+                }
+                const float4 rb = make_float4(b0, b1, b2, o4.w), rd = make_float4(d4.x, d4.y, d4.z, __int_as_float(prim));
+                if (r == 0) {
+                    rb0 = rb;
+                    rd0 = rd;
+                } else {
+                    const bool h0 = __float_as_int(rd0.w) >= 0;
+                    int p0, p1;
+                    block_append2(io.hq_len, h0, prim >= 0, hq_lds, p0, p1);
+                    if (h0) { io.hitB[p0] = rb0; io.hq_d[p0] = rd0; }
+                    if (prim >= 0) { io.hitB[p1] = rb; io.hq_d[p1] = rd; }
+                }
+                k = kn; o4 = on; d4 = dn;
+            }
+        }
+    } else if (!io.ticket && io.q.ns == 1) {
         const int n = q_len(io.q, 0);
         auto item = [&](int i) {
             return (blockIdx.x + (i / kStaticItems) * gridDim.x) * kChunk + (i % kStaticItems) * kBlock +
@@ -2049,7 +2101,8 @@ __device__ __forceinline__ bool cosine_bounce(float u0, float u1, V3 nrm, V3& wi
     return true;
 }
 
-template <int QCAP>
+// HQ (single leaf, PathIO hq_d): the items are the trace kernel's compacted hit records instead of queue positions.
+template <int QCAP, bool HQ = false>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCAP == 1 ? RT_SHADE1_WAVES : RT_SHADE_WAVES))) k_path_shade(DevScene sc, const DevSpectra* sp, DevSampler smp,
                                                                          DevFilm film, SampleIds ids, PathIO io,
                                                                          unsigned long long* ctr, ShadowQueueIO shq) {
@@ -2083,9 +2136,20 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
         if (live) {
             // (the ray's origin carries its slot; at depth 0 the queue is k_generate's dense camera queue, slot = k,
             // so the slot's state loads need not wait for the ray's)
-            slot = io.depth == 0 ? k : __float_as_int(io.rayO[2 * k].w);
-            const int prim = io.hitPrim[k];
-            if (prim >= 0) {
+            // HQ: item k is a hit record — barycentrics and slot, the ray's direction and prim >= 0 — in two dense
+            // streams, so the ray queue is not read at all
+            int prim;
+            float4 hq = make_float4(0, 0, 0, 0), hd = hq;
+            if constexpr (HQ) {
+                hq = io.hitB[k];
+                hd = io.hq_d[k];
+                slot = __float_as_int(hq.w);
+                prim = __float_as_int(hd.w);
+            } else {
+                slot = io.depth == 0 ? k : __float_as_int(io.rayO[2 * k].w);
+                prim = io.hitPrim[k];
+            }
+            if (HQ || prim >= 0) {
                 float lam[8], beta[8];
                 rload8(io.rec, slot, R_LAM, lam);
                 if (d0) {
@@ -2105,7 +2169,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                 }
                 V3 p0 = v3(P0.x, P0.y, P0.z), p1 = v3(P1.x, P1.y, P1.z), p2 = v3(P2.x, P2.y, P2.z);
                 V3 ng = vnorm(vcross(vsub(p0, p2), vsub(p1, p2)));  // Shapes.h:1073
-                const float4 d4 = io.rayD[2 * k];
+                const float4 d4 = HQ ? hd : io.rayD[2 * k];
                 V3 rayd = vnorm(v3(d4.x, d4.y, d4.z));
                 if (mt.w > 0) {
                     if (io.depth == 0 && vdot(ng, rayd) < 0) {
@@ -2119,7 +2183,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                 } else if (io.depth < io.max_depth) {
                     V3 nrm = ng;
                     if (vdot(nrm, rayd) > 0) nrm = v3(-nrm.x, -nrm.y, -nrm.z);
-                    const float4 hb = io.hitB[k];
+                    const float4 hb = HQ ? hq : io.hitB[k];
                     V3 p = vadd(vadd(vmul(p0, hb.x), vmul(p1, hb.y)), vmul(p2, hb.z));
                     float off = 1e-4f * (1.0f + max3f(fabsf(p.x), fabsf(p.y), fabsf(p.z)));
                     V3 po = vadd(p, vmul(nrm, off));
@@ -3109,7 +3173,14 @@ hipError_t launch_trace_closest(hipStream_t st, int grid, int qcap, const DevSce
         break;
     switch (qcap) {
         RT_TRACE_CASE(0)
-        case 1: hipLaunchKernelGGL((k_trace_closest<1, false>), dim3(resident_grid(k_trace_closest<1, false>, gb, grid)), b, 0, st, sc, io, ctr); break;
+        case 1:
+            if (io.hq_len) {  // compacted hits: static chunks of a one-shard queue only
+                if (io.ticket || io.q.ns != 1 || !io.hq_d) return hipErrorInvalidValue;
+                hipLaunchKernelGGL((k_trace_closest<1, false, true>), dim3(resident_grid(k_trace_closest<1, false, true>, gb, grid)), b, 0, st, sc, io, ctr);
+            } else {
+                hipLaunchKernelGGL((k_trace_closest<1, false>), dim3(resident_grid(k_trace_closest<1, false>, gb, grid)), b, 0, st, sc, io, ctr);
+            }
+            break;
         RT_TRACE_CASE(16)
         default: return hipErrorInvalidValue;
     }
@@ -3190,6 +3261,9 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
         else if (sc.full)                                                                                        \
             hipLaunchKernelGGL((k_path_shade_full<Q, 0>), dim3(resident_grid(k_path_shade_full<Q, 0>, gb, grid)), b, 0, \
                                st, sc, sp, smp, film, ids, io, nee);                                             \
+        else if (Q == 1 && io.hq_d)                                                                              \
+            hipLaunchKernelGGL((k_path_shade<1, true>), dim3(resident_grid(k_path_shade<1, true>, gb, grid)), b, 0, \
+                               st, sc, sp, smp, film, ids, io, ctr, shq);                                        \
         else                                                                                                     \
             hipLaunchKernelGGL(k_path_shade<Q>, dim3(resident_grid(k_path_shade<Q>, gb, grid)), b, 0, st, sc, sp,  \
                                smp, film, ids, io, ctr, shq);                                                    \
