@@ -25,7 +25,7 @@ RT_SENSOR_XYZ, RT_SENSOR_CANON_EOS_100D, RT_SENSOR_COUNT = 0, 1, 18
 RT_OCTREE_BUILD_DEVICE, RT_OCTREE_BUILD_HOST = 0, 1
 RT_ILLUM_D65, RT_ILLUM_A, RT_ILLUM_D50, RT_ILLUM_F1, RT_ILLUM_ACES_D60, RT_ILLUM_COUNT = 0, 1, 2, 3, 15, 16
 RT_INTEGRATOR_REFERENCE, RT_INTEGRATOR_PATH, RT_INTEGRATOR_PATH_MIS = 0, 1, 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 RT_MAX_DEVICES = 16
 QUEUE_SHARDS = 8  # RT_QUEUE_SHARDS
 
@@ -43,6 +43,20 @@ class rt_options(C.Structure):
 
 class rt_pixel(C.Structure):
     _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("w", C.c_float)]
+
+
+class rt_moment(C.Structure):
+    _fields_ = [("sum", C.c_float), ("sumsq", C.c_float)]
+
+
+class rt_adaptive_desc(C.Structure):
+    _fields_ = [("min_samples", C.c_int), ("step_samples", C.c_int), ("max_samples", C.c_int),
+                ("rel_error", C.c_float), ("abs_floor", C.c_float), ("reserved", C.c_int * 3)]
+
+
+class rt_adaptive_info(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("index_done", C.c_int), ("active_pixels", C.c_int),
+                ("active_blocks", C.c_int), ("samples", C.c_int64)]
 
 
 class rt_material(C.Structure):
@@ -130,6 +144,8 @@ EXPORTS = [
     "rt_debug_trace", "rt_debug_occluded", "rt_debug_samples", "rt_debug_sort",
     "rt_film_resolve_srgb", "rt_load_obj", "rt_mesh_free", "rt_image_write", "rt_rgb_to_sigmoid", "rt_rgb_fit_sigmoid",
     "rt_sensor_name", "rt_film_matrices",
+    "rt_adaptive_begin", "rt_adaptive_step", "rt_adaptive_read", "rt_adaptive_end", "rt_render_adaptive",
+    "rt_debug_adaptive_select",
 ]
 
 _lib = None
@@ -199,6 +215,14 @@ def load_library(path=None):
         "rt_rgb_fit_sigmoid": ([P(C.c_float), P(C.c_float)], C.c_int),
         "rt_sensor_name": ([C.c_int], C.c_char_p),
         "rt_film_matrices": ([C.c_void_p, P(C.c_float), P(C.c_float)], C.c_int),
+        "rt_adaptive_begin": ([C.c_void_p, P(rt_adaptive_desc)], C.c_int),
+        "rt_adaptive_step": ([C.c_void_p, P(rt_adaptive_info)], C.c_int),
+        "rt_adaptive_read": ([C.c_void_p, P(rt_pixel), P(rt_moment), P(C.c_float), P(C.c_int32), P(C.c_int)], C.c_int),
+        "rt_adaptive_end": ([C.c_void_p], C.c_int),
+        "rt_render_adaptive": ([C.c_void_p, P(rt_adaptive_desc), P(rt_pixel), P(rt_moment), P(rt_adaptive_info)],
+                               C.c_int),
+        "rt_debug_adaptive_select": ([C.c_void_p, P(rt_adaptive_desc), P(rt_pixel), P(rt_moment), P(C.c_float),
+                                      P(C.c_int32), P(C.c_int)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

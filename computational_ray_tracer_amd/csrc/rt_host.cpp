@@ -642,6 +642,24 @@ struct rt_ctx {
     std::vector<PeerLink> links;
     hipEvent_t gathered = nullptr;   // devices[0]: peers' pixels packed (multi-device) / peer: pass done
     DevBuf<float4> xfer;             // on a peer: its compact exchange buffer
+    // adaptive sampling session (rt_adaptive_*): device film and moments, the active pixel list (a
+    // subsequence of d_work, ping-ponged by the compaction), the per-block estimate and the compaction's scratch
+    struct Adaptive {
+        bool live = false;
+        rt_adaptive_desc desc{};
+        rt_adaptive_info info{};
+        DevBuf<float4> film;
+        DevBuf<float2> mom;
+        DevBuf<int> active[2];
+        int cur = 0;                 // active[cur] is the current list (info.active_pixels entries)
+        DevBuf<float> block_error;
+        DevBuf<int> converged, wave_count, wave_offset, totals;
+    } ad;
+    // what render_device_body renders: the full work list, or (inside rt_adaptive_step) the session's active list
+    // with its moment film
+    const int* pass_work = nullptr;
+    int pass_n = 0;
+    float2* pass_mom = nullptr;
 };
 
 namespace {
@@ -966,9 +984,9 @@ DevSampler dev_sampler(const rt_ctx* c) {
 }
 
 // sample ids of a batch starting at sample index b0 (s = i n_pixels + j)
-SampleIds sample_ids(const rt_ctx* c, int b0) {
-    SampleIds ids{c->d_work.get(), c->n_work, b0, nullptr, nullptr};
-    ids.np_div = make_intdiv((uint32_t)c->n_work);
+SampleIds sample_ids(const int* work, int n_work, int b0) {
+    SampleIds ids{work, n_work, b0, nullptr, nullptr};
+    ids.np_div = make_intdiv((uint32_t)n_work);
     return ids;
 }
 
@@ -1079,7 +1097,10 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
     if (c->smp.kind == RT_SAMPLER_STRATIFIED && !c->smp.jitter && ie > smp.spp)
         return fail(c, RT_E_ARG, "StratifiedSampler without jitter supports indices < SamplesPerPixel (samplers.h:83-87)");
     if ((rc = build_work(c))) return rc;
-    if (ie == ib || c->n_work == 0) return RT_OK;
+    // the pixels of this pass and their order: the full work list, or an adaptive session's active list
+    const int* const work = c->pass_work ? c->pass_work : c->d_work.get();
+    const int n_work = c->pass_work ? c->pass_n : c->n_work;
+    if (ie == ib || n_work == 0) return RT_OK;
     bool path = c->integ.kind == RT_INTEGRATOR_PATH || c->integ.kind == RT_INTEGRATOR_PATH_MIS;
     c->dsc.mis = c->integ.kind == RT_INTEGRATOR_PATH_MIS;
     c->dsc.full = c->scene_full || c->dsc.mis;
@@ -1088,9 +1109,9 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
     // +2.5 %, CFG4 +3.5 %, flat above, r06_ab23/24)
     const Knobs& kn = c->knobs;
     const size_t target = kn.batch_samples ? kn.batch_samples : (size_t)(c->dsc.qcap == 1 ? 16 : 32) << 20;
-    int B = (int)std::max<size_t>(1, target / (size_t)c->n_work);
+    int B = (int)std::max<size_t>(1, target / (size_t)n_work);
     B = std::min(B, ie - ib);
-    size_t nmax = (size_t)B * c->n_work;
+    size_t nmax = (size_t)B * n_work;
     // queue / hit capacity: the shards of the largest batch (>= nmax); single-leaf scenes use one shard
     const int nsh = c->dsc.qcap == 1 ? 1 : kShards;
     const size_t ncap = (size_t)nsh * (size_t)shard_stride((int)nmax, nsh);
@@ -1103,8 +1124,8 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
         if ((rc = ensure_workspace(c, w, ncap, false))) return rc;
         for (int b0 = ib; b0 < ie; b0 += B) {
             int nIdx = std::min(B, ie - b0);
-            int nS = nIdx * c->n_work;
-            SampleIds ids = sample_ids(c, b0);
+            int nS = nIdx * n_work;
+            SampleIds ids = sample_ids(work, n_work, b0);
             RefIO r = ref_io(c, w.b, nS, nsh);
             hipEvent_t e0 = ev_start(c, st);
             HIPCHK(c, launch_generate(st, c->grid, nS, ids, cam, smp, fd, r.go));
@@ -1112,8 +1133,9 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
             e0 = ev_start(c, st);
             HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), r.tio, d_ctr));
             ev_mark(c, st, ST_TRACE, e0);
-            r.sio.work_pixels = c->d_work.get(); r.sio.n_pixels = c->n_work; r.sio.n_index = nIdx;
+            r.sio.work_pixels = work; r.sio.n_pixels = n_work; r.sio.n_index = nIdx;
             r.sio.film = film;
+            r.sio.mom = c->pass_mom;
             e0 = ev_start(c, st);
             HIPCHK(c, launch_ref_shade_film(st, 0, c->dsc, d_spec, fd, r.sio, d_ctr));
             ev_mark(c, st, ST_FILM, e0);
@@ -1184,10 +1206,10 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
             hipStream_t s = lstream(l);
             const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
             nIdx[l] = std::min(B, ie - b0);
-            int nS = nIdx[l] * c->n_work;
+            int nS = nIdx[l] * n_work;
             nSq[l] = nS;
             Sq[l] = shard_stride(nS, nsh);  // every queue of this batch: shard j at [j S, j S + len_j)
-            SampleIds ids = sample_ids(c, b0);
+            SampleIds ids = sample_ids(work, n_work, b0);
             GenOut go{b.rayO(), b.rayD(), nullptr, nullptr, b.pdfA.get(), b.pdfB.get(), rv, lean, 1};
             // camera rays fill queue 0 densely (positions 0..nS-1: QueueView without lengths); both counter regions
             // start at zero: k_generate zeroes them (a memset launch here waited for the other lane's resident blocks
@@ -1205,7 +1227,7 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
                 const Batch& b = w.b;
                 hipStream_t s = lstream(l);
                 const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
-                SampleIds ids = sample_ids(c, g0 + l * B);
+                SampleIds ids = sample_ids(work, n_work, g0 + l * B);
                 int nxt = cur[l] ^ 1;
                 const float4* cO = b.rayO() + 2 * (size_t)cur[l] * qs;
                 const float4* cD = cO + 1;
@@ -1360,8 +1382,9 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
             hipStream_t s = lstream(l);
             const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
             if (last_film >= 0 && last_film != l) HIPCHK(c, hipStreamWaitEvent(s, c->ws[last_film].film_done, 0));
-            PathFilmIO fio{c->d_work.get(), c->n_work, nIdx[l], rv, b.pdfA.get(), b.pdfB.get(), film};
+            PathFilmIO fio{work, n_work, nIdx[l], rv, b.pdfA.get(), b.pdfB.get(), film};
             fio.lean = lean;
+            fio.mom = c->pass_mom;
             hipEvent_t e0 = ev_start(c, s);
             HIPCHK(c, launch_path_film(s, 0, d_spec, fd, fio, d_ctr));
             ev_mark(c, s, ST_FILM, e0);
@@ -2217,6 +2240,7 @@ static int film_set_one(rt_ctx* c, const rt_film_desc* d) {
     if (d->res_x <= 0 || d->res_y <= 0 || d->filter < RT_FILTER_BOX || d->filter > RT_FILTER_LANCZOS)
         return fail(c, RT_E_ARG, "invalid film");
     if ((size_t)d->res_x * d->res_y > ((size_t)1 << 27)) return fail(c, RT_E_LIMIT, "film too large");
+    if (c->ad.live) return fail(c, RT_E_STATE, "rt_film_set during an adaptive session (rt_adaptive_end first)");
     if (d->sensor < 0 || d->sensor >= RT_SENSOR_COUNT || d->sensor_illum < 0 || d->sensor_illum >= RT_ILLUM_COUNT)
         return fail(c, RT_E_ARG, "unknown sensor or sensor illuminant");
     hipSetDevice(c->device);
@@ -2280,6 +2304,7 @@ static int integrator_set_one(rt_ctx* c, const rt_integrator_desc* d) {
 static int set_shard_one(rt_ctx* c, int tile_size, int n_shards, int shard_id) {
     if (!c || tile_size <= 0 || tile_size % 8 || n_shards <= 0 || shard_id < 0 || shard_id >= n_shards)
         return c ? fail(c, RT_E_ARG, "invalid shard (tile_size must be a positive multiple of 8)") : RT_E_ARG;
+    if (c->ad.live) return fail(c, RT_E_STATE, "rt_set_shard during an adaptive session (rt_adaptive_end first)");
     c->tile = tile_size;
     c->n_shards = n_shards;
     c->shard_id = shard_id;
@@ -2305,6 +2330,213 @@ static int impl_rt_render_pass(rt_ctx* c, int ib, int ie, rt_pixel* film) {
     if ((rc = render_multi(c, ib, ie, c->d_film.get(), c->stream))) return rc;
     HIPCHK(c, hipMemcpyAsync(film, c->d_film.get(), n * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+// ---- adaptive sampling: a session's film, moments and active list stay on the device; a step renders
+// the next indices on the active list (render_device_body with the list in place of d_work), then estimates every
+// 8x8 block's error and compacts the list.  The host reads two ints per step: the new list length and the number
+// of blocks not converged.
+namespace {
+int adaptive_check_desc(rt_ctx* c, const rt_adaptive_desc* d, bool counts) {
+    if (counts) {
+        if (d->min_samples < 2) return fail(c, RT_E_ARG, "adaptive: min_samples must be at least 2 (a variance needs two samples)");
+        if (d->step_samples < 1) return fail(c, RT_E_ARG, "adaptive: step_samples must be at least 1");
+        if (d->max_samples < d->min_samples) return fail(c, RT_E_ARG, "adaptive: max_samples is below min_samples");
+        // (indices past spp: PermutationElement's cycle walk need not end for strata counts that are no power of two)
+        if (d->max_samples > dev_sampler(c).spp)
+            return fail(c, RT_E_ARG, "adaptive: max_samples exceeds the sampler's samples per pixel");
+    }
+    if (!std::isfinite(d->rel_error) || d->rel_error < 0) return fail(c, RT_E_ARG, "adaptive: rel_error must be finite and >= 0");
+    if (!std::isfinite(d->abs_floor) || d->abs_floor < 0) return fail(c, RT_E_ARG, "adaptive: abs_floor must be finite and >= 0");
+    return RT_OK;
+}
+
+int adaptive_blocks(const rt_ctx* c) { return ((c->film.res_x + 7) / 8) * ((c->film.res_y + 7) / 8); }
+
+// the estimate's outputs, the compaction's scratch and both active lists for the current film and work list
+int adaptive_reserve(rt_ctx* c) {
+    rt_ctx::Adaptive& a = c->ad;
+    const size_t nb = (size_t)adaptive_blocks(c), nw = (size_t)adaptive_waves(c->n_work);
+    HIPCHK(c, a.block_error.reserve(nb)); HIPCHK(c, a.converged.reserve(nb));
+    HIPCHK(c, a.wave_count.reserve(nw)); HIPCHK(c, a.wave_offset.reserve(nw));
+    HIPCHK(c, a.totals.reserve(2));
+    HIPCHK(c, a.active[0].reserve((size_t)c->n_work)); HIPCHK(c, a.active[1].reserve((size_t)c->n_work));
+    return RT_OK;
+}
+
+// block errors and flags from (film, mom), then in[0, n) compacted into out; blocks until the counts are read
+int adaptive_select(rt_ctx* c, const float4* film, const float2* mom, const rt_adaptive_desc& d, const int* in, int n,
+                    int* out, int* n_out, int* n_blocks, hipStream_t st) {
+    rt_ctx::Adaptive& a = c->ad;
+    const AdaptiveIO io{c->film.res_x, c->film.res_y, film, mom, d.rel_error, d.abs_floor, a.block_error.get(),
+                        a.converged.get(), a.totals.get()};
+    int t[2] = {0, 0};
+    HIPCHK(c, launch_adaptive_error(st, io));
+    HIPCHK(c, launch_adaptive_compact(st, io, in, n, out, a.wave_count.get(), a.wave_offset.get()));
+    HIPCHK(c, hipMemcpyAsync(t, a.totals.get(), sizeof(t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    *n_out = t[0];
+    *n_blocks = t[1];
+    return RT_OK;
+}
+
+void adaptive_release(rt_ctx* c) {
+    c->ad = rt_ctx::Adaptive{};  // (hipFree waits for the work that still uses the buffers)
+}
+}  // namespace
+
+static int impl_rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d) {
+    if (!c) return RT_E_ARG;
+    if (!d) return fail(c, RT_E_ARG, "adaptive: null descriptor");
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if (!c->peers.empty()) return fail(c, RT_E_STATE, "adaptive sampling supports one-device contexts only");
+    rt_ctx::Adaptive& a = c->ad;
+    if (a.live) return fail(c, RT_E_STATE, "an adaptive session is already open (rt_adaptive_end first)");
+    if ((rc = adaptive_check_desc(c, d, true))) return rc;
+    hipSetDevice(c->device);
+    if ((rc = build_work(c))) return rc;
+    if ((rc = adaptive_reserve(c))) return rc;
+    const size_t n = (size_t)c->film.res_x * c->film.res_y;
+    HIPCHK(c, a.film.reserve(n));
+    HIPCHK(c, a.mom.reserve(n));
+    hipStream_t st = c->stream;
+    if ((rc = order_after_previous(c, st))) return rc;
+    HIPCHK(c, hipMemsetAsync(a.film.get(), 0, n * sizeof(float4), st));
+    HIPCHK(c, hipMemsetAsync(a.mom.get(), 0, n * sizeof(float2), st));
+    HIPCHK(c, hipMemsetAsync(a.block_error.get(), 0, (size_t)adaptive_blocks(c) * sizeof(float), st));
+    if (c->n_work)
+        HIPCHK(c, hipMemcpyAsync(a.active[0].get(), c->d_work.get(), (size_t)c->n_work * sizeof(int),
+                                 hipMemcpyDeviceToDevice, st));
+    if ((rc = mark_done(c, st))) return rc;
+    a.cur = 0;
+    a.desc = *d;
+    a.info = rt_adaptive_info{};
+    a.info.active_pixels = c->n_work;
+    a.live = true;
+    return RT_OK;
+}
+
+static int impl_rt_adaptive_step(rt_ctx* c, rt_adaptive_info* info) {
+    if (!c) return RT_E_ARG;
+    rt_ctx::Adaptive& a = c->ad;
+    if (!a.live) return fail(c, RT_E_STATE, "no adaptive session is open (rt_adaptive_begin first)");
+    if (a.info.active_pixels > 0 && a.info.index_done < a.desc.max_samples) {
+        int rc = check_ready(c);
+        if (rc) return rc;
+        if (a.desc.max_samples > dev_sampler(c).spp)
+            return fail(c, RT_E_STATE, "adaptive: the sampler now has fewer samples per pixel than max_samples");
+        hipSetDevice(c->device);
+        const int ib = a.info.index_done;
+        const int k = a.info.iterations == 0 ? a.desc.min_samples : a.desc.step_samples;
+        const int ie = ib + std::min(k, a.desc.max_samples - ib);
+        const int n = a.info.active_pixels;
+        hipStream_t st = c->stream;
+        if ((rc = order_after_previous(c, st))) return rc;
+        c->pass_work = a.active[a.cur].get();
+        c->pass_n = n;
+        c->pass_mom = a.mom.get();
+        rc = render_device_body(c, ib, ie, a.film.get(), st);
+        c->pass_work = nullptr;
+        c->pass_n = 0;
+        c->pass_mom = nullptr;
+        int n_out = 0, n_blocks = 0;
+        if (!rc)
+            rc = adaptive_select(c, a.film.get(), a.mom.get(), a.desc, a.active[a.cur].get(), n,
+                                 a.active[a.cur ^ 1].get(), &n_out, &n_blocks, st);
+        const int rc2 = mark_done(c, st);
+        if (rc || rc2) return rc ? rc : rc2;
+        a.cur ^= 1;
+        a.info.samples += (int64_t)n * (ie - ib);
+        a.info.iterations += 1;
+        a.info.index_done = ie;
+        a.info.active_pixels = n_out;
+        a.info.active_blocks = n_blocks;
+    }
+    if (info) *info = a.info;
+    return RT_OK;
+}
+
+static int impl_rt_adaptive_read(rt_ctx* c, rt_pixel* film, rt_moment* mom, float* block_error, int32_t* active,
+                                 int* n_active) {
+    if (!c) return RT_E_ARG;
+    rt_ctx::Adaptive& a = c->ad;
+    if (!a.live) return fail(c, RT_E_STATE, "no adaptive session is open (rt_adaptive_begin first)");
+    hipSetDevice(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)c->film.res_x * c->film.res_y;
+    if (film) HIPCHK(c, hipMemcpy(film, a.film.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (mom) HIPCHK(c, hipMemcpy(mom, a.mom.get(), n * sizeof(float2), hipMemcpyDeviceToHost));
+    if (block_error)
+        HIPCHK(c, hipMemcpy(block_error, a.block_error.get(), (size_t)adaptive_blocks(c) * sizeof(float),
+                            hipMemcpyDeviceToHost));
+    if (active && a.info.active_pixels > 0)
+        HIPCHK(c, hipMemcpy(active, a.active[a.cur].get(), (size_t)a.info.active_pixels * sizeof(int),
+                            hipMemcpyDeviceToHost));
+    if (n_active) *n_active = a.info.active_pixels;
+    return RT_OK;
+}
+
+static int impl_rt_adaptive_end(rt_ctx* c) {
+    if (!c) return RT_E_ARG;
+    if (!c->ad.live) return fail(c, RT_E_STATE, "no adaptive session is open");
+    hipSetDevice(c->device);
+    adaptive_release(c);
+    return RT_OK;
+}
+
+static int impl_rt_render_adaptive(rt_ctx* c, const rt_adaptive_desc* d, rt_pixel* film, rt_moment* mom,
+                                   rt_adaptive_info* info) {
+    int rc = impl_rt_adaptive_begin(c, d);
+    if (rc) return rc;
+    rt_adaptive_info cur{};
+    do {
+        rc = impl_rt_adaptive_step(c, &cur);
+    } while (!rc && cur.active_pixels > 0 && cur.index_done < d->max_samples);
+    if (!rc) rc = impl_rt_adaptive_read(c, film, mom, nullptr, nullptr, nullptr);
+    if (rc) {  // close the session, keep the failing call's message
+        const std::string msg = c->err;
+        impl_rt_adaptive_end(c);
+        return fail(c, rc, msg);
+    }
+    if (info) *info = cur;
+    return impl_rt_adaptive_end(c);
+}
+
+static int impl_rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, const rt_pixel* film,
+                                         const rt_moment* mom, float* block_error, int32_t* active, int* n_active) {
+    if (!c) return RT_E_ARG;
+    if (!d || !film || !mom) return fail(c, RT_E_ARG, "adaptive select: descriptor, film and moments are required");
+    if (!c->have_film) return fail(c, RT_E_STATE, "film not set");
+    if (!c->peers.empty()) return fail(c, RT_E_STATE, "adaptive sampling supports one-device contexts only");
+    if (c->ad.live) return fail(c, RT_E_STATE, "rt_debug_adaptive_select during an adaptive session");
+    int rc = adaptive_check_desc(c, d, false);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    if ((rc = build_work(c))) return rc;
+    if ((rc = adaptive_reserve(c))) return rc;
+    const size_t n = (size_t)c->film.res_x * c->film.res_y;
+    DevBuf<float4> df;
+    DevBuf<float2> dm;
+    HIPCHK(c, df.reserve(n));
+    HIPCHK(c, dm.reserve(n));
+    HIPCHK(c, hipMemcpy(df.get(), film, n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dm.get(), mom, n * sizeof(float2), hipMemcpyHostToDevice));
+    rt_ctx::Adaptive& a = c->ad;
+    hipStream_t st = c->stream;
+    if ((rc = order_after_previous(c, st))) return rc;
+    int n_out = 0, n_blocks = 0;
+    rc = adaptive_select(c, df.get(), dm.get(), *d, c->d_work.get(), c->n_work, a.active[0].get(), &n_out, &n_blocks, st);
+    const int rc2 = mark_done(c, st);
+    if (rc || rc2) return rc ? rc : rc2;
+    if (block_error)
+        HIPCHK(c, hipMemcpy(block_error, a.block_error.get(), (size_t)adaptive_blocks(c) * sizeof(float),
+                            hipMemcpyDeviceToHost));
+    if (active && n_out > 0)
+        HIPCHK(c, hipMemcpy(active, a.active[0].get(), (size_t)n_out * sizeof(int), hipMemcpyDeviceToHost));
+    if (n_active) *n_active = n_out;
+    adaptive_release(c);
     return RT_OK;
 }
 
@@ -2727,6 +2959,26 @@ int rt_render_pass_device(rt_ctx* c, int ib, int ie, void* d_film, void* stream)
 }
 int rt_render_pass(rt_ctx* c, int ib, int ie, rt_pixel* film) {
     return guarded([&] { return impl_rt_render_pass(c, ib, ie, film); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d) {
+    return guarded([&] { return impl_rt_adaptive_begin(c, d); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_adaptive_step(rt_ctx* c, rt_adaptive_info* info) {
+    return guarded([&] { return impl_rt_adaptive_step(c, info); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_adaptive_read(rt_ctx* c, rt_pixel* film, rt_moment* mom, float* block_error, int32_t* active, int* n_active) {
+    return guarded([&] { return impl_rt_adaptive_read(c, film, mom, block_error, active, n_active); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_adaptive_end(rt_ctx* c) {
+    return guarded([&] { return impl_rt_adaptive_end(c); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_render_adaptive(rt_ctx* c, const rt_adaptive_desc* d, rt_pixel* film, rt_moment* mom, rt_adaptive_info* info) {
+    return guarded([&] { return impl_rt_render_adaptive(c, d, film, mom, info); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, const rt_pixel* film, const rt_moment* mom,
+                             float* block_error, int32_t* active, int* n_active) {
+    return guarded([&] { return impl_rt_debug_adaptive_select(c, d, film, mom, block_error, active, n_active); },
+                   [&](const std::string& m) { set_error(c, m); });
 }
 int rt_film_resolve(rt_ctx* c, const rt_pixel* film, uint8_t* out) {
     return guarded([&] { return impl_rt_film_resolve(c, film, out); }, [&](const std::string& m) { set_error(c, m); });

@@ -343,6 +343,7 @@ struct ShadeRefIO {
     float4* film;
     float albedo_c2, illum_c2, illum_scale;
     int rsh;  // ray k at rayD[k << rsh]
+    float2* mom = nullptr;  // adaptive session: per-pixel (sum, sumsq) updated with the film (k_ref_shade_film<true>)
 };
 
 // Coherence-sort key parameters of the bounce rays a shade kernel appends (ray_sort_key below).
@@ -446,6 +447,7 @@ struct PathFilmIO {
     float4* film;
     int lean;  // pdf = VisibleWavelengthsPDF(λ) recomputed here; 2: and divided as TerminateSecondary did when the
                // slot's R_MISC z flag is set (mixed scenes: dispersive glass)
+    float2* mom = nullptr;  // adaptive session: per-pixel (sum, sumsq) updated with the film (k_path_film<true>)
 };
 
 struct RecordIO {
@@ -512,5 +514,25 @@ hipError_t launch_resolve(hipStream_t st, int n, const float4* film, const float
                           const float* m_rgb_from_xyz, unsigned char* out, int srgb);
 hipError_t launch_film_gather(hipStream_t st, int n, const int* work, const float4* film, float4* out);
 hipError_t launch_film_scatter(hipStream_t st, int n, const int* work, const float4* in, float4* film);
+
+// Adaptive sampling (rt_adaptive.hip).  Blocks are the image-aligned 8x8 pixel blocks, row-major:
+// block (bx, by) = by * ceil(res_x / 8) + bx.
+struct AdaptiveIO {
+    int res_x, res_y;
+    const float4* film;      // res_x * res_y: w = the pixel's sample count n
+    const float2* mom;       // res_x * res_y: (sum, sumsq)
+    float rel_error, abs_floor;
+    float* block_error;      // per block: E
+    int* converged;          // per block: E <= rel_error
+    int* totals;             // written by the compaction's scan: [0] length of the compacted list, [1] blocks not
+                             // converged
+};
+// one wave64 per block: E and the converged flag of every block
+hipError_t launch_adaptive_error(hipStream_t st, const AdaptiveIO& io);
+// Stable compaction: out = the pixels of in[0, n) whose block is not converged, in the same order; *io.totals = their
+// number, io.totals[1] = the blocks not converged.  wave_count / wave_offset hold adaptive_waves(n) ints each.
+inline __host__ __device__ int adaptive_waves(int n) { return (n + 63) / 64; }
+hipError_t launch_adaptive_compact(hipStream_t st, const AdaptiveIO& io, const int* in, int n, int* out,
+                                   int* wave_count, int* wave_offset);
 
 }  // namespace rtmi

@@ -1993,8 +1993,18 @@ __device__ __forceinline__ void li_reference(const DevScene& sc, const DevSpectr
     }
 }
 
+// Moments of an adaptive session's pixel (rt_moment): one sample's v = (cr + cg) + cb of the clamped values the film
+// adds, sum += v, sumsq += v * v (float32, unfused: the build's -ffp-contract=off).
+__device__ __forceinline__ void moment_add(float2& m, float cr, float cg, float cb) {
+    const float v = (cr + cg) + cb;
+    m.x = m.x + v;
+    m.y = m.y + v * v;
+}
+
 // Film accumulation (RayTracerTestApp.h:330-337): each thread owns one pixel and adds the batch's sample
 // indices in increasing order — the same per-pixel summation order as the reference's passes.
+// MOM (adaptive sessions): the pixel's moments (io.mom) take every sample too, in the same order.
+template <bool MOM>
 __global__ void __launch_bounds__(kBlock) k_ref_shade_film(DevScene sc, const DevSpectra* sp, DevFilm film,
                                                            ShadeRefIO io, unsigned long long* ctr) {
     stage_spectra(sp);
@@ -2002,6 +2012,8 @@ __global__ void __launch_bounds__(kBlock) k_ref_shade_film(DevScene sc, const De
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < io.n_pixels; j += gridDim.x * blockDim.x) {
         int pixel = io.work_pixels[j];
         float4 f = io.film[pixel];
+        float2 m = make_float2(0.f, 0.f);
+        if constexpr (MOM) m = io.mom[pixel];
         for (int i = 0; i < io.n_index; ++i) {
             int s = i * io.n_pixels + j;
             float lam[8], pdf[8], L[8], rgb[3];
@@ -2010,13 +2022,17 @@ __global__ void __launch_bounds__(kBlock) k_ref_shade_film(DevScene sc, const De
             li_reference(sc, sp, io, s, lam, L);
             to_sensor_rgb_spk(sp, L, lam, pdf, film.imaging_ratio, rgb);
             const float w = 1.0f;  // FilterSample::weight (Box and Triangle both return 1)
-            f.x += w * gclamp(rgb[0], 0.0f, 1.0f);
-            f.y += w * gclamp(rgb[1], 0.0f, 1.0f);
-            f.z += w * gclamp(rgb[2], 0.0f, 1.0f);
+            const float cr = w * gclamp(rgb[0], 0.0f, 1.0f), cg = w * gclamp(rgb[1], 0.0f, 1.0f),
+                        cb = w * gclamp(rgb[2], 0.0f, 1.0f);
+            f.x += cr;
+            f.y += cg;
+            f.z += cb;
             f.w += w;
+            if constexpr (MOM) moment_add(m, cr, cg, cb);
             ++ns;
         }
         io.film[pixel] = f;
+        if constexpr (MOM) io.mom[pixel] = m;
     }
     count_add(ctr, C_SAMPLES, ns);
 }
@@ -3012,6 +3028,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
 }
 
 // sensor + film for path mode (pixel-owned, index order)
+template <bool MOM>  // (as k_ref_shade_film)
 __global__ void __launch_bounds__(kBlock) k_path_film(const DevSpectra* sp, DevFilm film, PathFilmIO io,
                                                       unsigned long long* ctr) {
     stage_spectra(sp);
@@ -3020,6 +3037,8 @@ __global__ void __launch_bounds__(kBlock) k_path_film(const DevSpectra* sp, DevF
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < io.n_pixels; j += gridDim.x * blockDim.x) {
         int pixel = io.work_pixels[j];
         float4 f = io.film[pixel];
+        float2 m = make_float2(0.f, 0.f);
+        if constexpr (MOM) m = io.mom[pixel];
         for (int i = 0; i < io.n_index; ++i) {
             int s = i * io.n_pixels + j;
             float lam[8], pdf[8], L[8], rgb[3];
@@ -3038,13 +3057,17 @@ __global__ void __launch_bounds__(kBlock) k_path_film(const DevSpectra* sp, DevF
             rload8(io.rec, s, R_L, L);
             to_sensor_rgb_spk(sp, L, lam, pdf, film.imaging_ratio, rgb);
             const float w = 1.0f;
-            f.x += w * gclamp(rgb[0], 0.0f, 1.0f);
-            f.y += w * gclamp(rgb[1], 0.0f, 1.0f);
-            f.z += w * gclamp(rgb[2], 0.0f, 1.0f);
+            const float cr = w * gclamp(rgb[0], 0.0f, 1.0f), cg = w * gclamp(rgb[1], 0.0f, 1.0f),
+                        cb = w * gclamp(rgb[2], 0.0f, 1.0f);
+            f.x += cr;
+            f.y += cg;
+            f.z += cb;
             f.w += w;
+            if constexpr (MOM) moment_add(m, cr, cg, cb);
             ++ns;
         }
         io.film[pixel] = f;
+        if constexpr (MOM) io.mom[pixel] = m;
     }
     count_add(ctr, C_SAMPLES, ns);
 }
@@ -3204,7 +3227,10 @@ hipError_t launch_trace_fallback(hipStream_t st, int grid, int qcap, const DevSc
 
 hipError_t launch_ref_shade_film(hipStream_t st, int grid, const DevScene& sc, const DevSpectra* sp, const DevFilm& film,
                                  const ShadeRefIO& io, unsigned long long* ctr) {
-    hipLaunchKernelGGL(k_ref_shade_film, dim3(grid_for(io.n_pixels, grid)), dim3(kBlock), 0, st, sc, sp, film, io, ctr);
+    if (io.mom)
+        hipLaunchKernelGGL(k_ref_shade_film<true>, dim3(grid_for(io.n_pixels, grid)), dim3(kBlock), 0, st, sc, sp, film, io, ctr);
+    else
+        hipLaunchKernelGGL(k_ref_shade_film<false>, dim3(grid_for(io.n_pixels, grid)), dim3(kBlock), 0, st, sc, sp, film, io, ctr);
     return hipGetLastError();
 }
 
@@ -3330,7 +3356,10 @@ hipError_t launch_occluded(hipStream_t st, int qcap, const DevScene& sc, int n, 
 
 hipError_t launch_path_film(hipStream_t st, int grid, const DevSpectra* sp, const DevFilm& film, const PathFilmIO& io,
                             unsigned long long* ctr) {
-    hipLaunchKernelGGL(k_path_film, dim3(resident_grid(k_path_film, grid_for(io.n_pixels, grid), grid)), dim3(kBlock), 0, st, sp, film, io, ctr);
+    if (io.mom)
+        hipLaunchKernelGGL(k_path_film<true>, dim3(resident_grid(k_path_film<true>, grid_for(io.n_pixels, grid), grid)), dim3(kBlock), 0, st, sp, film, io, ctr);
+    else
+        hipLaunchKernelGGL(k_path_film<false>, dim3(resident_grid(k_path_film<false>, grid_for(io.n_pixels, grid), grid)), dim3(kBlock), 0, st, sp, film, io, ctr);
     return hipGetLastError();
 }
 

@@ -67,6 +67,76 @@ class Renderer:
         self._chk("rt_render_pass_device", self.lib.rt_render_pass_device(
             self.h, index_begin, index_end, C.c_void_p(film_ptr), C.c_void_p(stream_ptr or 0)))
 
+    # ---- adaptive sampling (rt_adaptive_*) ------------------------------------------------------
+    @staticmethod
+    def _adaptive_desc(min_samples=2, step_samples=1, max_samples=2, rel_error=0.0, abs_floor=1e-3):
+        d = capi.rt_adaptive_desc()
+        d.min_samples, d.step_samples, d.max_samples = int(min_samples), int(step_samples), int(max_samples)
+        d.rel_error, d.abs_floor = float(rel_error), float(abs_floor)
+        return d
+
+    @staticmethod
+    def _adaptive_info(i):
+        return {k: getattr(i, k) for k, _ in i._fields_}
+
+    def n_blocks(self):
+        """Image-aligned 8x8 blocks of the film: (columns, rows); block (bx, by) is entry by * columns + bx."""
+        return (self.res[0] + 7) // 8, (self.res[1] + 7) // 8
+
+    def render_adaptive(self, min_samples, step_samples, max_samples, rel_error, abs_floor=1e-3):
+        """rt_render_adaptive: (film float32 [W*H, 4], moments float32 [W*H, 2] = (sum, sumsq), info dict).  A pixel's
+        film.w is the number of indices it took: min_samples, then step_samples more per iteration while its 8x8
+        block's error is above rel_error, max_samples at most."""
+        d = self._adaptive_desc(min_samples, step_samples, max_samples, rel_error, abs_floor)
+        film = self.new_film()
+        mom = np.zeros((self.res[0] * self.res[1], 2), np.float32)
+        info = capi.rt_adaptive_info()
+        self._chk("rt_render_adaptive", self.lib.rt_render_adaptive(
+            self.h, C.byref(d), film.ctypes.data_as(C.POINTER(capi.rt_pixel)),
+            mom.ctypes.data_as(C.POINTER(capi.rt_moment)), C.byref(info)))
+        return film, mom, self._adaptive_info(info)
+
+    def adaptive_begin(self, min_samples, step_samples, max_samples, rel_error, abs_floor=1e-3):
+        d = self._adaptive_desc(min_samples, step_samples, max_samples, rel_error, abs_floor)
+        self._chk("rt_adaptive_begin", self.lib.rt_adaptive_begin(self.h, C.byref(d)))
+
+    def adaptive_step(self):
+        """One iteration; returns the session's rt_adaptive_info as a dict."""
+        info = capi.rt_adaptive_info()
+        self._chk("rt_adaptive_step", self.lib.rt_adaptive_step(self.h, C.byref(info)))
+        return self._adaptive_info(info)
+
+    def adaptive_read(self):
+        """The session's state: dict(film, moments, block_error [rows, columns], active = the active pixel ids in
+        work-list order)."""
+        n = self.res[0] * self.res[1]
+        bx, by = self.n_blocks()
+        film, mom = self.new_film(), np.zeros((n, 2), np.float32)
+        err, act, na = np.zeros((by, bx), np.float32), np.zeros(n, np.int32), C.c_int()
+        self._chk("rt_adaptive_read", self.lib.rt_adaptive_read(
+            self.h, film.ctypes.data_as(C.POINTER(capi.rt_pixel)), mom.ctypes.data_as(C.POINTER(capi.rt_moment)),
+            err.ctypes.data_as(C.POINTER(C.c_float)), act.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(na)))
+        return dict(film=film, moments=mom, block_error=err, active=act[: na.value].copy())
+
+    def adaptive_end(self):
+        self._chk("rt_adaptive_end", self.lib.rt_adaptive_end(self.h))
+
+    def adaptive_select(self, film, moments, rel_error, abs_floor=1e-3):
+        """rt_debug_adaptive_select: the block error estimate and the compaction once, on host arrays, from the full
+        list of owned pixels; returns (block_error [rows, columns], active pixel ids)."""
+        n = self.res[0] * self.res[1]
+        film = np.ascontiguousarray(film, np.float32)
+        moments = np.ascontiguousarray(moments, np.float32)
+        assert film.shape == (n, 4) and moments.shape == (n, 2)
+        d = self._adaptive_desc(rel_error=rel_error, abs_floor=abs_floor)
+        bx, by = self.n_blocks()
+        err, act, na = np.zeros((by, bx), np.float32), np.zeros(n, np.int32), C.c_int()
+        self._chk("rt_debug_adaptive_select", self.lib.rt_debug_adaptive_select(
+            self.h, C.byref(d), film.ctypes.data_as(C.POINTER(capi.rt_pixel)),
+            moments.ctypes.data_as(C.POINTER(capi.rt_moment)), err.ctypes.data_as(C.POINTER(C.c_float)),
+            act.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(na)))
+        return err, act[: na.value].copy()
+
     def resolve(self, film, srgb=False):
         """rt_film_resolve (the reference's linear 255·x) or rt_film_resolve_srgb (pbrt's sRGB encoding)."""
         out = np.zeros((self.res[0] * self.res[1], 3), np.uint8)

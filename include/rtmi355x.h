@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 9
+#define RT_ABI_VERSION 10
 
 typedef enum {
     RT_OK = 0,
@@ -55,6 +55,9 @@ enum { RT_OCTREE_BUILD_DEVICE = 0, RT_OCTREE_BUILD_HOST = 1 };
 
 /* Film pixel, layout-identical to `pixel {glm::vec3 rgbsum; float weightsum;}` (Film.h:6-9). */
 typedef struct { float r, g, b, w; } rt_pixel;
+/* Per-pixel moments of the adaptive film: with v = (r + g) + b of one sample's clamped sensor RGB,
+ * sum = sum + v and sumsq = sumsq + v * v for every sample, in the film's index order (float32, nothing fused). */
+typedef struct { float sum, sumsq; } rt_moment;
 
 enum { RT_MAT_DIFFUSE = 0, RT_MAT_MIRROR = 1, RT_MAT_DIELECTRIC = 2 };
 /* Build-defined material (the reference has none: Shading.h:1-21 is a comment stub).
@@ -267,6 +270,47 @@ int rt_render_pass(rt_ctx* ctx, int index_begin, int index_end, rt_pixel* film_i
 /* Same, into a device-resident film (res_x*res_y rt_pixel in HBM) on the given hipStream_t
  * (NULL = the context's stream).  Returns after enqueueing; the caller synchronises. */
 int rt_render_pass_device(rt_ctx* ctx, int index_begin, int index_end, void* d_film, void* hip_stream);
+
+/* ---- adaptive sampling ---------------------------------------------------------- */
+/* A session renders sample indices only where an error estimate is still high.  The unit is the image-aligned 8x8
+ * pixel block: block error E = (sum of the pixels' standard errors of the mean) / (sum of their means + abs_floor),
+ * converged when E <= rel_error; a converged block's pixels leave the active list for good.  Every active pixel
+ * holds exactly the indices [0, film.w).  One-device contexts only. */
+typedef struct {
+    int min_samples;                 /* indices of the first step (>= 2)                                  */
+    int step_samples;                /* indices of every later step (>= 1)                                */
+    int max_samples;                 /* no pixel takes more (>= min_samples, <= the sampler's spp)        */
+    float rel_error;                 /* threshold on E (>= 0, finite)                                     */
+    float abs_floor;                 /* added to the block's mean sum (>= 0, finite)                      */
+    int reserved[3];
+} rt_adaptive_desc;
+typedef struct {
+    int iterations;                  /* steps that rendered                                               */
+    int index_done;                  /* every active pixel holds indices [0, index_done)                  */
+    int active_pixels;               /* pixels still in the active list                                   */
+    int active_blocks;               /* 8x8 blocks not converged at the last estimate                     */
+    int64_t samples;                 /* camera samples rendered by the session                            */
+} rt_adaptive_info;
+/* Zeroed device film and moments, every owned pixel active.  RT_E_STATE: a session is already open, or the
+ * context has more than one device.  rt_film_set and rt_set_shard return RT_E_STATE while a session is open. */
+int rt_adaptive_begin(rt_ctx* ctx, const rt_adaptive_desc* desc);
+/* The next min_samples (first step) or step_samples indices, clipped to max_samples, on the active pixels; then the
+ * block errors and the compaction of the active list.  Nothing active or index_done == max_samples: renders
+ * nothing.  info may be NULL.  Blocks until done. */
+int rt_adaptive_step(rt_ctx* ctx, rt_adaptive_info* info);
+/* Copy out the session's state: film and mom (res_x*res_y each), block_error (ceil(res_x/8)*ceil(res_y/8), row-major
+ * blocks; all 0 before the first step), the active pixel ids (up to the owned pixel count) and their number.  Any
+ * pointer may be NULL. */
+int rt_adaptive_read(rt_ctx* ctx, rt_pixel* film, rt_moment* mom, float* block_error, int32_t* active, int* n_active);
+int rt_adaptive_end(rt_ctx* ctx);
+/* begin; step until nothing is active or index_done == max_samples; read; end.  Outputs may be NULL. */
+int rt_render_adaptive(rt_ctx* ctx, const rt_adaptive_desc* desc, rt_pixel* film_out, rt_moment* mom_out,
+                       rt_adaptive_info* info);
+/* The error estimate and the compaction alone, once, on caller-supplied host film and moments (res_x*res_y each) for
+ * the current film and shard, starting from the full list of owned pixels (only rel_error and abs_floor of desc are
+ * read).  Outputs as in rt_adaptive_read; any may be NULL. */
+int rt_debug_adaptive_select(rt_ctx* ctx, const rt_adaptive_desc* desc, const rt_pixel* film, const rt_moment* mom,
+                             float* block_error, int32_t* active, int* n_active);
 
 /* a20 resolve (RayTracerTestApp.h:424-452): rgbsum/weightsum -> XYZFromSensorRGB -> sRGB -> clamp -> u8. */
 int rt_film_resolve(rt_ctx* ctx, const rt_pixel* film, uint8_t* rgb_out);
