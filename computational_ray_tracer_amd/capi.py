@@ -59,6 +59,16 @@ class rt_adaptive_info(C.Structure):
                 ("active_blocks", C.c_int), ("samples", C.c_int64)]
 
 
+class rt_feature(C.Structure):
+    _fields_ = [("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float), ("depth", C.c_float)]
+
+
+class rt_denoise_desc(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("feature_samples", C.c_int), ("normal_power_log2", C.c_int),
+                ("sigma_l", C.c_float), ("sigma_z", C.c_float), ("lum_floor", C.c_float), ("depth_floor", C.c_float),
+                ("reserved", C.c_int * 1)]
+
+
 class rt_material(C.Structure):
     _fields_ = [("type", C.c_int), ("sigmoid", F3), ("emission_scale", C.c_float), ("eta", C.c_float)]
 
@@ -146,6 +156,7 @@ EXPORTS = [
     "rt_sensor_name", "rt_film_matrices",
     "rt_adaptive_begin", "rt_adaptive_step", "rt_adaptive_read", "rt_adaptive_end", "rt_render_adaptive",
     "rt_debug_adaptive_select",
+    "rt_render_features", "rt_denoise", "rt_adaptive_denoise",
 ]
 
 _lib = None
@@ -223,6 +234,10 @@ def load_library(path=None):
                                C.c_int),
         "rt_debug_adaptive_select": ([C.c_void_p, P(rt_adaptive_desc), P(rt_pixel), P(rt_moment), P(C.c_float),
                                       P(C.c_int32), P(C.c_int)], C.c_int),
+        "rt_render_features": ([C.c_void_p, C.c_int, C.c_int, P(rt_feature)], C.c_int),
+        "rt_denoise": ([C.c_void_p, P(rt_denoise_desc), C.c_int, C.c_int, P(rt_pixel), P(rt_moment), P(rt_feature),
+                        P(rt_pixel), P(C.c_float)], C.c_int),
+        "rt_adaptive_denoise": ([C.c_void_p, P(rt_denoise_desc), P(rt_pixel)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

@@ -538,6 +538,9 @@ struct Knobs {
     // those (TraceIO hq_d; Cornell +4.2 %, r07_ab4).  RTMI_HIT_COMPACT=0: every queue position is shaded (A/B)
     int hit_compact = 1;
     size_t batch_samples = 0;  // samples in flight per batch (0: 16 Mi single leaf, 32 Mi multi-level; RTMI_BATCH_SAMPLES)
+    // denoiser iterations of step 1 and 2 stage their tile and halo in LDS (same bits; RTMI_DENOISE_LDS=0: every tap a
+    // plain load, A/B in DESIGN.md §3c)
+    int denoise_lds = 1;
 };
 
 static Knobs read_knobs() {
@@ -576,6 +579,7 @@ static Knobs read_knobs() {
     k.sort_nee_bits = std::max(1, std::min(9, k.sort_nee_bits));
     if (const char* e = std::getenv("RTMI_HIT_COMPACT")) k.hit_compact = std::atoi(e) != 0;
     if (const char* e = std::getenv("RTMI_BATCH_SAMPLES")) k.batch_samples = (size_t)std::max(0L, std::atol(e));
+    if (const char* e = std::getenv("RTMI_DENOISE_LDS")) k.denoise_lds = std::atoi(e) != 0;
     return k;
 }
 
@@ -654,7 +658,16 @@ struct rt_ctx {
         int cur = 0;                 // active[cur] is the current list (info.active_pixels entries)
         DevBuf<float> block_error;
         DevBuf<int> converged, wave_count, wave_offset, totals;
+        DevBuf<float4> feat;         // rt_adaptive_denoise: the feature film of indices [0, feat_k), 0: not rendered
+        int feat_k = 0;
     } ad;
+    // denoiser workspace (rt_denoise, rt_adaptive_denoise): staging of the host arrays, the guides and
+    // the (c, var) ping-pong; grows on demand
+    struct Denoise {
+        DevBuf<float4> film, feat, g, cv[2], out;
+        DevBuf<float2> mom, gz;
+        DevBuf<float> var;
+    } dn;
     // what render_device_body renders: the full work list, or (inside rt_adaptive_step) the session's active list
     // with its moment film
     const int* pass_work = nullptr;
@@ -2540,6 +2553,188 @@ static int impl_rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, c
     return RT_OK;
 }
 
+// ---- denoiser: the feature pass reuses the reference-mode workspace and the generate / trace kernels;
+// the filter runs on device arrays (an adaptive session's own, or staged copies of the caller's host arrays).
+namespace {
+// Features of indices [ib, ie) of the full work list added to the device feature film: per batch the camera rays, the
+// closest hits as the current integrator's first trace finds them (reference: the culled tile set when the scene
+// culls; path: every triangle), then k_feature_film.  Batches as render_device_body's reference loop.
+int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st) {
+    int rc;
+    if (ib < 0 || ie < ib) return fail(c, RT_E_ARG, "invalid index range");
+    if ((rc = ensure_sobol(c))) return rc;
+    DevSampler smp = dev_sampler(c);
+    if (c->smp.kind == RT_SAMPLER_STRATIFIED && !c->smp.jitter && ie > smp.spp)
+        return fail(c, RT_E_ARG, "StratifiedSampler without jitter supports indices < SamplesPerPixel (samplers.h:83-87)");
+    if ((rc = build_work(c))) return rc;
+    const int n_work = c->n_work;
+    if (ie == ib || n_work == 0) return RT_OK;
+    const bool path = c->integ.kind == RT_INTEGRATOR_PATH || c->integ.kind == RT_INTEGRATOR_PATH_MIS;
+    c->dsc.mis = c->integ.kind == RT_INTEGRATOR_PATH_MIS;
+    c->dsc.full = c->scene_full || c->dsc.mis;
+    const size_t target = c->knobs.batch_samples ? c->knobs.batch_samples : (size_t)(c->dsc.qcap == 1 ? 16 : 32) << 20;
+    int B = (int)std::max<size_t>(1, target / (size_t)n_work);
+    B = std::min(B, ie - ib);
+    const size_t nmax = (size_t)B * n_work;
+    const int nsh = c->dsc.qcap == 1 ? 1 : kShards;
+    const size_t ncap = (size_t)nsh * (size_t)shard_stride((int)nmax, nsh);
+    const DevCamera cam = dev_camera(c->cam);
+    const DevFilm fd = dev_film(c);
+    Work& w = c->ws[0];
+    if ((rc = ensure_workspace(c, w, ncap, false))) return rc;
+    for (int b0 = ib; b0 < ie; b0 += B) {
+        const int nIdx = std::min(B, ie - b0);
+        const int nS = nIdx * n_work;
+        const SampleIds ids = sample_ids(c->d_work.get(), n_work, b0);
+        RefIO r = ref_io(c, w.b, nS, nsh);
+        if (path) r.tio.set = 0;  // the path integrator traces every triangle
+        hipEvent_t e0 = ev_start(c, st);
+        HIPCHK(c, launch_generate(st, c->grid, nS, ids, cam, smp, fd, r.go));
+        ev_mark(c, st, ST_GEN, e0);
+        e0 = ev_start(c, st);
+        HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()));
+        ev_mark(c, st, ST_TRACE, e0);
+        const FeatureIO fio{c->d_work.get(), n_work, nIdx, w.b.rayD(), 1, w.b.hitB.get(), w.b.hitPrim.get(), feat};
+        HIPCHK(c, launch_feature_film(st, c->dsc, fio));
+    }
+    return RT_OK;
+}
+
+int denoise_check_desc(rt_ctx* c, const rt_denoise_desc* d) {
+    if (d->iterations < 1 || d->iterations > 6) return fail(c, RT_E_ARG, "denoise: iterations must be 1..6");
+    if (d->feature_samples < 1) return fail(c, RT_E_ARG, "denoise: feature_samples must be at least 1");
+    if (d->normal_power_log2 < 0 || d->normal_power_log2 > 8)
+        return fail(c, RT_E_ARG, "denoise: normal_power_log2 must be 0..8");
+    if (!std::isfinite(d->sigma_l) || !(d->sigma_l > 0) || !std::isfinite(d->sigma_z) || !(d->sigma_z > 0))
+        return fail(c, RT_E_ARG, "denoise: sigma_l and sigma_z must be finite and > 0");
+    if (!std::isfinite(d->lum_floor) || d->lum_floor < 0 || !std::isfinite(d->depth_floor) || d->depth_floor < 0)
+        return fail(c, RT_E_ARG, "denoise: lum_floor and depth_floor must be finite and >= 0");
+    return RT_OK;
+}
+
+// prepare and the iterations over device arrays of res_x * res_y; out = (c n, n), var (may be null) = the last variance
+int denoise_device(rt_ctx* c, const rt_denoise_desc& d, int res_x, int res_y, const float4* film, const float2* mom,
+                   const float4* feat, float4* out, float* var, hipStream_t st) {
+    rt_ctx::Denoise& w = c->dn;
+    const size_t n = (size_t)res_x * res_y;
+    HIPCHK(c, w.g.reserve(n)); HIPCHK(c, w.gz.reserve(n));
+    HIPCHK(c, w.cv[0].reserve(n)); HIPCHK(c, w.cv[1].reserve(n));
+    DenoiseIO io{};
+    io.res_x = res_x; io.res_y = res_y;
+    io.film = film; io.mom = mom; io.feat = feat;
+    io.kf = (float)d.feature_samples;
+    io.g = w.g.get(); io.gz = w.gz.get();
+    io.normal_power_log2 = d.normal_power_log2;
+    io.sigma_l = d.sigma_l; io.sigma_z = d.sigma_z; io.lum_floor = d.lum_floor; io.depth_floor = d.depth_floor;
+    io.cv_out = w.cv[0].get();
+    HIPCHK(c, launch_denoise_prepare(st, io));
+    for (int i = 0; i < d.iterations; ++i) {
+        io.cv_in = w.cv[i & 1].get();
+        io.cv_out = w.cv[(i & 1) ^ 1].get();
+        io.step = 1 << i;
+        if (i == d.iterations - 1) {  // the finish is fused into the last iteration
+            io.out = out;
+            io.var_out = var;
+        }
+        HIPCHK(c, launch_denoise_iter(st, io, c->knobs.denoise_lds != 0));
+    }
+    return RT_OK;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+}  // namespace
+
+static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat) {
+    if (!c || !feat) return RT_E_ARG;
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if (!c->peers.empty()) return fail(c, RT_E_STATE, "the feature pass supports one-device contexts only");
+    hipSetDevice(c->device);
+    const size_t n = (size_t)c->film.res_x * c->film.res_y;
+    HIPCHK(c, c->dn.feat.reserve(n));
+    hipStream_t st = c->stream;
+    if ((rc = order_after_previous(c, st))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->dn.feat.get(), feat, n * sizeof(float4), hipMemcpyHostToDevice, st));
+    rc = features_device(c, ib, ie, c->dn.feat.get(), st);
+    const int rc2 = mark_done(c, st);
+    if (rc || rc2) return rc ? rc : rc2;
+    HIPCHK(c, hipMemcpyAsync(feat, c->dn.feat.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+static int impl_rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int res_y, const rt_pixel* film,
+                           const rt_moment* mom, const rt_feature* feat, rt_pixel* out, float* variance_out) {
+    if (!c) return RT_E_ARG;
+    if (!d || !film || !mom || !feat || !out)
+        return fail(c, RT_E_ARG, "denoise: descriptor, film, moments, features and out are required");
+    if (res_x <= 0 || res_y <= 0) return fail(c, RT_E_ARG, "denoise: the resolution must be positive");
+    if ((int64_t)res_x * res_y > ((int64_t)1 << 28)) return fail(c, RT_E_LIMIT, "denoise: more than 2^28 pixels");
+    int rc = denoise_check_desc(c, d);
+    if (rc) return rc;
+    const size_t n = (size_t)res_x * res_y;
+    const void* const in[3] = {film, mom, feat};
+    const size_t in_bytes[3] = {n * sizeof(rt_pixel), n * sizeof(rt_moment), n * sizeof(rt_feature)};
+    for (int i = 0; i < 3; ++i)
+        if (ranges_overlap(out, n * sizeof(rt_pixel), in[i], in_bytes[i]) ||
+            (variance_out && ranges_overlap(variance_out, n * sizeof(float), in[i], in_bytes[i])))
+            return fail(c, RT_E_ARG, "denoise: an output overlaps an input");
+    if (variance_out && ranges_overlap(variance_out, n * sizeof(float), out, n * sizeof(rt_pixel)))
+        return fail(c, RT_E_ARG, "denoise: variance_out overlaps out");
+    hipSetDevice(c->device);
+    rt_ctx::Denoise& w = c->dn;
+    HIPCHK(c, w.film.reserve(n)); HIPCHK(c, w.mom.reserve(n)); HIPCHK(c, w.feat.reserve(n));
+    HIPCHK(c, w.out.reserve(n)); HIPCHK(c, w.var.reserve(n));
+    hipStream_t st = c->stream;
+    if ((rc = order_after_previous(c, st))) return rc;
+    HIPCHK(c, hipMemcpyAsync(w.film.get(), film, n * sizeof(float4), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(w.mom.get(), mom, n * sizeof(float2), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(w.feat.get(), feat, n * sizeof(float4), hipMemcpyHostToDevice, st));
+    rc = denoise_device(c, *d, res_x, res_y, w.film.get(), w.mom.get(), w.feat.get(), w.out.get(), w.var.get(), st);
+    const int rc2 = mark_done(c, st);
+    if (rc || rc2) return rc ? rc : rc2;
+    HIPCHK(c, hipMemcpyAsync(out, w.out.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
+    if (variance_out) HIPCHK(c, hipMemcpyAsync(variance_out, w.var.get(), n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+static int impl_rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixel* film_out) {
+    if (!c) return RT_E_ARG;
+    if (!d || !film_out) return fail(c, RT_E_ARG, "adaptive denoise: descriptor and film_out are required");
+    rt_ctx::Adaptive& a = c->ad;
+    if (!a.live) return fail(c, RT_E_STATE, "no adaptive session is open (rt_adaptive_begin first)");
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if ((rc = denoise_check_desc(c, d))) return rc;
+    if (d->feature_samples > dev_sampler(c).spp)
+        return fail(c, RT_E_ARG, "adaptive denoise: feature_samples exceeds the sampler's samples per pixel");
+    hipSetDevice(c->device);
+    const size_t n = (size_t)c->film.res_x * c->film.res_y;
+    HIPCHK(c, a.feat.reserve(n));
+    HIPCHK(c, c->dn.out.reserve(n));
+    hipStream_t st = c->stream;
+    if ((rc = order_after_previous(c, st))) return rc;
+    if (a.feat_k != d->feature_samples) {  // once per session (again only if the caller changes k)
+        a.feat_k = 0;
+        rc = hipMemsetAsync(a.feat.get(), 0, n * sizeof(float4), st) == hipSuccess ? RT_OK
+                                                                                   : fail(c, RT_E_HIP, "feature film memset");
+        if (!rc) rc = features_device(c, 0, d->feature_samples, a.feat.get(), st);
+        if (!rc) a.feat_k = d->feature_samples;
+    }
+    if (!rc)
+        rc = denoise_device(c, *d, c->film.res_x, c->film.res_y, a.film.get(), a.mom.get(), a.feat.get(),
+                            c->dn.out.get(), nullptr, st);
+    const int rc2 = mark_done(c, st);
+    if (rc || rc2) return rc ? rc : rc2;
+    HIPCHK(c, hipMemcpyAsync(film_out, c->dn.out.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
 namespace {
 int film_resolve(rt_ctx* c, const rt_pixel* film, uint8_t* out, int srgb) {
     if (!c || !film || !out) return RT_E_ARG;
@@ -2980,7 +3175,18 @@ int rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, const rt_pixe
     return guarded([&] { return impl_rt_debug_adaptive_select(c, d, film, mom, block_error, active, n_active); },
                    [&](const std::string& m) { set_error(c, m); });
 }
-int rt_film_resolve(rt_ctx* c, const rt_pixel* film, uint8_t* out) {
+int rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat) {
+    return guarded([&] { return impl_rt_render_features(c, ib, ie, feat); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int res_y, const rt_pixel* film, const rt_moment* mom,
+               const rt_feature* feat, rt_pixel* out, float* variance_out) {
+    return guarded([&] { return impl_rt_denoise(c, d, res_x, res_y, film, mom, feat, out, variance_out); },
+                   [&](const std::string& m) { set_error(c, m); });
+}
+int rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixel* film_out) {
+    return guarded([&] { return impl_rt_adaptive_denoise(c, d, film_out); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_film_resolve(rt_ctx* c,const rt_pixel* film, uint8_t* out) {
     return guarded([&] { return impl_rt_film_resolve(c, film, out); }, [&](const std::string& m) { set_error(c, m); });
 }
 int rt_film_resolve_srgb(rt_ctx* c, const rt_pixel* film, uint8_t* out) {

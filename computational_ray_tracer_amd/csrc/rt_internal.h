@@ -535,4 +535,31 @@ inline __host__ __device__ int adaptive_waves(int n) { return (n + 63) / 64; }
 hipError_t launch_adaptive_compact(hipStream_t st, const AdaptiveIO& io, const int* in, int n, int* out,
                                    int* wave_count, int* wave_offset);
 
+// Denoiser (rt_denoise.hip).
+// The feature film: pixel work_pixels[j] adds the shading-side normal and t of its first hits, samples
+// s = i * n_pixels + j for i in [0, n_index), to feat (nx, ny, nz, depth sums); misses add nothing.
+struct FeatureIO {
+    const int* work_pixels; int n_pixels; int n_index;
+    const float4* rayD; int rsh;  // sample s's direction at rayD[s << rsh]
+    const float4* hitB; const int* hitPrim;
+    float4* feat;                 // res_x * res_y
+};
+hipError_t launch_feature_film(hipStream_t st, const DevScene& sc, const FeatureIO& io);
+// The filter over a res_x x res_y image.  prepare: film, mom, feat -> cv_out = (c.rgb, var), g = (normal, depth) / kf,
+// gz = the depth gradient.  iter: one a-trous iteration of step `step` from cv_in to cv_out, or, when out is set (the
+// last iteration), to out = (c n, n) and var_out (may be null).
+struct DenoiseIO {
+    int res_x, res_y;
+    const float4* film; const float2* mom; const float4* feat;
+    float kf;                     // (float)feature_samples
+    float4* g; float2* gz;
+    const float4* cv_in; float4* cv_out;
+    int step, normal_power_log2;
+    float sigma_l, sigma_z, lum_floor, depth_floor;
+    float4* out; float* var_out;
+};
+hipError_t launch_denoise_prepare(hipStream_t st, const DenoiseIO& io);
+// lds: steps 1 and 2 stage the block's tile and halo in LDS (same arithmetic, same bits)
+hipError_t launch_denoise_iter(hipStream_t st, const DenoiseIO& io, bool lds);
+
 }  // namespace rtmi

@@ -7,6 +7,10 @@ import numpy as np
 
 from . import capi
 
+# rt_denoise_desc defaults (chosen on the oracle's Cornell render, tests/test_denoise_reference.py)
+DENOISE_DEFAULTS = dict(iterations=5, feature_samples=4, normal_power_log2=7, sigma_l=1.5, sigma_z=1.0,
+                        lum_floor=0.01, depth_floor=0.002)
+
 
 class Renderer:
     """One rt_ctx.  `device` is one HIP ordinal or a list of them (rt_options.devices: every pass renders on
@@ -136,6 +140,69 @@ class Renderer:
             moments.ctypes.data_as(C.POINTER(capi.rt_moment)), err.ctypes.data_as(C.POINTER(C.c_float)),
             act.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(na)))
         return err, act[: na.value].copy()
+
+    # ---- denoiser (rt_render_features, rt_denoise, rt_adaptive_denoise) ------------------------
+    @staticmethod
+    def _denoise_desc(**kw):
+        unknown = set(kw) - set(DENOISE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown denoise parameters: {sorted(unknown)}")
+        p = dict(DENOISE_DEFAULTS, **kw)
+        d = capi.rt_denoise_desc()
+        d.iterations, d.feature_samples = int(p["iterations"]), int(p["feature_samples"])
+        d.normal_power_log2 = int(p["normal_power_log2"])
+        d.sigma_l, d.sigma_z = float(p["sigma_l"]), float(p["sigma_z"])
+        d.lum_floor, d.depth_floor = float(p["lum_floor"]), float(p["depth_floor"])
+        return d
+
+    def render_features(self, index_begin, index_end, feat=None):
+        """Accumulate the first-hit features (normal and depth sums, float32 [W*H, 4]) of sample indices
+        [index_begin, index_end) into `feat`."""
+        if feat is None:
+            feat = self.new_film()
+        assert feat.dtype == np.float32 and feat.flags.c_contiguous and feat.shape == (self.res[0] * self.res[1], 4)
+        self._chk("rt_render_features", self.lib.rt_render_features(self.h, index_begin, index_end,
+                                                                    feat.ctypes.data_as(C.POINTER(capi.rt_feature))))
+        return feat
+
+    def denoise(self, film, mom, feat, res=None, variance=False, **desc):
+        """rt_denoise on host arrays of `res` (default: the film's): film [N, 4], moments [N, 2], features [N, 4] of
+        desc feature_samples indices -> the filtered film [N, 4] (and the filtered variance [N] with variance=True).
+        Descriptor fields default to DENOISE_DEFAULTS."""
+        W, H = res or self.res
+        film = np.ascontiguousarray(film, np.float32)
+        mom = np.ascontiguousarray(mom, np.float32)
+        feat = np.ascontiguousarray(feat, np.float32)
+        assert film.shape == (W * H, 4) and mom.shape == (W * H, 2) and feat.shape == (W * H, 4)
+        d = self._denoise_desc(**desc)
+        out = np.zeros((W * H, 4), np.float32)
+        var = np.zeros(W * H, np.float32) if variance else None
+        self._chk("rt_denoise", self.lib.rt_denoise(
+            self.h, C.byref(d), W, H, film.ctypes.data_as(C.POINTER(capi.rt_pixel)),
+            mom.ctypes.data_as(C.POINTER(capi.rt_moment)), feat.ctypes.data_as(C.POINTER(capi.rt_feature)),
+            out.ctypes.data_as(C.POINTER(capi.rt_pixel)),
+            None if var is None else var.ctypes.data_as(C.POINTER(C.c_float))))
+        return (out, var) if variance else out
+
+    def adaptive_denoise(self, **desc):
+        """rt_adaptive_denoise: the open session's film filtered on the device (features rendered once per session);
+        the session is left as it was."""
+        d = self._denoise_desc(**desc)
+        out = self.new_film()
+        self._chk("rt_adaptive_denoise", self.lib.rt_adaptive_denoise(self.h, C.byref(d),
+                                                                      out.ctypes.data_as(C.POINTER(capi.rt_pixel))))
+        return out
+
+    def render_denoised(self, min_samples, step_samples, max_samples, rel_error, abs_floor=1e-3, **desc):
+        """Adaptive session -> denoise -> end: (filtered film, info dict of the session)."""
+        self.adaptive_begin(min_samples, step_samples, max_samples, rel_error, abs_floor)
+        try:
+            info = self.adaptive_step()
+            while info["active_pixels"] > 0 and info["index_done"] < max_samples:
+                info = self.adaptive_step()
+            return self.adaptive_denoise(**desc), info
+        finally:
+            self.adaptive_end()
 
     def resolve(self, film, srgb=False):
         """rt_film_resolve (the reference's linear 255·x) or rt_film_resolve_srgb (pbrt's sRGB encoding)."""

@@ -312,6 +312,36 @@ int rt_render_adaptive(rt_ctx* ctx, const rt_adaptive_desc* desc, rt_pixel* film
 int rt_debug_adaptive_select(rt_ctx* ctx, const rt_adaptive_desc* desc, const rt_pixel* film, const rt_moment* mom,
                              float* block_error, int32_t* active, int* n_active);
 
+/* ---- denoiser ------------------------------------------------------------------- */
+/* First-hit guide image: per pixel the sums, over the samples of a feature pass, of the shading-side geometric
+ * normal and the hit distance t of the camera rays that hit (misses add nothing, so |n| / samples is coverage). */
+typedef struct { float nx, ny, nz, depth; } rt_feature;   /* 16 B, sums over the pass's samples */
+/* Accumulate (+=) the features of sample indices [index_begin, index_end) of every owned pixel into feat_inout
+ * (res_x*res_y, host memory): the camera rays of rt_render_pass traced as the current integrator's first trace
+ * (same tile set, same analytic shapes), index-ordered per pixel.  Allowed while an adaptive session is open (always
+ * the full work list).  Counts rays in rt_stats, not samples.  RT_E_STATE on multi-device contexts.  Blocks. */
+int rt_render_features(rt_ctx* ctx, int index_begin, int index_end, rt_feature* feat_inout);
+/* Variance-guided edge-avoiding a-trous filter (spatial SVGF): float32 in a fixed operation order, exp(-x) replaced
+ * by max(1 - x/8, 0)^8 (three squarings).  Pixels need film.w >= 2 to carry a variance. */
+typedef struct {
+    int iterations;         /* 1..6; step of iteration i is 2^i                      */
+    int feature_samples;    /* k >= 1: indices accumulated in feat                    */
+    int normal_power_log2;  /* 0..8: w_n = max(0, n_p.n_q)^(2^j), by j squarings      */
+    float sigma_l, sigma_z; /* > 0, finite                                            */
+    float lum_floor;        /* >= 0, finite; added to sigma_l*sqrt(var)               */
+    float depth_floor;      /* >= 0, finite; times z_p, added to the depth denominator */
+    int reserved[1];
+} rt_denoise_desc;          /* 32 B */
+/* Filter host arrays of any res_x x res_y (film, mom, feat, out: res_x*res_y each; variance_out: res_x*res_y floats
+ * or NULL): out = (filtered mean * film.w, film.w), so both resolves apply.  The context supplies the device, the
+ * stream and a workspace.  RT_E_ARG: bad descriptor, NULL array, or out overlapping an input.  Blocks. */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_desc* desc, int res_x, int res_y, const rt_pixel* film, const rt_moment* mom,
+               const rt_feature* feat, rt_pixel* out, float* variance_out);
+/* Inside an adaptive session: the features of indices [0, feature_samples) (rendered once per session into a device
+ * buffer), then the filter over the session's device film and moments into film_out (res_x*res_y, host).  The
+ * session's film and moments are not modified. */
+int rt_adaptive_denoise(rt_ctx* ctx, const rt_denoise_desc* desc, rt_pixel* film_out);
+
 /* a20 resolve (RayTracerTestApp.h:424-452): rgbsum/weightsum -> XYZFromSensorRGB -> sRGB -> clamp -> u8. */
 int rt_film_resolve(rt_ctx* ctx, const rt_pixel* film, uint8_t* rgb_out);
 
