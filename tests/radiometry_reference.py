@@ -3,8 +3,11 @@
 The GPU kernels are compared bit for bit with oracle/rtcore.hpp, which was written by the same hand.  This module
 states, independently of both, what the film of a few scenes must converge to: point, distant, quad and disk lights
 over a Lambert plane, a point light in an integrating sphere, and mirror / glass spheres in a furnace.  Every
-emitter is k * D65 and every albedo a grey (wavelength-constant) sigmoid, so the expected sensor RGB of a pixel is a
-geometric scalar times the sensor white W.
+emitter is k * D65.  In the grey cases every albedo is a wavelength-constant sigmoid, so the expected sensor RGB of a
+pixel is a geometric scalar times the sensor white W.  The colour cases ("spectral part" below) put a sigmoid that
+varies with the wavelength on the floor, the sphere or the mirror and change the film's sensor, so that W becomes
+`response(bars, imaging_ratio, f)`: the tables are read at the rounded wavelength, the sigmoid is evaluated at the
+continuous one, and throughput is a power of the sigmoid per wavelength.
 
 Nothing here calls the oracle or the product library; `capi` and `scene` are used only to build the descriptors the
 renderers are given, and the camera rays are generated in float64 from those descriptors' matrices.
@@ -38,9 +41,13 @@ BOUND_SLACK = 1.001        # on vmax: float32 rounding of the estimator, the 1e-
 # ------------------------------------------------------------------------------------------- spectra
 
 
+TABLES = dict(np.load(GOLDEN / "spectra_tables.npz"))
+LAMBDA = np.arange(360, 831, dtype=np.float64)
+
+
 def _tables():
-    z = np.load(GOLDEN / "spectra_tables.npz")
-    lam = np.arange(360, 831, dtype=np.float64)
+    z = TABLES
+    lam = LAMBDA
     assert np.array_equal(z["CIE_lambda"].astype(np.float64), lam)
     bars = np.stack([z["CIE_X"], z["CIE_Y"], z["CIE_Z"]]).astype(np.float64)
     d = z["CIE_Illum_D6500"].astype(np.float64)
@@ -74,18 +81,114 @@ def sensor_white(imaging_ratio):
     return w
 
 
-def sample_maxima(imaging_ratio, n=65536):
+def sample_maxima(imaging_ratio, n=65536, bars=None, envelope=None):
     """(M8, M1): per channel, the largest sensor value one sample of radiance 1 * D65 can take with all eight hero
-    wavelengths (u + i/8) alive, and with the first alone after TerminateSecondary (pdf[0] / 8, the others 0)."""
+    wavelengths (u + i/8) alive, and with the first alone after TerminateSecondary (pdf[0] / 8, the others 0).
+    `bars`: the sensor's curves (default: the CIE bars).  `envelope`: an upper envelope, a function of the
+    continuous wavelength, of the factor f in the radiance D65(round lambda) * f(lambda) (default: 1)."""
+    bars = BARS if bars is None else bars
     u = (np.arange(n) + 0.5) / n
     ui = (u[None, :] + np.arange(8)[:, None] / 8.0) % 1.0
     lam = np.clip(sample_visible(ui), 360.0, 830.0)
     k = np.clip(np.rint(lam).astype(int) - 360, 0, 470)
-    f = BARS[:, k] * D65[k] / visible_pdf(lam) * float(imaging_ratio)      # (3, 8, n)
+    f = bars[:, k] * D65[k] / visible_pdf(lam) * float(imaging_ratio)      # (3, 8, n)
+    if envelope is not None:
+        e = np.broadcast_to(envelope(lam), lam.shape)
+        assert np.all(e >= 0)
+        f = f * e[None]
     m8 = f.mean(axis=1).max(axis=1)
     m1 = f[:, 0, :].max(axis=1)
     assert np.all(np.isfinite(m8)) and np.all(np.isfinite(m1)) and np.all(m1 >= m8)
     return m8 * BOUND_SLACK, m1 * BOUND_SLACK
+
+
+# ------------------------------------------------------------------------------------------- spectral part
+
+S_RED = (0.0, 0.02, -0.02 * 580)                    # a red edge at 580 nm, about 100 nm wide
+S_GREEN = (-4e-4, 0.432, -4e-4 * 540 ** 2 + 2)      # a band around 540 nm: x = 2 - 4e-4 (lambda - 540)^2
+SUB = 1024                 # midpoint sub-grid per 1 nm bin (even: a table's knots at integer nm fall on its edges)
+ILLUMINANTS = {capi.RT_ILLUM_D65: "CIE_Illum_D6500", capi.RT_ILLUM_A: "CIE_Illum_A",
+               capi.RT_ILLUM_D50: "CIE_Illum_D5000", capi.RT_ILLUM_F1: "CIE_Illum_F1",
+               capi.RT_ILLUM_F1 + 10: "CIE_Illum_F11"}
+
+
+def sigmoid(c, lam):
+    """The albedo 0.5 + x / (2 sqrt(1 + x^2)), x = (c0 lambda + c1) lambda + c2, in float64 at the continuous
+    wavelength, of coefficients rounded to float32 first (what the material descriptor carries)."""
+    c0, c1, c2 = (float(np.float32(v)) for v in c)
+    lam = np.asarray(lam, np.float64)
+    x = (c0 * lam + c1) * lam + c2
+    return 0.5 + x / (2.0 * np.sqrt(1.0 + x * x))
+
+
+def sigmoid_power_sum(c, powers):
+    """f(lambda) = sum over `powers` of sigmoid(c, lambda)^p: what a path of several bounces multiplies up."""
+    powers = list(powers)
+    return lambda lam: sum(sigmoid(c, lam) ** p for p in powers)
+
+
+def illuminant(which):
+    """A named illuminant (RT_ILLUM_*) as a function of the continuous wavelength, built as D65 is in `_tables`:
+    linear interpolation of the table, constant beyond its ends, scaled so that sum over the integer nanometres of
+    Y * illuminant = CIE_Y_integral."""
+    a = TABLES[ILLUMINANTS[which]].astype(np.float64)
+    scale = CIE_Y_INTEGRAL / np.sum(BARS[1] * np.interp(LAMBDA, a[0::2], a[1::2]))
+    return lambda lam: scale * np.interp(np.asarray(lam, np.float64), a[0::2], a[1::2])
+
+
+def sensor_bars(sensor, zero_outside=False):
+    """The three response curves of a sensor (an index into, or a name of, scene.SENSORS) as a (3, 471) float64
+    array on the integer nanometres 360 .. 830.  "xyz" is the CIE bars.  A camera's curves are tabulated on
+    380 .. 720 nm; they are interpolated linearly and, not normalised, EXTENDED AS CONSTANTS beyond both ends of the
+    table (the reference's FromInterleaved adds the points (359, first) and (831, last)).  That extension is the
+    behaviour under test: `zero_outside` builds the other reading, 0 outside the table, which the power tests
+    require to fail."""
+    name = sensor if isinstance(sensor, str) else scene.SENSORS[sensor]
+    assert name in scene.SENSORS
+    if name == "xyz":
+        return BARS.copy()
+    out = []
+    for ch in "rgb":
+        a = TABLES[f"{name}_{ch}"].astype(np.float64)
+        lo, hi = (0.0, 0.0) if zero_outside else (None, None)
+        out.append(np.interp(LAMBDA, a[0::2], a[1::2], left=lo, right=hi))
+    return np.stack(out)
+
+
+def bin_integrals(f, sub=SUB):
+    """Integral of f over [k - 0.5, k + 0.5] intersected with [360, 830] for the 471 integer nanometres k: the set
+    of wavelengths whose table lookups round to k.  Midpoint rule on `sub` points per bin (the end bins have half
+    the width)."""
+    lo = np.maximum(LAMBDA - 0.5, 360.0)
+    hi = np.minimum(LAMBDA + 0.5, 830.0)
+    t = (np.arange(sub) + 0.5) / sub
+    pts = lo[:, None] + (hi - lo)[:, None] * t[None, :]
+    return np.mean(np.broadcast_to(f(pts), pts.shape), axis=1) * (hi - lo)
+
+
+def response(bars, imaging_ratio, f, table=None, sub=SUB):
+    """Expectation of one sample's sensor RGB for the spectral radiance table(round lambda) * f(lambda), `table`
+    D65 by default: the wavelength pdf cancels, each of the eight hero wavelengths is distributed with that pdf, so
+    E = imaging_ratio * sum_k bars[:, k] table[k] * integral of f over the wavelengths that round to k."""
+    table = D65 if table is None else table
+    r = float(imaging_ratio) * (bars * table) @ bin_integrals(f, sub)
+    fine = float(imaging_ratio) * (bars * table) @ bin_integrals(f, 2 * sub)
+    assert np.all(np.abs(fine - r) <= 1e-9 * np.abs(fine)), (r, fine)
+    return r
+
+
+def bin_envelope(f, half=0.5, m=17):
+    """An upper envelope of f for `sample_maxima`: at lambda, the largest f on a grid over lambda +- half nm, which
+    covers the gaps of the scan over u (they are below 0.1 nm wherever a bar is not negligible)."""
+    d = np.linspace(-half, half, m)
+    return lambda lam: np.max(np.stack([f(np.clip(np.asarray(lam, np.float64) + x, 360.0, 830.0)) for x in d]), axis=0)
+
+
+def sigmoid_power_sum_envelope(c, powers):
+    """The same sum over the envelope of the sigmoid: an upper envelope of the sum, which grows with the sigmoid."""
+    powers = list(powers)
+    env = bin_envelope(lambda lam: sigmoid(c, lam))
+    return lambda lam: sum(env(lam) ** p for p in powers)
 
 
 # ------------------------------------------------------------------------------------------- camera
@@ -234,11 +337,36 @@ def _floor_tris(n):
     return np.array(t)
 
 
-def _config(name, model, camera, spp, kind, max_depth, res=RES):
+def _config(name, model, camera, spp, kind, max_depth, res=RES, film=None, albedo_rgb=None):
     side = int(round(math.sqrt(spp)))
     assert side * side == spp
-    return scene.Config(name, model, camera, scene.StratifiedSampler(side, side, True, 0), scene.Film(res=res),
-                        scene.Integrator(kind, max_depth=max_depth), 0, spp)
+    film = scene.Film(res=res) if film is None else film
+    integ = scene.Integrator(kind, max_depth=max_depth)
+    if albedo_rgb is not None:
+        integ.albedo_rgb = tuple(albedo_rgb)
+    return scene.Config(name, model, camera, scene.StratifiedSampler(side, side, True, 0), film, integ, 0, spp)
+
+
+def _film(sensor="xyz", illum=capi.RT_ILLUM_D65, exposure=1.0):
+    """The film of a case: the sensor by name.  The sensor illuminant only enters the resolve matrices, never the
+    accumulated sensor RGB; the colour cases set it as a user of that sensor would.  `exposure` (a power of two)
+    scales the imaging ratio."""
+    film = scene.Film(res=RES, sensor=scene.SENSORS.index(sensor), sensor_illum=illum)
+    film.imaging_ratio = float(np.float32(film.imaging_ratio) * np.float32(exposure))
+    return film
+
+
+def _per_rho(film, albedo):
+    """(w, m8): expected and largest sensor RGB of the radiance D65 * rho(lambda), both divided by RHO, so that the
+    grey formulas `RHO * ... * w` hold for a coloured albedo as they stand.  Grey on the XYZ sensor: the sensor white
+    and `sample_maxima`, as before."""
+    if albedo is None and film.sensor == capi.RT_SENSOR_XYZ:
+        return sensor_white(film.imaging_ratio), sample_maxima(film.imaging_ratio)[0]
+    bars = sensor_bars(film.sensor)
+    c = scene.grey_sigmoid(RHO) if albedo is None else albedo
+    f = lambda lam: sigmoid(c, lam)
+    return (response(bars, film.imaging_ratio, f) / RHO,
+            sample_maxima(film.imaging_ratio, bars=bars, envelope=bin_envelope(f))[0] / RHO)
 
 
 def _fov(slope):
@@ -286,13 +414,14 @@ def _outside_frustum(cfg, pts):
                 np.all(s[:, 1] < lo[1]) or np.all(s[:, 1] > hi[1]))
 
 
-def _floor_model(tessellated, extra_tris=(), extra_mats=(), materials=(), lights=(), shapes=()):
+def _floor_model(tessellated, extra_tris=(), extra_mats=(), materials=(), lights=(), shapes=(), albedo=None):
     tris = _floor_tris(48 if tessellated else 1)
     mats = [0] * len(tris)
     if len(extra_tris):
         tris = np.concatenate([tris, np.asarray(extra_tris, np.float64)])
         mats += list(extra_mats)
-    return _model(tris, mats, [(scene.grey_sigmoid(RHO), 0.0)] + list(materials), lights, shapes)
+    floor = scene.grey_sigmoid(RHO) if albedo is None else albedo
+    return _model(tris, mats, [(floor, 0.0)] + list(materials), lights, shapes)
 
 
 # ------------------------------------------------------------------------------------------- K1, K1s, K2
@@ -314,13 +443,13 @@ def _point_bound(cfg, p):
     return p[1] / (p[1] ** 2 + gap ** 2) ** 1.5
 
 
-def k1_point(tessellated=False, spp=256):
+def k1_point(tessellated=False, spp=256, albedo=None, sensor="xyz", illum=capi.RT_ILLUM_D65):
     """K1: a point light of intensity I * D65 over the Lambert floor, L = rho / pi * I cos(theta) / d^2."""
     inten = 2.0e6
     lights = [dict(type=capi.RT_LIGHT_POINT, p=tuple(POINT_P), scale=inten)]
-    cfg = _config("k1_point", _floor_model(tessellated, lights=lights), _down_camera(), spp, capi.RT_INTEGRATOR_PATH, 1)
-    w = sensor_white(cfg.film.imaging_ratio)
-    m8, _ = sample_maxima(cfg.film.imaging_ratio)
+    cfg = _config("k1_point", _floor_model(tessellated, lights=lights, albedo=albedo), _down_camera(), spp,
+                  capi.RT_INTEGRATOR_PATH, 1, film=_film(sensor, illum))
+    w, m8 = _per_rho(cfg.film, albedo)
     x = _floor_points(cfg, _midpoints())
     k = RHO / math.pi * inten * _point_irradiance(x, POINT_P, np.array([0.0, 1.0, 0.0])).mean(axis=1)
     mu = k[:, None] * w[None, :]
@@ -363,15 +492,20 @@ def k1s_point_shadow(spp=256):
     return _finish("k1s_point_shadow", cfg, mu, vmax, umbra | lit, spp)
 
 
-def k2_distant(tessellated=False, spp=256):
-    """K2: a distant light of irradiance E * D65 from an oblique direction, L = rho / pi * E cos(theta), uniform."""
-    e = 2.5
-    d = np.array([0.3, 0.8, 0.2])
+K2_E = 2.5
+K2_DIR = np.array([0.3, 0.8, 0.2])
+K2_GEOMETRY = K2_E * K2_DIR[1] / np.linalg.norm(K2_DIR) / math.pi          # E cos(theta) / pi
+
+
+def k2_distant(tessellated=False, spp=256, albedo=None, sensor="xyz", illum=capi.RT_ILLUM_D65):
+    """K2: a distant light of irradiance E * D65 from an oblique direction, L = rho / pi * E cos(theta), uniform.
+    With a coloured floor: E cos(theta) / pi * response(bars, imaging_ratio, rho)."""
+    e = K2_E
+    d = K2_DIR
     lights = [dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)]
-    cfg = _config("k2_distant", _floor_model(tessellated, lights=lights), _down_camera(), spp,
-                  capi.RT_INTEGRATOR_PATH, 1)
-    w = sensor_white(cfg.film.imaging_ratio)
-    m8, _ = sample_maxima(cfg.film.imaging_ratio)
+    cfg = _config("k2_distant", _floor_model(tessellated, lights=lights, albedo=albedo), _down_camera(), spp,
+                  capi.RT_INTEGRATOR_PATH, 1, film=_film(sensor, illum))
+    w, m8 = _per_rho(cfg.film, albedo)
     k = RHO / math.pi * e * d[1] / np.linalg.norm(d)
     n = cfg.film.res[0] * cfg.film.res[1]
     mu = np.tile(k * w, (n, 1))
@@ -412,15 +546,17 @@ def quad_irradiance_bruteforce(x, p, e1, e2, nl, n, m=1024):
 QUAD_SEEN_SHIFT = -120.0       # along x: moves a corner of the light into the camera's view
 
 
-def k3_quad(mis=False, max_depth=1, tessellated=False, seen=False, spp=256):
+def k3_quad(mis=False, max_depth=1, tessellated=False, seen=False, spp=256, albedo=None, sensor="xyz",
+            illum=capi.RT_ILLUM_D65):
     """K3: a quad light Le * D65 above the floor and parallel to it, as two emissive triangles and an RT_LIGHT_QUAD.
     The plane is open: a bounce never returns to it, so every depth has the depth-1 expectation rho * F(x) * Le with
     pi F = Lambert's polygon formula.  One NEE sample is rho / pi Le G A (times w_l <= 1 with MIS); with MIS a bounce
     that hits the light adds rho Le w_b, w_b = 1 / (1 + (p_l / p_b)^2) and p_l / p_b = pi / (G A).
     `seen`: the light is moved under the camera, which then looks at its back: emitters are one-sided, so a pixel
     wholly on the light is exactly 0, and the floor pixels keep their closed form (nothing hides the light's front
-    from the floor)."""
-    le = 16.0
+    from the floor).  A coloured floor changes only the colour factor: no light reaches the floor twice, so the
+    albedo enters to the first power at every depth."""
+    le = 16.0 if albedo is None else 10.0        # rho peaks near 0.95, not 0.5: a dimmer light keeps vmax below 1
     qx = (QUAD_X[0] + QUAD_SEEN_SHIFT, QUAD_X[1] + QUAD_SEEN_SHIFT) if seen else QUAD_X
     p = np.array([qx[1], QUAD_H, QUAD_Z[0]])
     e1, e2 = np.array([0.0, 0.0, QUAD_Z[1] - QUAD_Z[0]]), np.array([qx[0] - qx[1], 0.0, 0.0])
@@ -430,13 +566,12 @@ def k3_quad(mis=False, max_depth=1, tessellated=False, seen=False, spp=256):
     ltris = np.array([(a, b, c), (a, c, d)])                      # wound so that the geometric normal is nl
     assert np.allclose(np.cross(b - a, c - a) / np.linalg.norm(np.cross(b - a, c - a)), nl)
     lights = [dict(type=capi.RT_LIGHT_QUAD, p=tuple(p), e1=tuple(e1), e2=tuple(e2), n=tuple(nl), material=1)]
-    model = _floor_model(tessellated, ltris, [1, 1], [((0.0, 0.0, 0.0), le)], lights)
+    model = _floor_model(tessellated, ltris, [1, 1], [((0.0, 0.0, 0.0), le)], lights, albedo=albedo)
     kind = capi.RT_INTEGRATOR_PATH_MIS if mis else capi.RT_INTEGRATOR_PATH
-    cfg = _config("k3_quad", model, _down_camera(), spp, kind, max_depth)
+    cfg = _config("k3_quad", model, _down_camera(), spp, kind, max_depth, film=_film(sensor, illum))
     verts = np.array([a, b, c, d])
     assert seen or _outside_frustum(cfg, verts), "the camera sees the light"
-    w = sensor_white(cfg.film.imaging_ratio)
-    m8, _ = sample_maxima(cfg.film.imaging_ratio)
+    w, m8 = _per_rho(cfg.film, albedo)
     x = _floor_points(cfg, _midpoints())
     up = np.array([0.0, 1.0, 0.0])
     form = polygon_irradiance(x, verts, up).mean(axis=1) / math.pi
@@ -543,28 +678,47 @@ SPHERE_LIGHT = np.array([20.0, -15.0, 10.0])
 SPHERE_EYE = np.array([0.0, 0.0, -60.0])
 
 
-def k5_sphere(max_depth=1, spp=256):
-    """K5: camera and an off-centre point light inside a diffuse Sphere shape of radius r.  The form factor between
-    any two elements of a sphere's inside is dA / (4 pi r^2), so every bounce spreads its flux evenly:
-    L(x) = rho / pi [I cos / d^2 + I / r^2 sum_{k=1..D-1} rho^k] with NEE at depths 0 .. D - 1 (max_depth = D)."""
-    inten = 1.2e4
-    lights = [dict(type=capi.RT_LIGHT_POINT, p=tuple(SPHERE_LIGHT), scale=inten)]
-    model = _model([FAR_TRIANGLE], [0], [(scene.grey_sigmoid(RHO), 0.0)], lights,
-                   [scene.Sphere(np.eye(4), 0, radius=SPHERE_R)])
-    cam = scene.PerspectiveCamera(near=1.0, far=5000.0, fov=_fov(0.8), position=tuple(SPHERE_EYE), look=(0, 0, 1),
-                                  worldup=(0, 1, 0), res=RES, aspect_fix=True)
-    cfg = _config("k5_sphere", model, cam, spp, capi.RT_INTEGRATOR_PATH, max_depth)
-    w = sensor_white(cfg.film.imaging_ratio)
-    m8, _ = sample_maxima(cfg.film.imaging_ratio)
+K5_COLOUR_INTENSITY = 4.0e3
+
+
+def k5_direct(cfg):
+    """cos / d^2 of the point light at what every pixel sees of the sphere's inside, footprint average."""
     o, d = camera_rays(cfg, _midpoints())
     bq = d @ o
     t = -bq + np.sqrt(bq * bq - (o @ o - SPHERE_R ** 2))           # the far root: the eye is inside
     x = o + t[..., None] * d
-    direct = _point_irradiance(x, SPHERE_LIGHT, -x / SPHERE_R).mean(axis=1)
+    return _point_irradiance(x, SPHERE_LIGHT, -x / SPHERE_R).mean(axis=1)
+
+
+def k5_sphere(max_depth=1, spp=256, albedo=None):
+    """K5: camera and an off-centre point light inside a diffuse Sphere shape of radius r.  The form factor between
+    any two elements of a sphere's inside is dA / (4 pi r^2), so every bounce spreads its flux evenly:
+    L(x) = rho / pi [I cos / d^2 + I / r^2 sum_{k=1..D-1} rho^k] with NEE at depths 0 .. D - 1 (max_depth = D).
+    With a coloured sphere rho is a function of the wavelength and the sum holds per wavelength, so
+    mu = I / pi [direct * response(rho) + 1 / r^2 sum_{k=1..D-1} response(rho^(k+1))]: the one closed form here in
+    which throughput is a power of the albedo per wavelength, not of a colour."""
+    inten = 1.2e4 if albedo is None else K5_COLOUR_INTENSITY
+    lights = [dict(type=capi.RT_LIGHT_POINT, p=tuple(SPHERE_LIGHT), scale=inten)]
+    model = _model([FAR_TRIANGLE], [0], [(scene.grey_sigmoid(RHO) if albedo is None else albedo, 0.0)], lights,
+                   [scene.Sphere(np.eye(4), 0, radius=SPHERE_R)])
+    cam = scene.PerspectiveCamera(near=1.0, far=5000.0, fov=_fov(0.8), position=tuple(SPHERE_EYE), look=(0, 0, 1),
+                                  worldup=(0, 1, 0), res=RES, aspect_fix=True)
+    cfg = _config("k5_sphere", model, cam, spp, capi.RT_INTEGRATOR_PATH, max_depth)
+    direct = k5_direct(cfg)
+    dmin = SPHERE_R - np.linalg.norm(SPHERE_LIGHT)
+    if albedo is not None:
+        ir = cfg.film.imaging_ratio
+        first = response(BARS, ir, sigmoid_power_sum(albedo, [1]))
+        later = response(BARS, ir, sigmoid_power_sum(albedo, range(2, max_depth + 1))) if max_depth > 1 else 0.0
+        mu = inten / math.pi * (direct[:, None] * first[None, :] + later / SPHERE_R ** 2)
+        # each depth's NEE sample is at most rho^(k+1) / pi I / d_min^2 at its wavelength
+        m8, _ = sample_maxima(ir, envelope=sigmoid_power_sum_envelope(albedo, range(1, max_depth + 1)))
+        return _finish("k5_sphere", cfg, mu, inten / math.pi / dmin ** 2 * m8, np.ones(len(mu), bool), spp)
+    w = sensor_white(cfg.film.imaging_ratio)
+    m8, _ = sample_maxima(cfg.film.imaging_ratio)
     bounces = sum(RHO ** k for k in range(1, max_depth)) / SPHERE_R ** 2
     mu = (RHO / math.pi * inten * (direct + bounces))[:, None] * w[None, :]
     # each depth's NEE sample is at most rho^(k+1) / pi I / d_min^2, d_min = r - |light|
-    dmin = SPHERE_R - np.linalg.norm(SPHERE_LIGHT)
     bound = inten / math.pi / dmin ** 2 * sum(RHO ** (k + 1) for k in range(max_depth))
     return _finish("k5_sphere", cfg, mu, bound * m8, np.ones(len(mu), bool), spp)
 
@@ -601,25 +755,30 @@ def _box_tris(h):
     return t
 
 
-def k6_furnace(kind="mirror", spp=256):
+def k6_furnace(kind="mirror", spp=256, reflectance=None, sensor="xyz", illum=capi.RT_ILLUM_D65):
     """K6: a closed box of 12 inward-facing triangles emitting L0 * D65, no light records; camera and one Sphere
     inside; PATH, max_depth 12.  A pixel that misses the sphere sees L0 W; the mirror (R = 0.9) 0.9 L0 W; glass
     (constant eta 1.5, or eta 0 = BK7 with TerminateSecondary) L0 W, because the 1 / eta'^2 factors cancel.  A path
     that enters the glass and is reflected inside 11 times is cut off: probability (1 - F) F^11, F the entry
-    reflectance, the same at every interface of a sphere; pixels where it can exceed 1e-4 are excluded."""
-    assert kind in ("mirror", "glass", "bk7")
-    film = scene.Film(res=RES)
-    m8, m1 = sample_maxima(film.imaging_ratio)
+    reflectance, the same at every interface of a sphere; pixels where it can exceed 1e-4 are excluded.
+    `reflectance`: a sigmoid R(lambda) on the mirror instead of 0.9; pixels on the sphere then expect
+    L0 * response(R), the others L0 * response(1)."""
+    assert kind in ("mirror", "glass", "bk7") and (reflectance is None or kind == "mirror")
+    film = _film(sensor, illum)
+    bars = sensor_bars(film.sensor)
+    m8, m1 = sample_maxima(film.imaging_ratio, bars=bars)
     l0 = 0.9 / (m1 if kind == "bk7" else m8).max()
     mats = [((0.0, 0.0, 0.0), l0),
-            {"mirror": (scene.grey_sigmoid(0.9), 0.0, capi.RT_MAT_MIRROR, 0.0),
+            {"mirror": (scene.grey_sigmoid(0.9) if reflectance is None else reflectance, 0.0, capi.RT_MAT_MIRROR, 0.0),
              "glass": ((0.0, 0.0, 0.0), 0.0, capi.RT_MAT_DIELECTRIC, 1.5),
              "bk7": ((0.0, 0.0, 0.0), 0.0, capi.RT_MAT_DIELECTRIC, 0.0)}[kind]]
     model = _model(_box_tris(BOX_HALF), [0] * 12, mats, (), [scene.Sphere(np.eye(4), 1, radius=FURNACE_R)])
     cam = scene.PerspectiveCamera(near=1.0, far=5000.0, fov=_fov(0.42), position=tuple(FURNACE_EYE), look=(0, 0, 1),
                                   worldup=(0, 1, 0), res=RES, aspect_fix=True)
-    cfg = _config(f"k6_furnace_{kind}", model, cam, spp, capi.RT_INTEGRATOR_PATH, FURNACE_DEPTH)
-    w = sensor_white(cfg.film.imaging_ratio)
+    cfg = _config(f"k6_furnace_{kind}", model, cam, spp, capi.RT_INTEGRATOR_PATH, FURNACE_DEPTH, film=film)
+    one = lambda lam: np.ones_like(np.asarray(lam, np.float64))
+    w = sensor_white(film.imaging_ratio) if film.sensor == capi.RT_SENSOR_XYZ else \
+        response(bars, film.imaging_ratio, one)
     o, d = camera_rays(cfg, _lattice())
     bq = d @ o
     disc = bq * bq - (o @ o - FURNACE_R ** 2)
@@ -637,8 +796,54 @@ def k6_furnace(kind="mirror", spp=256):
         lost = ((1 - f) * f ** (FURNACE_DEPTH - 1)).max(axis=(1, 2))
         include &= ~(on & (lost > LOST_MAX))
     mu = (l0 * k)[:, None] * w[None, :]
+    if reflectance is not None:          # the sigmoid is at most 1: the white bound m8 holds on the sphere too
+        wr = response(bars, film.imaging_ratio, lambda lam: sigmoid(reflectance, lam))
+        mu = l0 * np.where(on[:, None], wr[None, :], w[None, :])
     vmax = l0 * (m1 if kind == "bk7" else m8) * (1 + 1e-5)
     return _finish(f"k6_furnace_{kind}", cfg, mu, vmax, include, spp)
+
+
+# ------------------------------------------------------------------------------------------- reference integrator
+
+AMBIENT = 0.3              # RT_INTEGRATOR_REFERENCE (include/rtmi355x.h): ambient 0.3 F1 + clamp(n.(0,0,-1)) D65 albedo
+K_ILLUM = 2.0 * 0.5        # the light is RGBIlluminantSpectrum(sRGB, (1, 1, 1)): scale 2 max(rgb) times the sigmoid
+                           # of rgb / scale = grey 0.5, times the colour space's illuminant D65
+REF_FLIP_EPS = 1e-9
+REF_EXPOSURE = 0.5
+
+
+def kref_floor(albedo=0.5, spp=256, sensor="xyz", illum=capi.RT_ILLUM_D65):
+    """The reference workload's own Li on the plain floor: L(lambda) = 0.3 F1(lambda) + c D65(round lambda) a, a the
+    grey albedo_rgb.  F1 is a piecewise-linear table evaluated at the continuous wavelength, normalised as D65 is.
+    c is the clamped dot of (0, 0, -1) with the mesh's OBJECT-space normal after it was flipped against the
+    WORLD-space ray: with a normal (0, 0, +-1) it is 1 where the ray's z is positive and 0 where it is negative,
+    whichever way the triangle is wound.  Pixels whose footprint holds both signs are excluded.
+    This integrator has no light scale to choose, and F1's mercury lines at 405 and 436 nm lift one sample's Z to
+    1.5 (albedo 0.5) and 1.75 (albedo 0.73) at the default imaging ratio, where it would clamp: the film's imaging
+    ratio is halved (REF_EXPOSURE), which scales every expected value and bound alike."""
+    model = _floor_model(False)
+    cfg = _config("kref_floor", model, _down_camera(), spp, capi.RT_INTEGRATOR_REFERENCE, 1,
+                  film=_film(sensor, illum, REF_EXPOSURE), albedo_rgb=(albedo,) * 3)
+    nz = np.asarray(model.normals, np.float64)
+    assert np.all(nz[:, :2] == 0) and np.all(np.abs(nz[:, 2]) == 1), "the floor's object-space normals are +-z"
+    _floor_points(cfg, _lattice())                                  # every ray meets the floor
+    _, d = camera_rays(cfg, _lattice())
+    pos, neg = np.all(d[..., 2] > REF_FLIP_EPS, axis=1), np.all(d[..., 2] < -REF_FLIP_EPS, axis=1)
+    c = pos.astype(np.float64)          # ray z > 0: the normal ends as (0, 0, -1) and the cosine is 1; else 0
+    assert pos.mean() > 0.4 and neg.mean() > 0.4
+    ir, bars = cfg.film.imaging_ratio, sensor_bars(cfg.film.sensor)
+    a = float(sigmoid(scene.grey_sigmoid(albedo), 0.0))             # the constant sigmoid the descriptor's grey gives
+    assert abs(a - albedo) < 1e-6
+    f1 = illuminant(capi.RT_ILLUM_F1)
+    ambient = AMBIENT * response(bars, ir, f1, table=np.ones(471))
+    lit = K_ILLUM * a * response(bars, ir, lambda lam: np.ones_like(np.asarray(lam, np.float64)))
+    mu = ambient[None, :] + c[:, None] * lit[None, :]
+    # one sample is at most max over the scan of [0.3 F1(lambda) + a D65(round lambda)] bar / pdf: as an envelope of
+    # the factor on D65(round lambda), 0.3 F1 / D65 + a, F1 taken over lambda +- 0.5 nm
+    f1_env = bin_envelope(f1)
+    env = lambda lam: AMBIENT * f1_env(lam) / D65[np.clip(np.rint(lam).astype(int) - 360, 0, 470)] + K_ILLUM * a
+    m8, _ = sample_maxima(ir, bars=bars, envelope=env)
+    return _finish("kref_floor", cfg, mu, m8, pos | neg, spp)
 
 
 # ------------------------------------------------------------------------------------------- registry
@@ -669,12 +874,39 @@ CASES = [
     ("k6_furnace_glass", k6_furnace, dict(kind="glass")),
     ("k6_furnace_bk7", k6_furnace, dict(kind="bk7")),
 ]
+
+# The colour cases.  Variants of one scene are adjacent, and within a scene the sensor changes on its own at least
+# once (k2: xyz -> canon -> sony; k3: the last two; k6; kref), so that a renderer reused across them must replace its
+# sensor curves: a stale curve fails the closed form.
+_A, _D50 = capi.RT_ILLUM_A, capi.RT_ILLUM_D50
+_SENSOR_VARIANTS = [("xyz", "xyz", capi.RT_ILLUM_D65), ("canon", "canon_eos_100d", _A),
+                    ("sony", "sony_ilce_6400", _D50)]
+COLOUR_CASES = (
+    [(f"k2_{cn}_{sn}", k2_distant, dict(albedo=c, sensor=sensor, illum=illum))
+     for cn, c in (("red", S_RED), ("green", S_GREEN)) for sn, sensor, illum in _SENSOR_VARIANTS] +
+    [("k1_red_tess", k1_point, dict(tessellated=True, albedo=S_RED)),
+     ("k3_quad_green_path_d1", k3_quad, dict(mis=False, max_depth=1, albedo=S_GREEN)),
+     ("k3_quad_green_mis_d5", k3_quad, dict(mis=True, max_depth=5, albedo=S_GREEN)),
+     ("k3_quad_green_mis_d5_canon", k3_quad, dict(mis=True, max_depth=5, albedo=S_GREEN, sensor="canon_eos_100d",
+                                                   illum=_A)),
+     ("k5_red_d2", k5_sphere, dict(max_depth=2, albedo=S_RED)),
+     ("k5_red_d5", k5_sphere, dict(max_depth=5, albedo=S_RED)),
+     ("k5_green_d2", k5_sphere, dict(max_depth=2, albedo=S_GREEN)),
+     ("k5_green_d5", k5_sphere, dict(max_depth=5, albedo=S_GREEN)),
+     ("k6_furnace_mirror_red_xyz", k6_furnace, dict(kind="mirror", reflectance=S_RED)),
+     ("k6_furnace_mirror_red_sony", k6_furnace, dict(kind="mirror", reflectance=S_RED, sensor="sony_ilce_6400",
+                                                     illum=_D50)),
+     ("kref_floor_a50", kref_floor, dict(albedo=0.5)),
+     ("kref_floor_a73", kref_floor, dict(albedo=0.73)),
+     ("kref_floor_a50_canon", kref_floor, dict(albedo=0.5, sensor="canon_eos_100d", illum=_A))])
+CASES += COLOUR_CASES
 CASE_IDS = [c[0] for c in CASES]
 
 
 def scene_key(case_id):
-    """Variants with the same key differ in the integrator descriptor only."""
-    for prefix in ("k3_quad_tess", "k3_quad_seen", "k3_quad", "k4_disk"):
+    """Variants with the same key differ in the integrator descriptor and the film's sensor only."""
+    for prefix in ("k3_quad_tess", "k3_quad_seen", "k3_quad_green", "k3_quad", "k4_disk", "k2_red", "k2_green",
+                   "k5_red", "k5_green", "k6_furnace_mirror_red", "kref_floor"):
         if case_id.startswith(prefix):
             return prefix
     return case_id

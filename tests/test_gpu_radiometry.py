@@ -3,7 +3,11 @@
 For every case and variant: (1) the GPU film is the oracle's bit for bit, the project's standard check; (2) the GPU
 film itself passes the closed-form comparison, so the physics stays pinned even if (1) were ever relaxed; (3) the
 kernels that ran are the intended ones (rt_stats, rt_octree_info).  The environment knobs are left alone: the parity
-tests cover them bit for bit."""
+tests cover them bit for bit.
+
+The colour cases (ref.COLOUR_CASES) run through the same test.  Within a scene they change the film's sensor while the
+renderer is kept (ref.scene_key), so a sensor curve left over from the previous variant would fail (2);
+tests/test_gpu_spectral.py checks that transition on its own."""
 import ctypes as C
 
 import numpy as np
@@ -85,3 +89,5 @@ def test_gpu_film_is_the_oracle_s_and_matches_the_closed_form(shared, oracle_lib
         assert st["shadow_rays"] > 0
     elif case_id.startswith(("k1", "k2", "k3", "k4", "k5")):
         assert st["nee_vertices"] > 0, "k_path_shade_full + k_path_nee"
+    elif case_id.startswith("kref"):
+        assert st["nee_vertices"] == 0 and st["shadow_rays"] == 0, "the reference Li traces camera rays only"
