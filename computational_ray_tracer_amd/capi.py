@@ -69,6 +69,19 @@ class rt_denoise_desc(C.Structure):
                 ("reserved", C.c_int * 1)]
 
 
+class rt_position(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("hits", C.c_float)]
+
+
+class rt_temporal_desc(C.Structure):
+    _fields_ = [("normal_min", C.c_float), ("plane_rel", C.c_float), ("max_history", C.c_float),
+                ("feature_samples", C.c_int), ("reserved", C.c_int * 4)]
+
+
+class rt_temporal_info(C.Structure):
+    _fields_ = [("frames", C.c_int), ("reprojected", C.c_int), ("disoccluded", C.c_int), ("background", C.c_int)]
+
+
 class rt_material(C.Structure):
     _fields_ = [("type", C.c_int), ("sigmoid", F3), ("emission_scale", C.c_float), ("eta", C.c_float)]
 
@@ -157,6 +170,8 @@ EXPORTS = [
     "rt_adaptive_begin", "rt_adaptive_step", "rt_adaptive_read", "rt_adaptive_end", "rt_render_adaptive",
     "rt_debug_adaptive_select",
     "rt_render_features", "rt_denoise", "rt_adaptive_denoise",
+    "rt_render_features_pos", "rt_temporal_accumulate", "rt_temporal_begin", "rt_temporal_frame", "rt_temporal_reset",
+    "rt_temporal_end",
 ]
 
 _lib = None
@@ -238,6 +253,16 @@ def load_library(path=None):
         "rt_denoise": ([C.c_void_p, P(rt_denoise_desc), C.c_int, C.c_int, P(rt_pixel), P(rt_moment), P(rt_feature),
                         P(rt_pixel), P(C.c_float)], C.c_int),
         "rt_adaptive_denoise": ([C.c_void_p, P(rt_denoise_desc), P(rt_pixel)], C.c_int),
+        "rt_render_features_pos": ([C.c_void_p, C.c_int, C.c_int, P(rt_feature), P(rt_position)], C.c_int),
+        "rt_temporal_accumulate": ([C.c_void_p, P(rt_temporal_desc), C.c_int, C.c_int, P(rt_pixel), P(rt_moment),
+                                    P(rt_feature), P(rt_position), P(rt_pixel), P(rt_moment), P(rt_feature),
+                                    P(rt_position), P(C.c_float), P(rt_pixel), P(rt_moment), P(rt_temporal_info)],
+                                   C.c_int),
+        "rt_temporal_begin": ([C.c_void_p, P(rt_temporal_desc)], C.c_int),
+        "rt_temporal_frame": ([C.c_void_p, P(rt_adaptive_desc), P(rt_denoise_desc), P(C.c_float), P(rt_pixel),
+                               P(rt_temporal_info)], C.c_int),
+        "rt_temporal_reset": ([C.c_void_p], C.c_int),
+        "rt_temporal_end": ([C.c_void_p], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

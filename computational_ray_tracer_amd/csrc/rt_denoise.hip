@@ -1,7 +1,8 @@
 // Denoiser: the first-hit feature film and the variance-guided a-trous filter.
 //
 //   k_feature_film     one thread per owned pixel: adds the shading-side geometric normal and t of the batch's first
-//                      hits, in increasing index order (the normal is k_path_shade_full's "surface" block)
+//                      hits, in increasing index order (the normal is k_path_shade_full's "surface" block); <true> also
+//                      adds the hit point o + t d and a hit count to the position film
 //   k_denoise_prepare  per pixel: c = rgb / n, the variance of the mean from the moment film, the guides
 //                      g = (normal, depth) / k and the screen-space depth gradient
 //   k_denoise_iter     one a-trous iteration with step s: the 3x3 blur of the variance, then the 25 taps in row-major
@@ -19,10 +20,13 @@ namespace {
 
 constexpr int kBlock = kBlockThreads;
 
+template <bool POS>  // POS: also the position film, the sums of (o + t d, 1) over the same hits
 __global__ void __launch_bounds__(kBlock) k_feature_film(DevScene sc, FeatureIO io) {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < io.n_pixels; j += gridDim.x * blockDim.x) {
         const int pixel = io.work_pixels[j];
         float4 f = io.feat[pixel];
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (POS) q = io.pos[pixel];
         for (int i = 0; i < io.n_index; ++i) {
             const int s = i * io.n_pixels + j;
             const int prim = io.hitPrim[s];
@@ -48,8 +52,16 @@ __global__ void __launch_bounds__(kBlock) k_feature_film(DevScene sc, FeatureIO 
             f.y += nrm.y;
             f.z += nrm.z;
             f.w += hb.w;
+            if constexpr (POS) {
+                const float4 o4 = io.rayO[(size_t)s << io.rsh];
+                q.x += o4.x + hb.w * d4.x;
+                q.y += o4.y + hb.w * d4.y;
+                q.z += o4.z + hb.w * d4.z;
+                q.w += 1.f;
+            }
         }
         io.feat[pixel] = f;
+        if constexpr (POS) io.pos[pixel] = q;
     }
 }
 
@@ -205,7 +217,9 @@ dim3 tile_grid(const DenoiseIO& io) { return dim3((io.res_x + kTX - 1) / kTX, (i
 
 hipError_t launch_feature_film(hipStream_t st, const DevScene& sc, const FeatureIO& io) {
     if (io.n_pixels <= 0 || io.n_index <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_feature_film, dim3((io.n_pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, io);
+    const dim3 grid((io.n_pixels + kBlock - 1) / kBlock), block(kBlock);
+    if (io.pos) hipLaunchKernelGGL(k_feature_film<true>, grid, block, 0, st, sc, io);
+    else hipLaunchKernelGGL(k_feature_film<false>, grid, block, 0, st, sc, io);
     return hipGetLastError();
 }
 

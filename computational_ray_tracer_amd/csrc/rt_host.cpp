@@ -668,6 +668,22 @@ struct rt_ctx {
         DevBuf<float2> mom, gz;
         DevBuf<float> var;
     } dn;
+    // temporal accumulation (rt_temporal_*): the session's device-resident history, 56 B per pixel in
+    // each of two sets (set `cur` is the last frame's: its unfiltered accumulation, features and positions, with M its
+    // camera's world-to-film matrix); the staging of rt_temporal_accumulate's host arrays; the class counters
+    struct Temporal {
+        bool live = false;
+        bool in_frame = false;       // rt_temporal_frame is running its own adaptive session
+        rt_temporal_desc desc{};
+        int frames = 0;              // frames behind set `cur` (0: no history)
+        int cur = 0;
+        float M[16] = {};
+        DevBuf<float4> film[2], feat[2], pos[2];
+        DevBuf<float2> mom[2];
+        DevBuf<float4> s_film, s_feat, s_pos, s_hfilm, s_hfeat, s_hpos, s_out;
+        DevBuf<float2> s_mom, s_hmom, s_outm;
+        DevBuf<unsigned long long> ctr;
+    } tp;
     // what render_device_body renders: the full work list, or (inside rt_adaptive_step) the session's active list
     // with its moment film
     const int* pass_work = nullptr;
@@ -2254,6 +2270,7 @@ static int film_set_one(rt_ctx* c, const rt_film_desc* d) {
         return fail(c, RT_E_ARG, "invalid film");
     if ((size_t)d->res_x * d->res_y > ((size_t)1 << 27)) return fail(c, RT_E_LIMIT, "film too large");
     if (c->ad.live) return fail(c, RT_E_STATE, "rt_film_set during an adaptive session (rt_adaptive_end first)");
+    if (c->tp.live) return fail(c, RT_E_STATE, "rt_film_set during a temporal session (rt_temporal_end first)");
     if (d->sensor < 0 || d->sensor >= RT_SENSOR_COUNT || d->sensor_illum < 0 || d->sensor_illum >= RT_ILLUM_COUNT)
         return fail(c, RT_E_ARG, "unknown sensor or sensor illuminant");
     hipSetDevice(c->device);
@@ -2318,6 +2335,7 @@ static int set_shard_one(rt_ctx* c, int tile_size, int n_shards, int shard_id) {
     if (!c || tile_size <= 0 || tile_size % 8 || n_shards <= 0 || shard_id < 0 || shard_id >= n_shards)
         return c ? fail(c, RT_E_ARG, "invalid shard (tile_size must be a positive multiple of 8)") : RT_E_ARG;
     if (c->ad.live) return fail(c, RT_E_STATE, "rt_set_shard during an adaptive session (rt_adaptive_end first)");
+    if (c->tp.live) return fail(c, RT_E_STATE, "rt_set_shard during a temporal session (rt_temporal_end first)");
     c->tile = tile_size;
     c->n_shards = n_shards;
     c->shard_id = shard_id;
@@ -2407,6 +2425,8 @@ static int impl_rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d) {
     if (!c->peers.empty()) return fail(c, RT_E_STATE, "adaptive sampling supports one-device contexts only");
     rt_ctx::Adaptive& a = c->ad;
     if (a.live) return fail(c, RT_E_STATE, "an adaptive session is already open (rt_adaptive_end first)");
+    if (c->tp.live && !c->tp.in_frame)
+        return fail(c, RT_E_STATE, "a temporal session is open: its frames own the adaptive session (rt_temporal_end first)");
     if ((rc = adaptive_check_desc(c, d, true))) return rc;
     hipSetDevice(c->device);
     if ((rc = build_work(c))) return rc;
@@ -2559,7 +2579,8 @@ namespace {
 // Features of indices [ib, ie) of the full work list added to the device feature film: per batch the camera rays, the
 // closest hits as the current integrator's first trace finds them (reference: the culled tile set when the scene
 // culls; path: every triangle), then k_feature_film.  Batches as render_device_body's reference loop.
-int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st) {
+// pos (may be null): the position film of the same hits.
+int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, float4* pos = nullptr) {
     int rc;
     if (ib < 0 || ie < ib) return fail(c, RT_E_ARG, "invalid index range");
     if ((rc = ensure_sobol(c))) return rc;
@@ -2594,7 +2615,8 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st) {
         e0 = ev_start(c, st);
         HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()));
         ev_mark(c, st, ST_TRACE, e0);
-        const FeatureIO fio{c->d_work.get(), n_work, nIdx, w.b.rayD(), 1, w.b.hitB.get(), w.b.hitPrim.get(), feat};
+        const FeatureIO fio{c->d_work.get(), n_work, nIdx, w.b.rayD(), 1, w.b.hitB.get(), w.b.hitPrim.get(), feat,
+                            w.b.rayO(), pos};
         HIPCHK(c, launch_feature_film(st, c->dsc, fio));
     }
     return RT_OK;
@@ -2647,21 +2669,29 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 }
 }  // namespace
 
-static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat) {
-    if (!c || !feat) return RT_E_ARG;
+// rt_render_features (with_pos false: pos is not looked at) and rt_render_features_pos
+static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos = nullptr,
+                                   bool with_pos = false) {
+    if (!c || !feat || (with_pos && !pos)) return RT_E_ARG;
     int rc = check_ready(c);
     if (rc) return rc;
     if (!c->peers.empty()) return fail(c, RT_E_STATE, "the feature pass supports one-device contexts only");
     hipSetDevice(c->device);
     const size_t n = (size_t)c->film.res_x * c->film.res_y;
+    if (with_pos && ranges_overlap(feat, n * sizeof(rt_feature), pos, n * sizeof(rt_position)))
+        return fail(c, RT_E_ARG, "the feature film and the position film overlap");
     HIPCHK(c, c->dn.feat.reserve(n));
+    if (with_pos) HIPCHK(c, c->tp.s_pos.reserve(n));
+    float4* const d_pos = with_pos ? c->tp.s_pos.get() : nullptr;
     hipStream_t st = c->stream;
     if ((rc = order_after_previous(c, st))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->dn.feat.get(), feat, n * sizeof(float4), hipMemcpyHostToDevice, st));
-    rc = features_device(c, ib, ie, c->dn.feat.get(), st);
+    if (with_pos) HIPCHK(c, hipMemcpyAsync(d_pos, pos, n * sizeof(float4), hipMemcpyHostToDevice, st));
+    rc = features_device(c, ib, ie, c->dn.feat.get(), st, d_pos);
     const int rc2 = mark_done(c, st);
     if (rc || rc2) return rc ? rc : rc2;
     HIPCHK(c, hipMemcpyAsync(feat, c->dn.feat.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
+    if (with_pos) HIPCHK(c, hipMemcpyAsync(pos, d_pos, n * sizeof(float4), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -2732,6 +2762,229 @@ static int impl_rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixe
     if (rc || rc2) return rc ? rc : rc2;
     HIPCHK(c, hipMemcpyAsync(film_out, c->dn.out.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+// ---- temporal accumulation: the stage runs on device arrays (a session's own, or staged copies of
+// the caller's host arrays); a frame is an adaptive session, a feature + position pass, the stage and the filter.
+namespace {
+int temporal_check_desc(rt_ctx* c, const rt_temporal_desc* d) {
+    if (!std::isfinite(d->normal_min) || d->normal_min < -1.f || d->normal_min > 1.f)
+        return fail(c, RT_E_ARG, "temporal: normal_min must be in [-1, 1]");
+    if (!std::isfinite(d->plane_rel) || d->plane_rel < 0) return fail(c, RT_E_ARG, "temporal: plane_rel must be finite and >= 0");
+    if (!(d->max_history >= 1.f)) return fail(c, RT_E_ARG, "temporal: max_history must be at least 1");
+    if (d->feature_samples < 1) return fail(c, RT_E_ARG, "temporal: feature_samples must be at least 1");
+    return RT_OK;
+}
+
+// The stage over device arrays of res_x * res_y (hfilm null: no history, M not read); counts[T_NCLASSES] read back
+// after the kernel (blocks until then).
+int temporal_device(rt_ctx* c, const rt_temporal_desc& d, int res_x, int res_y, const float4* film, const float2* mom,
+                    const float4* feat, const float4* pos, const float4* hfilm, const float2* hmom, const float4* hfeat,
+                    const float4* hpos, const float* M, float4* out_film, float2* out_mom, int* counts, hipStream_t st) {
+    rt_ctx::Temporal& t = c->tp;
+    HIPCHK(c, t.ctr.reserve(kTemporalCtrWords));
+    HIPCHK(c, hipMemsetAsync(t.ctr.get(), 0, kTemporalCtrWords * sizeof(unsigned long long), st));
+    TemporalIO io{};
+    io.res_x = res_x; io.res_y = res_y;
+    io.film = film; io.mom = mom; io.feat = feat; io.pos = pos;
+    io.hfilm = hfilm; io.hmom = hmom; io.hfeat = hfeat; io.hpos = hpos;
+    if (hfilm) std::memcpy(io.M, M, sizeof(io.M));
+    io.kf = (float)d.feature_samples;
+    io.normal_min = d.normal_min; io.plane_rel = d.plane_rel; io.max_history = d.max_history;
+    io.out_film = out_film; io.out_mom = out_mom;
+    io.ctr = t.ctr.get();
+    HIPCHK(c, launch_temporal_accumulate(st, io));
+    std::vector<unsigned long long> raw(kTemporalCtrWords);
+    HIPCHK(c, hipMemcpyAsync(raw.data(), t.ctr.get(), kTemporalCtrWords * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (int k = 0; k < T_NCLASSES; ++k) {
+        unsigned long long s = 0;
+        for (int u = 0; u < kCtrSubs; ++u) s += raw[ctr_word(k, u)];
+        counts[k] = (int)s;
+    }
+    return RT_OK;
+}
+
+void temporal_fill_info(rt_temporal_info* info, int frames, const int* counts) {
+    if (!info) return;
+    info->frames = frames;
+    info->reprojected = counts[T_REPROJECTED];
+    info->disoccluded = counts[T_DISOCCLUDED];
+    info->background = counts[T_BACKGROUND];
+}
+}  // namespace
+
+static int impl_rt_render_features_pos(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos) {
+    return impl_rt_render_features(c, ib, ie, feat, pos, true);
+}
+
+static int impl_rt_temporal_accumulate(rt_ctx* c, const rt_temporal_desc* d, int res_x, int res_y, const rt_pixel* film,
+                                       const rt_moment* mom, const rt_feature* feat, const rt_position* pos,
+                                       const rt_pixel* hfilm, const rt_moment* hmom, const rt_feature* hfeat,
+                                       const rt_position* hpos, const float* M, rt_pixel* out_film, rt_moment* out_mom,
+                                       rt_temporal_info* info) {
+    if (!c) return RT_E_ARG;
+    if (!d || !film || !mom || !feat || !pos || !out_film || !out_mom)
+        return fail(c, RT_E_ARG, "temporal: descriptor, film, moments, features, positions and both outputs are required");
+    const int n_hist = (hfilm != nullptr) + (hmom != nullptr) + (hfeat != nullptr) + (hpos != nullptr);
+    if (n_hist != 0 && n_hist != 4) return fail(c, RT_E_ARG, "temporal: the history is all four arrays or none");
+    const bool hist = n_hist == 4;
+    if (hist && !M) return fail(c, RT_E_ARG, "temporal: a history needs its world-to-film matrix");
+    if (res_x <= 0 || res_y <= 0) return fail(c, RT_E_ARG, "temporal: the resolution must be positive");
+    if ((int64_t)res_x * res_y > ((int64_t)1 << 28)) return fail(c, RT_E_LIMIT, "temporal: more than 2^28 pixels");
+    int rc = temporal_check_desc(c, d);
+    if (rc) return rc;
+    const size_t n = (size_t)res_x * res_y;
+    const void* const in[8] = {film, mom, feat, pos, hfilm, hmom, hfeat, hpos};
+    const size_t in_bytes[8] = {n * 16, n * 8, n * 16, n * 16, n * 16, n * 8, n * 16, n * 16};
+    for (int i = 0; i < (hist ? 8 : 4); ++i)
+        if (ranges_overlap(out_film, n * 16, in[i], in_bytes[i]) || ranges_overlap(out_mom, n * 8, in[i], in_bytes[i]))
+            return fail(c, RT_E_ARG, "temporal: an output overlaps an input");
+    if (ranges_overlap(out_film, n * 16, out_mom, n * 8)) return fail(c, RT_E_ARG, "temporal: out_film overlaps out_mom");
+    hipSetDevice(c->device);
+    rt_ctx::Temporal& t = c->tp;
+    HIPCHK(c, t.s_film.reserve(n)); HIPCHK(c, t.s_mom.reserve(n)); HIPCHK(c, t.s_feat.reserve(n));
+    HIPCHK(c, t.s_pos.reserve(n)); HIPCHK(c, t.s_out.reserve(n)); HIPCHK(c, t.s_outm.reserve(n));
+    if (hist) {
+        HIPCHK(c, t.s_hfilm.reserve(n)); HIPCHK(c, t.s_hmom.reserve(n));
+        HIPCHK(c, t.s_hfeat.reserve(n)); HIPCHK(c, t.s_hpos.reserve(n));
+    }
+    hipStream_t st = c->stream;
+    if ((rc = order_after_previous(c, st))) return rc;
+    HIPCHK(c, hipMemcpyAsync(t.s_film.get(), film, n * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(t.s_mom.get(), mom, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(t.s_feat.get(), feat, n * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(t.s_pos.get(), pos, n * 16, hipMemcpyHostToDevice, st));
+    if (hist) {
+        HIPCHK(c, hipMemcpyAsync(t.s_hfilm.get(), hfilm, n * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(t.s_hmom.get(), hmom, n * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(t.s_hfeat.get(), hfeat, n * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(t.s_hpos.get(), hpos, n * 16, hipMemcpyHostToDevice, st));
+    }
+    int counts[T_NCLASSES] = {};
+    rc = temporal_device(c, *d, res_x, res_y, t.s_film.get(), t.s_mom.get(), t.s_feat.get(), t.s_pos.get(),
+                         hist ? t.s_hfilm.get() : nullptr, hist ? t.s_hmom.get() : nullptr,
+                         hist ? t.s_hfeat.get() : nullptr, hist ? t.s_hpos.get() : nullptr, M, t.s_out.get(),
+                         t.s_outm.get(), counts, st);
+    const int rc2 = mark_done(c, st);
+    if (rc || rc2) return rc ? rc : rc2;
+    HIPCHK(c, hipMemcpyAsync(out_film, t.s_out.get(), n * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_mom, t.s_outm.get(), n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    temporal_fill_info(info, hist ? 1 : 0, counts);
+    return RT_OK;
+}
+
+static int impl_rt_temporal_begin(rt_ctx* c, const rt_temporal_desc* d) {
+    if (!c) return RT_E_ARG;
+    if (!d) return fail(c, RT_E_ARG, "temporal: null descriptor");
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if (!c->peers.empty()) return fail(c, RT_E_STATE, "temporal accumulation supports one-device contexts only");
+    rt_ctx::Temporal& t = c->tp;
+    if (t.live) return fail(c, RT_E_STATE, "a temporal session is already open (rt_temporal_end first)");
+    if (c->ad.live) return fail(c, RT_E_STATE, "rt_temporal_begin inside an adaptive session (rt_adaptive_end first)");
+    if ((rc = temporal_check_desc(c, d))) return rc;
+    if (d->feature_samples > dev_sampler(c).spp)
+        return fail(c, RT_E_ARG, "temporal: feature_samples exceeds the sampler's samples per pixel");
+    hipSetDevice(c->device);
+    const size_t n = (size_t)c->film.res_x * c->film.res_y;
+    for (int k = 0; k < 2; ++k) {
+        HIPCHK(c, t.film[k].reserve(n)); HIPCHK(c, t.mom[k].reserve(n));
+        HIPCHK(c, t.feat[k].reserve(n)); HIPCHK(c, t.pos[k].reserve(n));
+    }
+    t.desc = *d;
+    t.frames = 0;
+    t.cur = 0;
+    t.in_frame = false;
+    t.live = true;
+    return RT_OK;
+}
+
+namespace {
+// the frame inside its adaptive session: steps, feature + position pass, the stage, the filter, the copy out
+int temporal_frame_body(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_desc* dd, rt_pixel* film_out, int* counts) {
+    rt_ctx::Temporal& t = c->tp;
+    rt_ctx::Adaptive& a = c->ad;
+    int rc;
+    rt_adaptive_info cur{};
+    do {
+        if ((rc = impl_rt_adaptive_step(c, &cur))) return rc;
+    } while (cur.active_pixels > 0 && cur.index_done < ad->max_samples);
+    const int res_x = c->film.res_x, res_y = c->film.res_y, nx = t.cur ^ 1;
+    const size_t n = (size_t)res_x * res_y;
+    const bool hist = t.frames > 0;
+    if (dd) HIPCHK(c, c->dn.out.reserve(n));
+    hipStream_t st = c->stream;
+    if ((rc = order_after_previous(c, st))) return rc;
+    rc = hipMemsetAsync(t.feat[nx].get(), 0, n * sizeof(float4), st) == hipSuccess &&
+                 hipMemsetAsync(t.pos[nx].get(), 0, n * sizeof(float4), st) == hipSuccess
+             ? RT_OK : fail(c, RT_E_HIP, "feature and position film memset");
+    if (!rc) rc = features_device(c, 0, t.desc.feature_samples, t.feat[nx].get(), st, t.pos[nx].get());
+    if (!rc)
+        rc = temporal_device(c, t.desc, res_x, res_y, a.film.get(), a.mom.get(), t.feat[nx].get(), t.pos[nx].get(),
+                             hist ? t.film[t.cur].get() : nullptr, hist ? t.mom[t.cur].get() : nullptr,
+                             hist ? t.feat[t.cur].get() : nullptr, hist ? t.pos[t.cur].get() : nullptr, t.M,
+                             t.film[nx].get(), t.mom[nx].get(), counts, st);
+    if (!rc && dd)
+        rc = denoise_device(c, *dd, res_x, res_y, t.film[nx].get(), t.mom[nx].get(), t.feat[nx].get(), c->dn.out.get(),
+                            nullptr, st);
+    const int rc2 = mark_done(c, st);
+    if (rc || rc2) return rc ? rc : rc2;
+    HIPCHK(c, hipMemcpyAsync(film_out, dd ? c->dn.out.get() : t.film[nx].get(), n * sizeof(float4),
+                             hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return RT_OK;
+}
+}  // namespace
+
+static int impl_rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_desc* dd, const float* M,
+                                  rt_pixel* film_out, rt_temporal_info* info) {
+    if (!c) return RT_E_ARG;
+    rt_ctx::Temporal& t = c->tp;
+    if (!t.live) return fail(c, RT_E_STATE, "no temporal session is open (rt_temporal_begin first)");
+    if (!ad || !M || !film_out)
+        return fail(c, RT_E_ARG, "temporal frame: the adaptive descriptor, the matrix and film_out are required");
+    int rc;
+    if (dd) {
+        if ((rc = denoise_check_desc(c, dd))) return rc;
+        if (dd->feature_samples != t.desc.feature_samples)
+            return fail(c, RT_E_ARG, "temporal frame: the filter's feature_samples differs from the session's");
+    }
+    if ((rc = check_ready(c))) return rc;
+    if (t.desc.feature_samples > dev_sampler(c).spp)
+        return fail(c, RT_E_ARG, "temporal: feature_samples exceeds the sampler's samples per pixel");
+    if (c->ad.live) adaptive_release(c);  // (only a frame that ended in an exception leaves its session behind)
+    t.in_frame = true;
+    rc = impl_rt_adaptive_begin(c, ad);
+    t.in_frame = false;
+    if (rc) return rc;
+    int counts[T_NCLASSES] = {};
+    rc = temporal_frame_body(c, ad, dd, film_out, counts);
+    const std::string msg = c->err;
+    impl_rt_adaptive_end(c);
+    if (rc) return fail(c, rc, msg);  // the history is as it was: the failed frame is not part of it
+    temporal_fill_info(info, t.frames, counts);
+    t.cur ^= 1;
+    t.frames += 1;
+    std::memcpy(t.M, M, sizeof(t.M));
+    return RT_OK;
+}
+
+static int impl_rt_temporal_reset(rt_ctx* c) {
+    if (!c) return RT_E_ARG;
+    if (!c->tp.live) return fail(c, RT_E_STATE, "no temporal session is open");
+    c->tp.frames = 0;
+    return RT_OK;
+}
+
+static int impl_rt_temporal_end(rt_ctx* c) {
+    if (!c) return RT_E_ARG;
+    if (!c->tp.live) return fail(c, RT_E_STATE, "no temporal session is open");
+    hipSetDevice(c->device);
+    c->tp = rt_ctx::Temporal{};  // (hipFree waits for the work that still uses the buffers)
     return RT_OK;
 }
 
@@ -3185,6 +3438,35 @@ int rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int res_y, const 
 }
 int rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixel* film_out) {
     return guarded([&] { return impl_rt_adaptive_denoise(c, d, film_out); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_render_features_pos(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos) {
+    return guarded([&] { return impl_rt_render_features_pos(c, ib, ie, feat, pos); },
+                   [&](const std::string& m) { set_error(c, m); });
+}
+int rt_temporal_accumulate(rt_ctx* c, const rt_temporal_desc* d, int res_x, int res_y, const rt_pixel* film,
+                           const rt_moment* mom, const rt_feature* feat, const rt_position* pos, const rt_pixel* hist_film,
+                           const rt_moment* hist_mom, const rt_feature* hist_feat, const rt_position* hist_pos,
+                           const float* world_to_film_prev, rt_pixel* out_film, rt_moment* out_mom, rt_temporal_info* info) {
+    return guarded(
+        [&] {
+            return impl_rt_temporal_accumulate(c, d, res_x, res_y, film, mom, feat, pos, hist_film, hist_mom, hist_feat,
+                                               hist_pos, world_to_film_prev, out_film, out_mom, info);
+        },
+        [&](const std::string& m) { set_error(c, m); });
+}
+int rt_temporal_begin(rt_ctx* c, const rt_temporal_desc* d) {
+    return guarded([&] { return impl_rt_temporal_begin(c, d); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* adaptive, const rt_denoise_desc* denoise, const float* world_to_film,
+                      rt_pixel* film_out, rt_temporal_info* info) {
+    return guarded([&] { return impl_rt_temporal_frame(c, adaptive, denoise, world_to_film, film_out, info); },
+                   [&](const std::string& m) { set_error(c, m); });
+}
+int rt_temporal_reset(rt_ctx* c) {
+    return guarded([&] { return impl_rt_temporal_reset(c); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_temporal_end(rt_ctx* c) {
+    return guarded([&] { return impl_rt_temporal_end(c); }, [&](const std::string& m) { set_error(c, m); });
 }
 int rt_film_resolve(rt_ctx* c,const rt_pixel* film, uint8_t* out) {
     return guarded([&] { return impl_rt_film_resolve(c, film, out); }, [&](const std::string& m) { set_error(c, m); });

@@ -543,6 +543,9 @@ struct FeatureIO {
     const float4* rayD; int rsh;  // sample s's direction at rayD[s << rsh]
     const float4* hitB; const int* hitPrim;
     float4* feat;                 // res_x * res_y
+    // the position film, when pos is set: (o + t d, 1) of the same hits, the origin at rayO[s << rsh]
+    const float4* rayO = nullptr;
+    float4* pos = nullptr;        // res_x * res_y
 };
 hipError_t launch_feature_film(hipStream_t st, const DevScene& sc, const FeatureIO& io);
 // The filter over a res_x x res_y image.  prepare: film, mom, feat -> cv_out = (c.rgb, var), g = (normal, depth) / kf,
@@ -561,5 +564,22 @@ struct DenoiseIO {
 hipError_t launch_denoise_prepare(hipStream_t st, const DenoiseIO& io);
 // lds: steps 1 and 2 stage the block's tile and halo in LDS (same arithmetic, same bits)
 hipError_t launch_denoise_iter(hipStream_t st, const DenoiseIO& io, bool lds);
+
+// Temporal accumulation (rt_temporal.hip): one thread per pixel of a res_x x res_y image.  The current
+// frame (film, mom, feat, pos) is blended with the history (h*: null = none) fetched bilinearly where the pixel's
+// first hit projects through M, the previous camera's world-to-film matrix (column-major).
+enum { T_REPROJECTED = 0, T_DISOCCLUDED, T_BACKGROUND, T_NCLASSES };
+constexpr size_t kTemporalCtrWords = (size_t)T_NCLASSES * kCtrSubs * kCtrLine;
+struct TemporalIO {
+    int res_x, res_y;
+    const float4* film; const float2* mom; const float4* feat; const float4* pos;
+    const float4* hfilm; const float2* hmom; const float4* hfeat; const float4* hpos;
+    float M[16];
+    float kf;                     // (float)feature_samples
+    float normal_min, plane_rel, max_history;
+    float4* out_film; float2* out_mom;
+    unsigned long long* ctr;      // kTemporalCtrWords: the class counts, spread as the kernels' counter slots (ctr_word)
+};
+hipError_t launch_temporal_accumulate(hipStream_t st, const TemporalIO& io);
 
 }  // namespace rtmi

@@ -11,6 +11,10 @@ from . import capi
 DENOISE_DEFAULTS = dict(iterations=5, feature_samples=4, normal_power_log2=7, sigma_l=1.5, sigma_z=1.0,
                         lum_floor=0.01, depth_floor=0.002)
 
+# rt_temporal_desc defaults (frozen on the oracle's moving-camera Cornell frames,
+# tests/test_temporal_reference.py); max_history is 32 frames of 16 samples
+TEMPORAL_DEFAULTS = dict(normal_min=0.9, plane_rel=0.01, max_history=512.0, feature_samples=4)
+
 
 class Renderer:
     """One rt_ctx.  `device` is one HIP ordinal or a list of them (rt_options.devices: every pass renders on
@@ -203,6 +207,92 @@ class Renderer:
             return self.adaptive_denoise(**desc), info
         finally:
             self.adaptive_end()
+
+    # ---- temporal accumulation (rt_render_features_pos, rt_temporal_*) -------------------------
+    @staticmethod
+    def _temporal_desc(**kw):
+        unknown = set(kw) - set(TEMPORAL_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown temporal parameters: {sorted(unknown)}")
+        p = dict(TEMPORAL_DEFAULTS, **kw)
+        d = capi.rt_temporal_desc()
+        d.normal_min, d.plane_rel, d.max_history = float(p["normal_min"]), float(p["plane_rel"]), float(p["max_history"])
+        d.feature_samples = int(p["feature_samples"])
+        return d
+
+    @staticmethod
+    def _matrix16(m):
+        m = np.ascontiguousarray(m, np.float32).reshape(-1)
+        assert m.shape == (16,), "a column-major 4x4 matrix (scene.world_to_film)"
+        return m
+
+    def render_features_pos(self, index_begin, index_end, feat=None, pos=None):
+        """rt_render_features_pos: render_features that also accumulates the first-hit position film (hit point sums
+        and hit count, float32 [W*H, 4]); returns (feat, pos)."""
+        feat = self.new_film() if feat is None else feat
+        pos = self.new_film() if pos is None else pos
+        for a in (feat, pos):
+            assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (self.res[0] * self.res[1], 4)
+        self._chk("rt_render_features_pos", self.lib.rt_render_features_pos(
+            self.h, index_begin, index_end, feat.ctypes.data_as(C.POINTER(capi.rt_feature)),
+            pos.ctypes.data_as(C.POINTER(capi.rt_position))))
+        return feat, pos
+
+    def temporal_accumulate(self, film, mom, feat, pos, history=None, world_to_film_prev=None, res=None, **desc):
+        """rt_temporal_accumulate on host arrays of `res` (default: the film's).  history: None, or the previous
+        frame's (accumulated film, moments, features, positions), reprojected through world_to_film_prev.  Returns
+        (out_film [N, 4], out_mom [N, 2], info dict).  Descriptor fields default to TEMPORAL_DEFAULTS."""
+        W, H = res or self.res
+        n = W * H
+        cur = [np.ascontiguousarray(a, np.float32) for a in (film, mom, feat, pos)]
+        assert [a.shape for a in cur] == [(n, 4), (n, 2), (n, 4), (n, 4)]
+        types = [capi.rt_pixel, capi.rt_moment, capi.rt_feature, capi.rt_position]
+        args = [a.ctypes.data_as(C.POINTER(t)) for a, t in zip(cur, types)]
+        if history is None:
+            hist, args, m = [], args + [None] * 4, None
+        else:
+            hist = [np.ascontiguousarray(a, np.float32) for a in history]
+            assert [a.shape for a in hist] == [(n, 4), (n, 2), (n, 4), (n, 4)]
+            args += [a.ctypes.data_as(C.POINTER(t)) for a, t in zip(hist, types)]
+            m = self._matrix16(world_to_film_prev)
+        d = self._temporal_desc(**desc)
+        out, outm, info = np.zeros((n, 4), np.float32), np.zeros((n, 2), np.float32), capi.rt_temporal_info()
+        self._chk("rt_temporal_accumulate", self.lib.rt_temporal_accumulate(
+            self.h, C.byref(d), W, H, *args, None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
+            out.ctypes.data_as(C.POINTER(capi.rt_pixel)), outm.ctypes.data_as(C.POINTER(capi.rt_moment)),
+            C.byref(info)))
+        return out, outm, self._adaptive_info(info)
+
+    def temporal_begin(self, **desc):
+        """Open a temporal session: the history of the frames to come stays on the device."""
+        self._chk("rt_temporal_begin", self.lib.rt_temporal_begin(self.h, C.byref(self._temporal_desc(**desc))))
+
+    def temporal_frame(self, world_to_film, min_samples, step_samples=1, max_samples=None, rel_error=0.0,
+                       abs_floor=1e-3, denoise=None):
+        """rt_temporal_frame of the current camera, whose matrix is world_to_film (scene.world_to_film): an adaptive
+        frame (max_samples None: uniform, min_samples everywhere), accumulated against the session's history and,
+        with denoise = a dict of rt_denoise_desc fields (may be empty: DENOISE_DEFAULTS), filtered.  Returns (film,
+        info dict)."""
+        ad = self._adaptive_desc(min_samples, step_samples, min_samples if max_samples is None else max_samples,
+                                 rel_error, abs_floor)
+        dd = None if denoise is None else self._denoise_desc(**denoise)
+        m = self._matrix16(world_to_film)
+        out, info = self.new_film(), capi.rt_temporal_info()
+        self._chk("rt_temporal_frame", self.lib.rt_temporal_frame(
+            self.h, C.byref(ad), None if dd is None else C.byref(dd), m.ctypes.data_as(C.POINTER(C.c_float)),
+            out.ctypes.data_as(C.POINTER(capi.rt_pixel)), C.byref(info)))
+        return out, self._adaptive_info(info)
+
+    def temporal_reset(self):
+        """Drop the session's history: the next frame is a first frame."""
+        self._chk("rt_temporal_reset", self.lib.rt_temporal_reset(self.h))
+
+    def temporal_end(self):
+        self._chk("rt_temporal_end", self.lib.rt_temporal_end(self.h))
+
+    def set_camera(self, camera):
+        """rt_camera_set alone (allowed inside a temporal session)."""
+        self._chk("rt_camera_set", self.lib.rt_camera_set(self.h, C.byref(camera.desc())))
 
     def resolve(self, film, srgb=False):
         """rt_film_resolve (the reference's linear 255·x) or rt_film_resolve_srgb (pbrt's sRGB encoding)."""

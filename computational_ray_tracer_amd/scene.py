@@ -95,10 +95,15 @@ class OrthographicCamera:
     worldup: tuple = (0.0, 1.0, 0.0)
     res: tuple = (500, 500)
 
-    def desc(self):
+    def matrices(self):
+        """(raster_to_camera, camera_to_world, raster_to_screen), float64."""
         r2s, c2w = _camera_base(self.sensor[0], self.sensor[1], self.res, self.position, self.look, self.worldup)
         c2s = scale((1, 1, 1.0 / (self.far - self.near))) @ translate((0, 0, -self.near))   # Cameras.h:222-223
-        return _camera_desc(capi.RT_CAMERA_ORTHOGRAPHIC, np.linalg.inv(c2s) @ r2s, c2w, r2s)
+        return np.linalg.inv(c2s) @ r2s, c2w, r2s
+
+    def desc(self):
+        r2c, c2w, r2s = self.matrices()
+        return _camera_desc(capi.RT_CAMERA_ORTHOGRAPHIC, r2c, c2w, r2s)
 
 
 @dataclass
@@ -186,6 +191,23 @@ class PerspectiveCamera:
         r2c, c2w = self.matrices()
         return _camera_desc(capi.RT_CAMERA_PERSPECTIVE, r2c, c2w, lens_radius=self.lens_radius,
                             focal_distance=self.focal_distance)
+
+
+def world_to_film(camera):
+    """The camera's world-to-film matrix for the temporal stage, column-major float32 [16]: a world
+    point (x, y, z, 1) goes to (X, Y, ., W) with (X / W, Y / W) its film position, pixel (x = id % resX, row =
+    id // resX) covering [x, x + 1) x [row, row + 1), and W > 0 in front of a perspective camera (W = 1 for an
+    orthographic one).  Built in float64 as inverse(camera_to_world * raster_to_camera), the matrices desc() hands to
+    the renderer, then the kept raster quirk y = resY - row (RayTracerTestApp.h:289-291): a sample of that pixel has
+    raster y in [resY - row, resY - row + 1), so the film's Y is (resY + 1) W - raster y.  The lens radius is ignored
+    (the pixel's centre of projection).  PerspectiveCamera and OrthographicCamera only."""
+    if isinstance(camera, (PerspectiveCamera, OrthographicCamera)):
+        r2c, c2w = camera.matrices()[:2]
+    else:
+        raise TypeError(f"world_to_film: no film matrix for {type(camera).__name__}")
+    m = np.linalg.inv(c2w @ r2c)
+    m[1] = (camera.res[1] + 1) * m[3] - m[1]
+    return colmajor(m)
 
 
 # ------------------------------------------------------------------------------- sampler / film

@@ -342,6 +342,55 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_desc* desc, int res_x, int res_y, c
  * session's film and moments are not modified. */
 int rt_adaptive_denoise(rt_ctx* ctx, const rt_denoise_desc* desc, rt_pixel* film_out);
 
+/* ---- temporal accumulation ------------------------------------------------------- */
+/* First-hit position film: per pixel the sums, over the hits of a feature pass, of the render-space hit point
+ * o + t d (per component, nothing fused) and the number of hits (a miss adds nothing). */
+typedef struct { float x, y, z, hits; } rt_position;      /* 16 B, sums over the pass's hits */
+/* rt_render_features that also accumulates (+=) the position film pos_inout (res_x*res_y, host memory) of the same
+ * first hits; feat_inout comes out exactly as rt_render_features leaves it. */
+int rt_render_features_pos(rt_ctx* ctx, int index_begin, int index_end, rt_feature* feat_inout, rt_position* pos_inout);
+/* Reprojection of the previous frame's accumulated film and moments through the previous camera, rejection of taps
+ * whose geometry disagrees, and a sample-count-weighted running mean; float32 in a fixed operation order. */
+typedef struct {
+    float normal_min;       /* -1..1: a history tap needs n_p.n_q >= normal_min                              */
+    float plane_rel;        /* >= 0, finite: and |n_p.(P_q - P)| <= plane_rel * depth                        */
+    float max_history;      /* >= 1: cap of the accumulated sample count n'                                  */
+    int feature_samples;    /* k >= 1: indices accumulated in the feature and position films                 */
+    int reserved[4];
+} rt_temporal_desc;         /* 32 B */
+typedef struct {
+    int frames;             /* frames behind the history that was used (0: none, the outputs are the inputs)  */
+    int reprojected;        /* pixels blended with their history                                              */
+    int disoccluded;        /* pixels with a first hit and no usable history                                  */
+    int background;         /* pixels whose feature pass hit nothing                                          */
+} rt_temporal_info;         /* pixels with film.w == 0 are in no class */
+/* The stage alone on host arrays of any res_x x res_y (res_x*res_y each): the current frame's film, moments, features
+ * and positions, the previous frame's accumulated film and moments with its features and positions, and the previous
+ * camera's world-to-film matrix (column-major; film space puts pixel (x, row) on [x, x+1) x [row, row+1)).  All four
+ * hist_* NULL: no history (world_to_film_prev may be NULL too).  out = (mean * n', n') and (m1 * n', m2 * n'), an
+ * ordinary film and moment film.  The context supplies the device, the stream and a workspace.  RT_E_ARG: bad
+ * descriptor, NULL array, only some hist_* NULL, or an output overlapping an input.  info may be NULL.  Blocks. */
+int rt_temporal_accumulate(rt_ctx* ctx, const rt_temporal_desc* desc, int res_x, int res_y, const rt_pixel* film,
+                           const rt_moment* mom, const rt_feature* feat, const rt_position* pos,
+                           const rt_pixel* hist_film, const rt_moment* hist_mom, const rt_feature* hist_feat,
+                           const rt_position* hist_pos, const float* world_to_film_prev, rt_pixel* out_film,
+                           rt_moment* out_mom, rt_temporal_info* info);
+/* Frame session: the history (accumulated film and moments, features, positions: 56 B per pixel, ping-ponged) stays
+ * on the device.  RT_E_STATE: a temporal or an adaptive session is already open, or the context has more than one
+ * device.  While it is open rt_film_set, rt_set_shard, rt_adaptive_begin and rt_render_adaptive return RT_E_STATE;
+ * rt_camera_set and the ordinary passes are allowed. */
+int rt_temporal_begin(rt_ctx* ctx, const rt_temporal_desc* desc);
+/* One frame of the current camera: an internal adaptive session by `adaptive` (uniform: min_samples == max_samples),
+ * the features and positions of indices [0, feature_samples), the accumulation against the history, the a-trous filter
+ * with the frame's features when `denoise` is not NULL (its feature_samples must equal the session's), the result
+ * copied to film_out (res_x*res_y, host).  The unfiltered accumulation, the features, the positions and
+ * world_to_film (this frame's camera) become the next frame's history.  info may be NULL.  Blocks. */
+int rt_temporal_frame(rt_ctx* ctx, const rt_adaptive_desc* adaptive, const rt_denoise_desc* denoise,
+                      const float* world_to_film, rt_pixel* film_out, rt_temporal_info* info);
+/* Drop the history (a cut, or a change of the scene): the next frame is a first frame. */
+int rt_temporal_reset(rt_ctx* ctx);
+int rt_temporal_end(rt_ctx* ctx);
+
 /* a20 resolve (RayTracerTestApp.h:424-452): rgbsum/weightsum -> XYZFromSensorRGB -> sRGB -> clamp -> u8. */
 int rt_film_resolve(rt_ctx* ctx, const rt_pixel* film, uint8_t* rgb_out);
 
