@@ -27,6 +27,7 @@ RT_ILLUM_D65, RT_ILLUM_A, RT_ILLUM_D50, RT_ILLUM_F1, RT_ILLUM_ACES_D60, RT_ILLUM
 RT_INTEGRATOR_REFERENCE, RT_INTEGRATOR_PATH, RT_INTEGRATOR_PATH_MIS = 0, 1, 2
 ABI_VERSION = 10
 RT_MAX_DEVICES = 16
+RT_CHAIN_MAX = 4
 QUEUE_SHARDS = 8  # RT_QUEUE_SHARDS
 
 F16 = C.c_float * 16
@@ -66,7 +67,7 @@ class rt_feature(C.Structure):
 class rt_denoise_desc(C.Structure):
     _fields_ = [("iterations", C.c_int), ("feature_samples", C.c_int), ("normal_power_log2", C.c_int),
                 ("sigma_l", C.c_float), ("sigma_z", C.c_float), ("lum_floor", C.c_float), ("depth_floor", C.c_float),
-                ("reserved", C.c_int * 1)]
+                ("chain_depth", C.c_int)]
 
 
 class rt_position(C.Structure):
@@ -75,7 +76,7 @@ class rt_position(C.Structure):
 
 class rt_temporal_desc(C.Structure):
     _fields_ = [("normal_min", C.c_float), ("plane_rel", C.c_float), ("max_history", C.c_float),
-                ("feature_samples", C.c_int), ("reserved", C.c_int * 4)]
+                ("feature_samples", C.c_int), ("chain_depth", C.c_int), ("reserved", C.c_int * 3)]
 
 
 class rt_temporal_info(C.Structure):
@@ -172,6 +173,7 @@ EXPORTS = [
     "rt_render_features", "rt_denoise", "rt_adaptive_denoise",
     "rt_render_features_pos", "rt_temporal_accumulate", "rt_temporal_begin", "rt_temporal_frame", "rt_temporal_reset",
     "rt_temporal_end",
+    "rt_render_features_chain",
 ]
 
 _lib = None
@@ -254,6 +256,7 @@ def load_library(path=None):
                         P(rt_pixel), P(C.c_float)], C.c_int),
         "rt_adaptive_denoise": ([C.c_void_p, P(rt_denoise_desc), P(rt_pixel)], C.c_int),
         "rt_render_features_pos": ([C.c_void_p, C.c_int, C.c_int, P(rt_feature), P(rt_position)], C.c_int),
+        "rt_render_features_chain": ([C.c_void_p, C.c_int, C.c_int, C.c_int, P(rt_feature), P(rt_position)], C.c_int),
         "rt_temporal_accumulate": ([C.c_void_p, P(rt_temporal_desc), C.c_int, C.c_int, P(rt_pixel), P(rt_moment),
                                     P(rt_feature), P(rt_position), P(rt_pixel), P(rt_moment), P(rt_feature),
                                     P(rt_position), P(C.c_float), P(rt_pixel), P(rt_moment), P(rt_temporal_info)],

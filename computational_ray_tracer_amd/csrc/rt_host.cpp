@@ -478,6 +478,8 @@ struct Batch {
     DevBuf<float4> neeRec;
     DevBuf<int> neeSlot;
     NeeSlots nee;                          // neeSlot's regions for the current queue capacity
+    // specular-chain guides: two ping-pong queues of continuation rays, interleaved pairs like ray
+    DevBuf<float4> chainRay;
 
     float4* rayO() const { return ray.get(); }
     float4* rayD() const { return ray.get() + 1; }
@@ -500,6 +502,9 @@ struct Work {
     // multi-level scenes in path mode: the queue positions of the rays the trace kernel's BVH walk could not decide
     // (TraceIO fb_pos; k_trace_fallback traces them with the reference BFS)
     DevBuf<int> tfb;
+    // specular-chain guides: the counters of the continuation queues, region l - 1 for level l's queue (its shard
+    // lengths, its trace's chunk tickets and fallback list length), and the unused region the last level is given
+    DevBuf<int> chain_ctr;
     hipStream_t stream = nullptr;  // lanes >= 1: own stream (lane 0 runs on the caller's stream)
     hipEvent_t film_done = nullptr;
 };
@@ -658,8 +663,9 @@ struct rt_ctx {
         int cur = 0;                 // active[cur] is the current list (info.active_pixels entries)
         DevBuf<float> block_error;
         DevBuf<int> converged, wave_count, wave_offset, totals;
-        DevBuf<float4> feat;         // rt_adaptive_denoise: the feature film of indices [0, feat_k), 0: not rendered
-        int feat_k = 0;
+        DevBuf<float4> feat;         // rt_adaptive_denoise: the feature film of indices [0, feat_k), 0: not rendered,
+        int feat_k = 0;              // through the chain pass of depth feat_chain
+        int feat_chain = 0;
     } ad;
     // denoiser workspace (rt_denoise, rt_adaptive_denoise): staging of the host arrays, the guides and
     // the (c, var) ping-pong; grows on demand
@@ -2576,12 +2582,23 @@ static int impl_rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, c
 // ---- denoiser: the feature pass reuses the reference-mode workspace and the generate / trace kernels;
 // the filter runs on device arrays (an adaptive session's own, or staged copies of the caller's host arrays).
 namespace {
+int chain_check_depth(rt_ctx* c, int chain_depth) {
+    if (chain_depth < 0 || chain_depth > kChainMax) return fail(c, RT_E_ARG, "chain_depth must be 0..RT_CHAIN_MAX");
+    return RT_OK;
+}
+
 // Features of indices [ib, ie) of the full work list added to the device feature film: per batch the camera rays, the
 // closest hits as the current integrator's first trace finds them (reference: the culled tile set when the scene
 // culls; path: every triangle), then k_feature_film.  Batches as render_device_body's reference loop.
 // pos (may be null): the position film of the same hits.
-int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, float4* pos = nullptr) {
+// chain_depth > 0 under a path integrator: the guides of the end of each sample's specular chain.  Per
+// level, k_chain_level over the level's queue and, for the rays it appends, the trace of a path bounce; then
+// k_chain_film.  The chain's per-slot state uses the reference workspace's wavelength and pdf arrays, which k_generate
+// fills and the feature pass never reads.
+int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, float4* pos = nullptr,
+                    int chain_depth = 0) {
     int rc;
+    if ((rc = chain_check_depth(c, chain_depth))) return rc;
     if (ib < 0 || ie < ib) return fail(c, RT_E_ARG, "invalid index range");
     if ((rc = ensure_sobol(c))) return rc;
     DevSampler smp = dev_sampler(c);
@@ -2603,6 +2620,17 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
     const DevFilm fd = dev_film(c);
     Work& w = c->ws[0];
     if ((rc = ensure_workspace(c, w, ncap, false))) return rc;
+    // (the reference integrator consults no material: every chain has length 0)
+    const bool chain = path && chain_depth > 0;
+    const bool dyn = c->dsc.qcap != 1;  // the bounce rays' trace: per-wave tickets on multi-level octrees
+    float eta_bk7 = 0.f;
+    if (chain) {
+        if (ncap > ((size_t)1 << kChainSlotBits)) return fail(c, RT_E_LIMIT, "chain pass: more than 2^28 samples per batch");
+        HIPCHK(c, w.b.chainRay.reserve(4 * ncap));
+        HIPCHK(c, w.chain_ctr.reserve((size_t)(kChainMax + 1) * kQRegion));
+        if (dyn) HIPCHK(c, w.tfb.reserve(ncap));
+        eta_bk7 = c->hs.BK7.query(550.f);
+    }
     for (int b0 = ib; b0 < ie; b0 += B) {
         const int nIdx = std::min(B, ie - b0);
         const int nS = nIdx * n_work;
@@ -2615,9 +2643,47 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
         e0 = ev_start(c, st);
         HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()));
         ev_mark(c, st, ST_TRACE, e0);
-        const FeatureIO fio{c->d_work.get(), n_work, nIdx, w.b.rayD(), 1, w.b.hitB.get(), w.b.hitPrim.get(), feat,
-                            w.b.rayO(), pos};
-        HIPCHK(c, launch_feature_film(st, c->dsc, fio));
+        if (!chain) {
+            const FeatureIO fio{c->d_work.get(), n_work, nIdx, w.b.rayD(), 1, w.b.hitB.get(), w.b.hitPrim.get(), feat,
+                                w.b.rayO(), pos};
+            HIPCHK(c, launch_feature_film(st, c->dsc, fio));
+            continue;
+        }
+        const Batch& b = w.b;
+        const DevScene dsl = lane_scene(c, w);
+        int* const ctr = w.chain_ctr.get();
+        HIPCHK(c, hipMemsetAsync(ctr, 0, (size_t)chain_depth * kQRegion * sizeof(int), st));
+        ChainIO cio{};
+        cio.hitB = b.hitB.get(); cio.hitPrim = b.hitPrim.get();
+        cio.depth = chain_depth;
+        cio.eta_bk7 = eta_bk7;
+        cio.n[0] = b.lamB.get(); cio.n[1] = b.pdfA.get(); cio.n[2] = b.pdfB.get();
+        cio.res = b.lamA.get();
+        const int S = shard_stride(nS, nsh);
+        for (int level = 0; level <= chain_depth; ++level) {
+            int* const reg = level > 0 ? ctr + (size_t)(level - 1) * kQRegion : nullptr;  // this level's queue
+            cio.level = level;
+            cio.q = level > 0 ? QueueView{reg + kQLen, S, 0, nsh} : QueueView{nullptr, S, nS, nsh};
+            cio.ray = level > 0 ? b.chainRay.get() + 2 * ncap * (size_t)((level - 1) & 1) : b.rayO();
+            cio.nray = b.chainRay.get() + 2 * ncap * (size_t)(level & 1);
+            cio.nlen = ctr + (size_t)level * kQRegion + kQLen;
+            if (level > 0) {  // the continuation rays, traced as a path bounce: every triangle, every shape, no tMax
+                TraceIO tio{cio.ray, cio.ray + 1, cio.q, 0, b.hitB.get(), b.hitPrim.get(),
+                            dyn ? reg + kQTraceTicket : nullptr, 1};
+                if (dyn) {
+                    tio.fb_pos = w.tfb.get();
+                    tio.fb_len = reg + kQTraceFallback;
+                }
+                e0 = ev_start(c, st);
+                HIPCHK(c, launch_trace_closest(st, c->grid, c->dsc.qcap, dsl, tio, c->d_ctr.get()));
+                if (tio.fb_pos && !c->dsc.coop_ok)
+                    HIPCHK(c, launch_trace_fallback(st, c->grid, c->dsc.qcap, dsl, tio, c->d_ctr.get()));
+                ev_mark(c, st, ST_TRACE, e0);
+            }
+            HIPCHK(c, launch_chain_level(st, c->grid, dsl, cio));
+        }
+        const ChainFilmIO fio{c->d_work.get(), n_work, nIdx, b.rayO(), b.lamA.get(), feat, pos};
+        HIPCHK(c, launch_chain_film(st, fio));
     }
     return RT_OK;
 }
@@ -2631,6 +2697,8 @@ int denoise_check_desc(rt_ctx* c, const rt_denoise_desc* d) {
         return fail(c, RT_E_ARG, "denoise: sigma_l and sigma_z must be finite and > 0");
     if (!std::isfinite(d->lum_floor) || d->lum_floor < 0 || !std::isfinite(d->depth_floor) || d->depth_floor < 0)
         return fail(c, RT_E_ARG, "denoise: lum_floor and depth_floor must be finite and >= 0");
+    if (d->chain_depth < 0 || d->chain_depth > kChainMax)
+        return fail(c, RT_E_ARG, "denoise: chain_depth must be 0..RT_CHAIN_MAX");
     return RT_OK;
 }
 
@@ -2669,12 +2737,13 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 }
 }  // namespace
 
-// rt_render_features (with_pos false: pos is not looked at) and rt_render_features_pos
+// rt_render_features (with_pos false: pos is not looked at), rt_render_features_pos and rt_render_features_chain
 static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos = nullptr,
-                                   bool with_pos = false) {
+                                   bool with_pos = false, int chain_depth = 0) {
     if (!c || !feat || (with_pos && !pos)) return RT_E_ARG;
-    int rc = check_ready(c);
+    int rc = chain_check_depth(c, chain_depth);
     if (rc) return rc;
+    if ((rc = check_ready(c))) return rc;
     if (!c->peers.empty()) return fail(c, RT_E_STATE, "the feature pass supports one-device contexts only");
     hipSetDevice(c->device);
     const size_t n = (size_t)c->film.res_x * c->film.res_y;
@@ -2687,7 +2756,7 @@ static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat, 
     if ((rc = order_after_previous(c, st))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->dn.feat.get(), feat, n * sizeof(float4), hipMemcpyHostToDevice, st));
     if (with_pos) HIPCHK(c, hipMemcpyAsync(d_pos, pos, n * sizeof(float4), hipMemcpyHostToDevice, st));
-    rc = features_device(c, ib, ie, c->dn.feat.get(), st, d_pos);
+    rc = features_device(c, ib, ie, c->dn.feat.get(), st, d_pos, chain_depth);
     const int rc2 = mark_done(c, st);
     if (rc || rc2) return rc ? rc : rc2;
     HIPCHK(c, hipMemcpyAsync(feat, c->dn.feat.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
@@ -2748,12 +2817,16 @@ static int impl_rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixe
     HIPCHK(c, c->dn.out.reserve(n));
     hipStream_t st = c->stream;
     if ((rc = order_after_previous(c, st))) return rc;
-    if (a.feat_k != d->feature_samples) {  // once per session (again only if the caller changes k)
+    // once per session (again only if the caller changes k or the chain depth)
+    if (a.feat_k != d->feature_samples || a.feat_chain != d->chain_depth) {
         a.feat_k = 0;
         rc = hipMemsetAsync(a.feat.get(), 0, n * sizeof(float4), st) == hipSuccess ? RT_OK
                                                                                    : fail(c, RT_E_HIP, "feature film memset");
-        if (!rc) rc = features_device(c, 0, d->feature_samples, a.feat.get(), st);
-        if (!rc) a.feat_k = d->feature_samples;
+        if (!rc) rc = features_device(c, 0, d->feature_samples, a.feat.get(), st, nullptr, d->chain_depth);
+        if (!rc) {
+            a.feat_k = d->feature_samples;
+            a.feat_chain = d->chain_depth;
+        }
     }
     if (!rc)
         rc = denoise_device(c, *d, c->film.res_x, c->film.res_y, a.film.get(), a.mom.get(), a.feat.get(),
@@ -2774,6 +2847,8 @@ int temporal_check_desc(rt_ctx* c, const rt_temporal_desc* d) {
     if (!std::isfinite(d->plane_rel) || d->plane_rel < 0) return fail(c, RT_E_ARG, "temporal: plane_rel must be finite and >= 0");
     if (!(d->max_history >= 1.f)) return fail(c, RT_E_ARG, "temporal: max_history must be at least 1");
     if (d->feature_samples < 1) return fail(c, RT_E_ARG, "temporal: feature_samples must be at least 1");
+    if (d->chain_depth < 0 || d->chain_depth > kChainMax)
+        return fail(c, RT_E_ARG, "temporal: chain_depth must be 0..RT_CHAIN_MAX");
     return RT_OK;
 }
 
@@ -2818,6 +2893,10 @@ void temporal_fill_info(rt_temporal_info* info, int frames, const int* counts) {
 
 static int impl_rt_render_features_pos(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos) {
     return impl_rt_render_features(c, ib, ie, feat, pos, true);
+}
+
+static int impl_rt_render_features_chain(rt_ctx* c, int ib, int ie, int chain_depth, rt_feature* feat, rt_position* pos) {
+    return impl_rt_render_features(c, ib, ie, feat, pos, pos != nullptr, chain_depth);
 }
 
 static int impl_rt_temporal_accumulate(rt_ctx* c, const rt_temporal_desc* d, int res_x, int res_y, const rt_pixel* film,
@@ -2922,7 +3001,8 @@ int temporal_frame_body(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_
     rc = hipMemsetAsync(t.feat[nx].get(), 0, n * sizeof(float4), st) == hipSuccess &&
                  hipMemsetAsync(t.pos[nx].get(), 0, n * sizeof(float4), st) == hipSuccess
              ? RT_OK : fail(c, RT_E_HIP, "feature and position film memset");
-    if (!rc) rc = features_device(c, 0, t.desc.feature_samples, t.feat[nx].get(), st, t.pos[nx].get());
+    if (!rc)
+        rc = features_device(c, 0, t.desc.feature_samples, t.feat[nx].get(), st, t.pos[nx].get(), t.desc.chain_depth);
     if (!rc)
         rc = temporal_device(c, t.desc, res_x, res_y, a.film.get(), a.mom.get(), t.feat[nx].get(), t.pos[nx].get(),
                              hist ? t.film[t.cur].get() : nullptr, hist ? t.mom[t.cur].get() : nullptr,
@@ -2952,6 +3032,8 @@ static int impl_rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* ad, const r
         if ((rc = denoise_check_desc(c, dd))) return rc;
         if (dd->feature_samples != t.desc.feature_samples)
             return fail(c, RT_E_ARG, "temporal frame: the filter's feature_samples differs from the session's");
+        if (dd->chain_depth != t.desc.chain_depth)
+            return fail(c, RT_E_ARG, "temporal frame: the filter's chain_depth differs from the session's");
     }
     if ((rc = check_ready(c))) return rc;
     if (t.desc.feature_samples > dev_sampler(c).spp)
@@ -3438,6 +3520,10 @@ int rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int res_y, const 
 }
 int rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixel* film_out) {
     return guarded([&] { return impl_rt_adaptive_denoise(c, d, film_out); }, [&](const std::string& m) { set_error(c, m); });
+}
+int rt_render_features_chain(rt_ctx* c, int ib, int ie, int chain_depth, rt_feature* feat, rt_position* pos) {
+    return guarded([&] { return impl_rt_render_features_chain(c, ib, ie, chain_depth, feat, pos); },
+                   [&](const std::string& m) { set_error(c, m); });
 }
 int rt_render_features_pos(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos) {
     return guarded([&] { return impl_rt_render_features_pos(c, ib, ie, feat, pos); },

@@ -548,6 +548,38 @@ struct FeatureIO {
     float4* pos = nullptr;        // res_x * res_y
 };
 hipError_t launch_feature_film(hipStream_t st, const DevScene& sc, const FeatureIO& io);
+// Specular-chain guides (rt_chain.hip): a sample whose hit is a mirror or a dielectric is followed along
+// the deterministic specular ray, level by level, and the guides describe the end of its chain.  One launch of
+// k_chain_level per level: an item that stops is finished into res[slot], one that continues is appended (wave
+// ballot, one atomic per wave) to the next level's queue, shard by shard, which the bounce rays' k_trace_closest traces.
+static const int kChainMax = 4;          // RT_CHAIN_MAX: continuations per sample at most
+static const int kChainSlotBits = 28;    // a continuation's origin w = bits(slot | reflections << kChainSlotBits)
+struct ChainIO {
+    QueueView q;                  // this level's queue; level 0: the dense camera-ray queue (slot = position)
+    const float4* ray;            // interleaved (o, d) pairs: ray k at ray[2k], ray[2k + 1]; levels >= 1: the
+                                  // direction's w = D, the chain's length up to this ray's origin
+    const float4* hitB; const int* hitPrim;  // at queue position
+    int level, depth;             // 0 <= level <= depth <= kChainMax
+    float eta_bk7;                // the eta of a dielectric with eta == 0: glass-BK7 at 550 nm
+    // per sample slot: the reflection normals N[0..2] (xyz) while the chain runs, and res = N[3], then the result:
+    // (the final normal mirrored back through N, D), or w = -1 for a chain that ended in a miss
+    float4* n[3];
+    float4* res;
+    float4* nray;                 // the next level's queue (same shard stride), lengths at nlen + j kQStride (zeroed)
+    int* nlen;
+};
+hipError_t launch_chain_level(hipStream_t st, int grid, const DevScene& sc, const ChainIO& io);
+// Per owned pixel, in increasing index order: feat += res[s] and, when pos is set, pos += (o0 + D d0, 1), for the
+// samples s = i * n_pixels + j whose chain ended in a hit; (o0, d0) at ray[2s], ray[2s + 1].
+struct ChainFilmIO {
+    const int* work_pixels; int n_pixels; int n_index;
+    const float4* ray;
+    const float4* res;
+    float4* feat;
+    float4* pos = nullptr;
+};
+hipError_t launch_chain_film(hipStream_t st, const ChainFilmIO& io);
+
 // The filter over a res_x x res_y image.  prepare: film, mom, feat -> cv_out = (c.rgb, var), g = (normal, depth) / kf,
 // gz = the depth gradient.  iter: one a-trous iteration of step `step` from cv_in to cv_out, or, when out is set (the
 // last iteration), to out = (c n, n) and var_out (may be null).

@@ -15,6 +15,10 @@ DENOISE_DEFAULTS = dict(iterations=5, feature_samples=4, normal_power_log2=7, si
 # tests/test_temporal_reference.py); max_history is 32 frames of 16 samples
 TEMPORAL_DEFAULTS = dict(normal_min=0.9, plane_rel=0.01, max_history=512.0, feature_samples=4)
 
+# chain_depth of rt_denoise_desc and rt_temporal_desc: 0 = first-surface guides.  Accepted next to the
+# fields above by every call that takes them; kept apart because the two dicts above are pinned to the numpy references'.
+CHAIN_DEFAULTS = dict(chain_depth=0)
+
 
 class Renderer:
     """One rt_ctx.  `device` is one HIP ordinal or a list of them (rt_options.devices: every pass renders on
@@ -148,15 +152,16 @@ class Renderer:
     # ---- denoiser (rt_render_features, rt_denoise, rt_adaptive_denoise) ------------------------
     @staticmethod
     def _denoise_desc(**kw):
-        unknown = set(kw) - set(DENOISE_DEFAULTS)
+        unknown = set(kw) - set(DENOISE_DEFAULTS) - set(CHAIN_DEFAULTS)
         if unknown:
             raise TypeError(f"unknown denoise parameters: {sorted(unknown)}")
-        p = dict(DENOISE_DEFAULTS, **kw)
+        p = {**DENOISE_DEFAULTS, **CHAIN_DEFAULTS, **kw}
         d = capi.rt_denoise_desc()
         d.iterations, d.feature_samples = int(p["iterations"]), int(p["feature_samples"])
         d.normal_power_log2 = int(p["normal_power_log2"])
         d.sigma_l, d.sigma_z = float(p["sigma_l"]), float(p["sigma_z"])
         d.lum_floor, d.depth_floor = float(p["lum_floor"]), float(p["depth_floor"])
+        d.chain_depth = int(p["chain_depth"])
         return d
 
     def render_features(self, index_begin, index_end, feat=None):
@@ -211,13 +216,14 @@ class Renderer:
     # ---- temporal accumulation (rt_render_features_pos, rt_temporal_*) -------------------------
     @staticmethod
     def _temporal_desc(**kw):
-        unknown = set(kw) - set(TEMPORAL_DEFAULTS)
+        unknown = set(kw) - set(TEMPORAL_DEFAULTS) - set(CHAIN_DEFAULTS)
         if unknown:
             raise TypeError(f"unknown temporal parameters: {sorted(unknown)}")
-        p = dict(TEMPORAL_DEFAULTS, **kw)
+        p = {**TEMPORAL_DEFAULTS, **CHAIN_DEFAULTS, **kw}
         d = capi.rt_temporal_desc()
         d.normal_min, d.plane_rel, d.max_history = float(p["normal_min"]), float(p["plane_rel"]), float(p["max_history"])
         d.feature_samples = int(p["feature_samples"])
+        d.chain_depth = int(p["chain_depth"])
         return d
 
     @staticmethod
@@ -237,6 +243,20 @@ class Renderer:
             self.h, index_begin, index_end, feat.ctypes.data_as(C.POINTER(capi.rt_feature)),
             pos.ctypes.data_as(C.POINTER(capi.rt_position))))
         return feat, pos
+
+    def render_features_chain(self, index_begin, index_end, chain_depth, feat=None, pos=None, with_pos=True):
+        """rt_render_features_chain: render_features_pos whose samples follow mirrors and dielectrics for up to
+        chain_depth continuation rays (0..capi.RT_CHAIN_MAX) and describe the end of that chain.
+        Returns (feat, pos); with_pos=False: the feature film alone (pos_inout NULL), returns feat."""
+        feat = self.new_film() if feat is None else feat
+        if with_pos:
+            pos = self.new_film() if pos is None else pos
+        for a in (feat, pos) if with_pos else (feat,):
+            assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (self.res[0] * self.res[1], 4)
+        self._chk("rt_render_features_chain", self.lib.rt_render_features_chain(
+            self.h, index_begin, index_end, int(chain_depth), feat.ctypes.data_as(C.POINTER(capi.rt_feature)),
+            pos.ctypes.data_as(C.POINTER(capi.rt_position)) if with_pos else None))
+        return (feat, pos) if with_pos else feat
 
     def temporal_accumulate(self, film, mom, feat, pos, history=None, world_to_film_prev=None, res=None, **desc):
         """rt_temporal_accumulate on host arrays of `res` (default: the film's).  history: None, or the previous

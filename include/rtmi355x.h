@@ -330,16 +330,16 @@ typedef struct {
     float sigma_l, sigma_z; /* > 0, finite                                            */
     float lum_floor;        /* >= 0, finite; added to sigma_l*sqrt(var)               */
     float depth_floor;      /* >= 0, finite; times z_p, added to the depth denominator */
-    int reserved[1];
+    int chain_depth;        /* 0..RT_CHAIN_MAX: the sessions render their guides with rt_render_features_chain */
 } rt_denoise_desc;          /* 32 B */
 /* Filter host arrays of any res_x x res_y (film, mom, feat, out: res_x*res_y each; variance_out: res_x*res_y floats
  * or NULL): out = (filtered mean * film.w, film.w), so both resolves apply.  The context supplies the device, the
  * stream and a workspace.  RT_E_ARG: bad descriptor, NULL array, or out overlapping an input.  Blocks. */
 int rt_denoise(rt_ctx* ctx, const rt_denoise_desc* desc, int res_x, int res_y, const rt_pixel* film, const rt_moment* mom,
                const rt_feature* feat, rt_pixel* out, float* variance_out);
-/* Inside an adaptive session: the features of indices [0, feature_samples) (rendered once per session into a device
- * buffer), then the filter over the session's device film and moments into film_out (res_x*res_y, host).  The
- * session's film and moments are not modified. */
+/* Inside an adaptive session: the features of indices [0, feature_samples) at chain_depth (rendered once per session
+ * into a device buffer, again when either changes), then the filter over the session's device film and moments into
+ * film_out (res_x*res_y, host).  The session's film and moments are not modified. */
 int rt_adaptive_denoise(rt_ctx* ctx, const rt_denoise_desc* desc, rt_pixel* film_out);
 
 /* ---- temporal accumulation ------------------------------------------------------- */
@@ -349,6 +349,24 @@ typedef struct { float x, y, z, hits; } rt_position;      /* 16 B, sums over the
 /* rt_render_features that also accumulates (+=) the position film pos_inout (res_x*res_y, host memory) of the same
  * first hits; feat_inout comes out exactly as rt_render_features leaves it. */
 int rt_render_features_pos(rt_ctx* ctx, int index_begin, int index_end, rt_feature* feat_inout, rt_position* pos_inout);
+/* Specular-chain guides: rt_render_features_pos (pos_inout may be NULL: the feature film alone) whose
+ * samples follow perfect mirrors and smooth dielectrics for up to chain_depth continuation rays (0..RT_CHAIN_MAX, else
+ * RT_E_ARG) and describe the end of that chain.  Per sample, float32, nothing fused:
+ *   the camera ray (o0, d0) is traced as in rt_render_features (a miss adds nothing); D = t0;
+ *   at each hit the path integrator's surface: stop on an emitter (checked first), on a diffuse material, or after
+ *   chain_depth continuations; otherwise the ray the integrator would spawn, offset 1e-4 (1 + max |p|) along the
+ *   shading-side normal n: the reflection off a mirror (n is appended to a list N), through a dielectric the
+ *   refraction whenever it exists (eta, or glass-BK7 at 550 nm when eta is 0; no sampler draw; nothing appended) and
+ *   the reflection on total internal reflection; it is traced as a path bounce (every triangle, every analytic
+ *   shape; a miss: the sample adds nothing) and D += t;
+ *   feat += (v, D), v the last hit's normal reflected about the entries of N from last to first, and
+ *   pos += (o0 + D d0, 1): the virtual point on the camera ray, exact for planar mirrors.
+ * chain_depth 0, or the reference integrator (no materials: every chain has length 0), gives rt_render_features_pos'
+ * films bit for bit.  Batches, shards, sessions, rt_stats (continuation rays count as rays) and RT_E_STATE on
+ * multi-device contexts as rt_render_features. */
+#define RT_CHAIN_MAX 4
+int rt_render_features_chain(rt_ctx* ctx, int index_begin, int index_end, int chain_depth, rt_feature* feat_inout,
+                             rt_position* pos_inout);
 /* Reprojection of the previous frame's accumulated film and moments through the previous camera, rejection of taps
  * whose geometry disagrees, and a sample-count-weighted running mean; float32 in a fixed operation order. */
 typedef struct {
@@ -356,7 +374,8 @@ typedef struct {
     float plane_rel;        /* >= 0, finite: and |n_p.(P_q - P)| <= plane_rel * depth                        */
     float max_history;      /* >= 1: cap of the accumulated sample count n'                                  */
     int feature_samples;    /* k >= 1: indices accumulated in the feature and position films                 */
-    int reserved[4];
+    int chain_depth;        /* 0..RT_CHAIN_MAX: the frames render their guides with rt_render_features_chain */
+    int reserved[3];
 } rt_temporal_desc;         /* 32 B */
 typedef struct {
     int frames;             /* frames behind the history that was used (0: none, the outputs are the inputs)  */
@@ -382,8 +401,8 @@ int rt_temporal_accumulate(rt_ctx* ctx, const rt_temporal_desc* desc, int res_x,
 int rt_temporal_begin(rt_ctx* ctx, const rt_temporal_desc* desc);
 /* One frame of the current camera: an internal adaptive session by `adaptive` (uniform: min_samples == max_samples),
  * the features and positions of indices [0, feature_samples), the accumulation against the history, the a-trous filter
- * with the frame's features when `denoise` is not NULL (its feature_samples must equal the session's), the result
- * copied to film_out (res_x*res_y, host).  The unfiltered accumulation, the features, the positions and
+ * with the frame's features when `denoise` is not NULL (its feature_samples and chain_depth must equal the session's),
+ * the result copied to film_out (res_x*res_y, host).  The unfiltered accumulation, the features, the positions and
  * world_to_film (this frame's camera) become the next frame's history.  info may be NULL.  Blocks. */
 int rt_temporal_frame(rt_ctx* ctx, const rt_adaptive_desc* adaptive, const rt_denoise_desc* denoise,
                       const float* world_to_film, rt_pixel* film_out, rt_temporal_info* info);
