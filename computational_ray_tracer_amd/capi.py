@@ -174,6 +174,7 @@ EXPORTS = [
     "rt_render_features_pos", "rt_temporal_accumulate", "rt_temporal_begin", "rt_temporal_frame", "rt_temporal_reset",
     "rt_temporal_end",
     "rt_render_features_chain",
+    "rt_temporal_frame_guided", "rt_temporal_block_error",
 ]
 
 _lib = None
@@ -264,6 +265,11 @@ def load_library(path=None):
         "rt_temporal_begin": ([C.c_void_p, P(rt_temporal_desc)], C.c_int),
         "rt_temporal_frame": ([C.c_void_p, P(rt_adaptive_desc), P(rt_denoise_desc), P(C.c_float), P(rt_pixel),
                                P(rt_temporal_info)], C.c_int),
+        "rt_temporal_frame_guided": ([C.c_void_p, P(rt_adaptive_desc), P(rt_denoise_desc), P(C.c_float), P(rt_pixel),
+                                      P(rt_temporal_info), P(rt_adaptive_info)], C.c_int),
+        "rt_temporal_block_error": ([C.c_void_p, P(rt_temporal_desc), P(rt_adaptive_desc), C.c_int, C.c_int, P(rt_pixel),
+                                     P(rt_moment), P(rt_feature), P(rt_position), P(rt_pixel), P(rt_moment),
+                                     P(rt_feature), P(rt_position), P(C.c_float), P(C.c_float), P(C.c_int32)], C.c_int),
         "rt_temporal_reset": ([C.c_void_p], C.c_int),
         "rt_temporal_end": ([C.c_void_p], C.c_int),
     }

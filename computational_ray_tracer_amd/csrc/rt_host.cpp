@@ -666,6 +666,14 @@ struct rt_ctx {
         DevBuf<float4> feat;         // rt_adaptive_denoise: the feature film of indices [0, feat_k), 0: not rendered,
         int feat_k = 0;              // through the chain pass of depth feat_chain
         int feat_chain = 0;
+        // a guided temporal frame's session (rt_temporal_frame_guided): with `on` the steps estimate the
+        // block errors with k_temporal_error, on the film blended with rec, the frame's reprojected history (the
+        // temporal session's buffer; null: there is none)
+        struct Guide {
+            bool on = false;
+            const float4* rec = nullptr;
+            float max_history = 0.f;
+        } guide;
     } ad;
     // denoiser workspace (rt_denoise, rt_adaptive_denoise): staging of the host arrays, the guides and
     // the (c, var) ping-pong; grows on demand
@@ -689,6 +697,8 @@ struct rt_ctx {
         DevBuf<float4> s_film, s_feat, s_pos, s_hfilm, s_hfeat, s_hpos, s_out;
         DevBuf<float2> s_mom, s_hmom, s_outm;
         DevBuf<unsigned long long> ctr;
+        DevBuf<float4> rec;          // guided frames: the reprojected history, (nh, m1h, m2h, 0) per pixel;
+                                     // also rt_temporal_block_error's
     } tp;
     // what render_device_body renders: the full work list, or (inside rt_adaptive_step) the session's active list
     // with its moment film
@@ -2402,14 +2412,17 @@ int adaptive_reserve(rt_ctx* c) {
     return RT_OK;
 }
 
-// block errors and flags from (film, mom), then in[0, n) compacted into out; blocks until the counts are read
+// block errors and flags from (film, mom), by the plain estimate or the guided one, then in[0, n)
+// compacted into out; blocks until the counts are read
 int adaptive_select(rt_ctx* c, const float4* film, const float2* mom, const rt_adaptive_desc& d, const int* in, int n,
-                    int* out, int* n_out, int* n_blocks, hipStream_t st) {
+                    int* out, int* n_out, int* n_blocks, hipStream_t st,
+                    const rt_ctx::Adaptive::Guide& guide = rt_ctx::Adaptive::Guide{}) {
     rt_ctx::Adaptive& a = c->ad;
     const AdaptiveIO io{c->film.res_x, c->film.res_y, film, mom, d.rel_error, d.abs_floor, a.block_error.get(),
                         a.converged.get(), a.totals.get()};
     int t[2] = {0, 0};
-    HIPCHK(c, launch_adaptive_error(st, io));
+    if (guide.on) HIPCHK(c, launch_temporal_error(st, io, guide.rec, guide.max_history));
+    else HIPCHK(c, launch_adaptive_error(st, io));
     HIPCHK(c, launch_adaptive_compact(st, io, in, n, out, a.wave_count.get(), a.wave_offset.get()));
     HIPCHK(c, hipMemcpyAsync(t, a.totals.get(), sizeof(t), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -2481,9 +2494,9 @@ static int impl_rt_adaptive_step(rt_ctx* c, rt_adaptive_info* info) {
         c->pass_n = 0;
         c->pass_mom = nullptr;
         int n_out = 0, n_blocks = 0;
-        if (!rc)
+        if (!rc)  // (the estimate is all a guided frame's step does differently)
             rc = adaptive_select(c, a.film.get(), a.mom.get(), a.desc, a.active[a.cur].get(), n,
-                                 a.active[a.cur ^ 1].get(), &n_out, &n_blocks, st);
+                                 a.active[a.cur ^ 1].get(), &n_out, &n_blocks, st, a.guide);
         const int rc2 = mark_done(c, st);
         if (rc || rc2) return rc ? rc : rc2;
         a.cur ^= 1;
@@ -2852,6 +2865,19 @@ int temporal_check_desc(rt_ctx* c, const rt_temporal_desc* d) {
     return RT_OK;
 }
 
+// the guides, the history and the descriptor's parameters of a kernel launch (hfilm null: no history, M not read)
+TemporalIO temporal_io(const rt_temporal_desc& d, int res_x, int res_y, const float4* feat, const float4* pos,
+                       const float4* hfilm, const float2* hmom, const float4* hfeat, const float4* hpos, const float* M) {
+    TemporalIO io{};
+    io.res_x = res_x; io.res_y = res_y;
+    io.feat = feat; io.pos = pos;
+    io.hfilm = hfilm; io.hmom = hmom; io.hfeat = hfeat; io.hpos = hpos;
+    if (hfilm) std::memcpy(io.M, M, sizeof(io.M));
+    io.kf = (float)d.feature_samples;
+    io.normal_min = d.normal_min; io.plane_rel = d.plane_rel; io.max_history = d.max_history;
+    return io;
+}
+
 // The stage over device arrays of res_x * res_y (hfilm null: no history, M not read); counts[T_NCLASSES] read back
 // after the kernel (blocks until then).
 int temporal_device(rt_ctx* c, const rt_temporal_desc& d, int res_x, int res_y, const float4* film, const float2* mom,
@@ -2860,13 +2886,8 @@ int temporal_device(rt_ctx* c, const rt_temporal_desc& d, int res_x, int res_y, 
     rt_ctx::Temporal& t = c->tp;
     HIPCHK(c, t.ctr.reserve(kTemporalCtrWords));
     HIPCHK(c, hipMemsetAsync(t.ctr.get(), 0, kTemporalCtrWords * sizeof(unsigned long long), st));
-    TemporalIO io{};
-    io.res_x = res_x; io.res_y = res_y;
-    io.film = film; io.mom = mom; io.feat = feat; io.pos = pos;
-    io.hfilm = hfilm; io.hmom = hmom; io.hfeat = hfeat; io.hpos = hpos;
-    if (hfilm) std::memcpy(io.M, M, sizeof(io.M));
-    io.kf = (float)d.feature_samples;
-    io.normal_min = d.normal_min; io.plane_rel = d.plane_rel; io.max_history = d.max_history;
+    TemporalIO io = temporal_io(d, res_x, res_y, feat, pos, hfilm, hmom, hfeat, hpos, M);
+    io.film = film; io.mom = mom;
     io.out_film = out_film; io.out_mom = out_mom;
     io.ctr = t.ctr.get();
     HIPCHK(c, launch_temporal_accumulate(st, io));
@@ -2956,6 +2977,67 @@ static int impl_rt_temporal_accumulate(rt_ctx* c, const rt_temporal_desc* d, int
     return RT_OK;
 }
 
+static int impl_rt_temporal_block_error(rt_ctx* c, const rt_temporal_desc* d, const rt_adaptive_desc* ad, int res_x,
+                                        int res_y, const rt_pixel* film, const rt_moment* mom, const rt_feature* feat,
+                                        const rt_position* pos, const rt_pixel* hfilm, const rt_moment* hmom,
+                                        const rt_feature* hfeat, const rt_position* hpos, const float* M,
+                                        float* block_error, int32_t* converged) {
+    if (!c) return RT_E_ARG;
+    if (!d || !ad || !film || !mom || !feat || !pos)
+        return fail(c, RT_E_ARG, "temporal block error: both descriptors, film, moments, features and positions are required");
+    const int n_hist = (hfilm != nullptr) + (hmom != nullptr) + (hfeat != nullptr) + (hpos != nullptr);
+    if (n_hist != 0 && n_hist != 4) return fail(c, RT_E_ARG, "temporal: the history is all four arrays or none");
+    const bool hist = n_hist == 4;
+    if (hist && !M) return fail(c, RT_E_ARG, "temporal: a history needs its world-to-film matrix");
+    if (res_x <= 0 || res_y <= 0) return fail(c, RT_E_ARG, "temporal: the resolution must be positive");
+    if ((int64_t)res_x * res_y > ((int64_t)1 << 28)) return fail(c, RT_E_LIMIT, "temporal: more than 2^28 pixels");
+    int rc = temporal_check_desc(c, d);
+    if (rc) return rc;
+    if ((rc = adaptive_check_desc(c, ad, false))) return rc;
+    const size_t n = (size_t)res_x * res_y, nb = (size_t)((res_x + 7) / 8) * ((res_y + 7) / 8);
+    hipSetDevice(c->device);
+    rt_ctx::Temporal& t = c->tp;
+    DevBuf<float> d_err;
+    DevBuf<int> d_conv;
+    HIPCHK(c, d_err.reserve(nb)); HIPCHK(c, d_conv.reserve(nb));
+    HIPCHK(c, t.s_film.reserve(n)); HIPCHK(c, t.s_mom.reserve(n));
+    if (hist) {
+        HIPCHK(c, t.s_feat.reserve(n)); HIPCHK(c, t.s_pos.reserve(n)); HIPCHK(c, t.rec.reserve(n));
+        HIPCHK(c, t.s_hfilm.reserve(n)); HIPCHK(c, t.s_hmom.reserve(n));
+        HIPCHK(c, t.s_hfeat.reserve(n)); HIPCHK(c, t.s_hpos.reserve(n));
+    }
+    hipStream_t st = c->stream;
+    if ((rc = order_after_previous(c, st))) return rc;
+    HIPCHK(c, hipMemcpyAsync(t.s_film.get(), film, n * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(t.s_mom.get(), mom, n * 8, hipMemcpyHostToDevice, st));
+    if (hist) {
+        HIPCHK(c, hipMemcpyAsync(t.s_feat.get(), feat, n * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(t.s_pos.get(), pos, n * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(t.s_hfilm.get(), hfilm, n * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(t.s_hmom.get(), hmom, n * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(t.s_hfeat.get(), hfeat, n * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(t.s_hpos.get(), hpos, n * 16, hipMemcpyHostToDevice, st));
+    }
+    rc = RT_OK;
+    if (hist) {
+        const TemporalIO io = temporal_io(*d, res_x, res_y, t.s_feat.get(), t.s_pos.get(), t.s_hfilm.get(), t.s_hmom.get(),
+                                          t.s_hfeat.get(), t.s_hpos.get(), M);
+        if (launch_temporal_reproject(st, io, t.rec.get()) != hipSuccess) rc = fail(c, RT_E_HIP, "k_temporal_reproject");
+    }
+    if (!rc) {
+        const AdaptiveIO io{res_x, res_y, t.s_film.get(), t.s_mom.get(), ad->rel_error, ad->abs_floor, d_err.get(),
+                            d_conv.get(), nullptr};
+        if (launch_temporal_error(st, io, hist ? t.rec.get() : nullptr, d->max_history) != hipSuccess)
+            rc = fail(c, RT_E_HIP, "k_temporal_error");
+    }
+    const int rc2 = mark_done(c, st);
+    if (rc || rc2) return rc ? rc : rc2;
+    if (block_error) HIPCHK(c, hipMemcpyAsync(block_error, d_err.get(), nb * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (converged) HIPCHK(c, hipMemcpyAsync(converged, d_conv.get(), nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
 static int impl_rt_temporal_begin(rt_ctx* c, const rt_temporal_desc* d) {
     if (!c) return RT_E_ARG;
     if (!d) return fail(c, RT_E_ARG, "temporal: null descriptor");
@@ -2983,26 +3065,55 @@ static int impl_rt_temporal_begin(rt_ctx* c, const rt_temporal_desc* d) {
 }
 
 namespace {
-// the frame inside its adaptive session: steps, feature + position pass, the stage, the filter, the copy out
-int temporal_frame_body(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_desc* dd, rt_pixel* film_out, int* counts) {
+// the frame's guides: the feature and position films of indices [0, feature_samples) into the non-history set
+int temporal_frame_guides(rt_ctx* c, hipStream_t st) {
+    rt_ctx::Temporal& t = c->tp;
+    const int nx = t.cur ^ 1;
+    const size_t n = (size_t)c->film.res_x * c->film.res_y;
+    int rc = hipMemsetAsync(t.feat[nx].get(), 0, n * sizeof(float4), st) == hipSuccess &&
+                     hipMemsetAsync(t.pos[nx].get(), 0, n * sizeof(float4), st) == hipSuccess
+                 ? RT_OK : fail(c, RT_E_HIP, "feature and position film memset");
+    if (!rc)
+        rc = features_device(c, 0, t.desc.feature_samples, t.feat[nx].get(), st, t.pos[nx].get(), t.desc.chain_depth);
+    return rc;
+}
+
+// the frame inside its adaptive session: steps, feature + position pass, the stage, the filter, the copy out.
+// guided: the guides and the reprojection first, and the steps estimate on the accumulated film.
+int temporal_frame_body(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_desc* dd, rt_pixel* film_out, int* counts,
+                        bool guided, rt_adaptive_info* session) {
     rt_ctx::Temporal& t = c->tp;
     rt_ctx::Adaptive& a = c->ad;
     int rc;
+    const int res_x = c->film.res_x, res_y = c->film.res_y, nx = t.cur ^ 1;
+    const size_t n = (size_t)res_x * res_y;
+    const bool hist = t.frames > 0;
+    if (guided) {
+        if (hist) HIPCHK(c, t.rec.reserve(n));
+        hipStream_t st = c->stream;
+        if ((rc = order_after_previous(c, st))) return rc;
+        rc = temporal_frame_guides(c, st);
+        if (!rc && hist) {
+            const TemporalIO io = temporal_io(t.desc, res_x, res_y, t.feat[nx].get(), t.pos[nx].get(), t.film[t.cur].get(),
+                                              t.mom[t.cur].get(), t.feat[t.cur].get(), t.pos[t.cur].get(), t.M);
+            rc = launch_temporal_reproject(st, io, t.rec.get()) == hipSuccess ? RT_OK
+                                                                             : fail(c, RT_E_HIP, "k_temporal_reproject");
+        }
+        const int rc2 = mark_done(c, st);
+        if (rc || rc2) return rc ? rc : rc2;
+        a.guide.on = true;
+        a.guide.rec = hist ? t.rec.get() : nullptr;
+        a.guide.max_history = t.desc.max_history;
+    }
     rt_adaptive_info cur{};
     do {
         if ((rc = impl_rt_adaptive_step(c, &cur))) return rc;
     } while (cur.active_pixels > 0 && cur.index_done < ad->max_samples);
-    const int res_x = c->film.res_x, res_y = c->film.res_y, nx = t.cur ^ 1;
-    const size_t n = (size_t)res_x * res_y;
-    const bool hist = t.frames > 0;
+    if (session) *session = cur;
     if (dd) HIPCHK(c, c->dn.out.reserve(n));
     hipStream_t st = c->stream;
     if ((rc = order_after_previous(c, st))) return rc;
-    rc = hipMemsetAsync(t.feat[nx].get(), 0, n * sizeof(float4), st) == hipSuccess &&
-                 hipMemsetAsync(t.pos[nx].get(), 0, n * sizeof(float4), st) == hipSuccess
-             ? RT_OK : fail(c, RT_E_HIP, "feature and position film memset");
-    if (!rc)
-        rc = features_device(c, 0, t.desc.feature_samples, t.feat[nx].get(), st, t.pos[nx].get(), t.desc.chain_depth);
+    rc = guided ? RT_OK : temporal_frame_guides(c, st);
     if (!rc)
         rc = temporal_device(c, t.desc, res_x, res_y, a.film.get(), a.mom.get(), t.feat[nx].get(), t.pos[nx].get(),
                              hist ? t.film[t.cur].get() : nullptr, hist ? t.mom[t.cur].get() : nullptr,
@@ -3020,8 +3131,10 @@ int temporal_frame_body(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_
 }
 }  // namespace
 
+// rt_temporal_frame and rt_temporal_frame_guided (guided; session: its adaptive session's last info, may be null)
 static int impl_rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_desc* dd, const float* M,
-                                  rt_pixel* film_out, rt_temporal_info* info) {
+                                  rt_pixel* film_out, rt_temporal_info* info, bool guided = false,
+                                  rt_adaptive_info* session = nullptr) {
     if (!c) return RT_E_ARG;
     rt_ctx::Temporal& t = c->tp;
     if (!t.live) return fail(c, RT_E_STATE, "no temporal session is open (rt_temporal_begin first)");
@@ -3044,11 +3157,13 @@ static int impl_rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* ad, const r
     t.in_frame = false;
     if (rc) return rc;
     int counts[T_NCLASSES] = {};
-    rc = temporal_frame_body(c, ad, dd, film_out, counts);
+    rt_adaptive_info cur{};
+    rc = temporal_frame_body(c, ad, dd, film_out, counts, guided, &cur);
     const std::string msg = c->err;
     impl_rt_adaptive_end(c);
     if (rc) return fail(c, rc, msg);  // the history is as it was: the failed frame is not part of it
     temporal_fill_info(info, t.frames, counts);
+    if (session) *session = cur;
     t.cur ^= 1;
     t.frames += 1;
     std::memcpy(t.M, M, sizeof(t.M));
@@ -3547,6 +3662,25 @@ int rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* adaptive, const rt_deno
                       rt_pixel* film_out, rt_temporal_info* info) {
     return guarded([&] { return impl_rt_temporal_frame(c, adaptive, denoise, world_to_film, film_out, info); },
                    [&](const std::string& m) { set_error(c, m); });
+}
+int rt_temporal_frame_guided(rt_ctx* c, const rt_adaptive_desc* adaptive, const rt_denoise_desc* denoise,
+                             const float* world_to_film, rt_pixel* film_out, rt_temporal_info* info,
+                             rt_adaptive_info* session_info) {
+    return guarded(
+        [&] { return impl_rt_temporal_frame(c, adaptive, denoise, world_to_film, film_out, info, true, session_info); },
+        [&](const std::string& m) { set_error(c, m); });
+}
+int rt_temporal_block_error(rt_ctx* c, const rt_temporal_desc* d, const rt_adaptive_desc* adaptive, int res_x, int res_y,
+                            const rt_pixel* film, const rt_moment* mom, const rt_feature* feat, const rt_position* pos,
+                            const rt_pixel* hist_film, const rt_moment* hist_mom, const rt_feature* hist_feat,
+                            const rt_position* hist_pos, const float* world_to_film_prev, float* block_error,
+                            int32_t* converged) {
+    return guarded(
+        [&] {
+            return impl_rt_temporal_block_error(c, d, adaptive, res_x, res_y, film, mom, feat, pos, hist_film, hist_mom,
+                                                hist_feat, hist_pos, world_to_film_prev, block_error, converged);
+        },
+        [&](const std::string& m) { set_error(c, m); });
 }
 int rt_temporal_reset(rt_ctx* c) {
     return guarded([&] { return impl_rt_temporal_reset(c); }, [&](const std::string& m) { set_error(c, m); });

@@ -613,5 +613,11 @@ struct TemporalIO {
     unsigned long long* ctr;      // kTemporalCtrWords: the class counts, spread as the kernels' counter slots (ctr_word)
 };
 hipError_t launch_temporal_accumulate(hipStream_t st, const TemporalIO& io);
+// The guided estimate.  reproject: rec[p] = (nh, m1h, m2h, 0) from io's guides, history and M (film,
+// mom, out_* and ctr are not used), zeros where the pixel has no history.  error: every 8x8 block's E and converged
+// flag (io.totals is not used) of the film and moments blended with rec (null: no history), bit for bit what
+// k_adaptive_error gives on k_temporal_accumulate's outputs.
+hipError_t launch_temporal_reproject(hipStream_t st, const TemporalIO& io, float4* rec);
+hipError_t launch_temporal_error(hipStream_t st, const AdaptiveIO& io, const float4* rec, float max_history);
 
 }  // namespace rtmi

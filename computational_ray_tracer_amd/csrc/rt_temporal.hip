@@ -6,6 +6,10 @@
 //                          tested (sample count, hit count, normal, plane distance) and the survivors' means are
 //                          blended with the current mean, alpha = n / n', n' = min(history + n, max_history).
 //                          out = (mean n', n') and (m1 n', m2 n'): an ordinary film and moment film.
+//   k_temporal_reproject   the guided estimate, once per frame: the same fetch, kept as a 16-B record
+//                          (history count, per-sample moments) per pixel
+//   k_temporal_error       once per iteration of a guided frame's session: the blend of the moments with the record and
+//                          k_adaptive_error's block estimate on the result, one wave64 per 8x8 block
 //
 // Everything is float32 in the order written (the build's -ffp-contract=off; / is correctly rounded) with only
 // + - * /, floorf, fmaxf, fminf and fabsf, so a numpy float32 restatement gives the same bits
@@ -118,7 +122,83 @@ __global__ void __launch_bounds__(kBlock) k_temporal_accumulate(TemporalIO io) {
     }
 }
 
+// The guided estimate, first half: steps 2-6 of the stage for every pixel with a first hit, whatever
+// the film holds.  rec = (nh, m1h, m2h, 0), the history's sample count and per-sample moments at the pixel; all 0
+// where there is none (nh > 0 wherever there is one: every tap that counts has w ns > 0 or adds 0).
+__global__ void __launch_bounds__(kBlock) k_temporal_reproject(TemporalIO io, float4* __restrict__ rec) {
+    const int x = (int)blockIdx.x * kTX + (int)(threadIdx.x % kTX), y = (int)blockIdx.y * kTY + (int)(threadIdx.x / kTX);
+    if (x >= io.res_x || y >= io.res_y) return;
+    const int p = y * io.res_x + x;
+    float4 R = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 Q = io.pos[p];
+    if (Q.w != 0.f) {
+        const float4 G = io.feat[p];
+        const V3 P = v3(Q.x / Q.w, Q.y / Q.w, Q.z / Q.w);
+        const V3 n_p = v3(G.x / io.kf, G.y / io.kf, G.z / io.kf);
+        float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, s1 = 0.f, s2 = 0.f, sn = 0.f;
+        if (fetch_history(io, P, n_p, G.w / io.kf, sw, sr, sg, sb, s1, s2, sn)) R = make_float4(sn / sw, s1 / sw, s2 / sw, 0.f);
+    }
+    rec[p] = R;
+}
+
+// Second half, once per iteration: one wave64 per image-aligned 8x8 block with k_adaptive_error's lane mapping.  Step 7
+// of the stage on the moments alone, then k_adaptive_error's arithmetic on the result: the bits of k_temporal_accumulate
+// followed by k_adaptive_error.  rec null: no history.
+__global__ void __launch_bounds__(kBlock) k_temporal_error(AdaptiveIO io, const float4* __restrict__ rec,
+                                                           float max_history, int nbx, int nblocks) {
+    const int b = (int)blockIdx.x * (kBlock / 64) + (int)(threadIdx.x >> 6);  // wave-uniform
+    if (b >= nblocks) return;
+    const int by = b / nbx, bx = b - by * nbx;
+    const int l = (int)(threadIdx.x & 63u);
+    const int x = bx * 8 + (l & 7), y = by * 8 + (l >> 3);
+    float sem = 0.f, mean = 0.f;
+    if (x < io.res_x && y < io.res_y) {
+        const int p = y * io.res_x + x;
+        const float n = reinterpret_cast<const float*>(io.film)[4 * (size_t)p + 3];
+        if (n != 0.f) {
+            const float2 Mo = io.mom[p];
+            float n2 = n, s = Mo.x, q = Mo.y;
+            const float4 R = rec ? rec[p] : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (R.x != 0.f) {
+                n2 = fmaxf(fminf(R.x + n, max_history), n);
+                const float al = n / n2, be = 1.f - al;
+                s = (be * R.y + al * (Mo.x / n)) * n2;
+                q = (be * R.z + al * (Mo.y / n)) * n2;
+            }
+            if (n2 >= 2.f) {
+                mean = s / n2;
+                const float d = fmaxf(q - s * mean, 0.f);
+                sem = sqrtf((d / (n2 - 1.f)) / n2);
+            }
+        }
+    }
+    float S = sem, M = mean;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        S += __shfl_xor(S, o);
+        M += __shfl_xor(M, o);
+    }
+    if (l == 0) {
+        const float E = S / (M + io.abs_floor);
+        io.block_error[b] = E;
+        io.converged[b] = E <= io.rel_error ? 1 : 0;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_temporal_reproject(hipStream_t st, const TemporalIO& io, float4* rec) {
+    const dim3 grid((io.res_x + kTX - 1) / kTX, (io.res_y + kTY - 1) / kTY);
+    hipLaunchKernelGGL(k_temporal_reproject, grid, dim3(kBlock), 0, st, io, rec);
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal_error(hipStream_t st, const AdaptiveIO& io, const float4* rec, float max_history) {
+    const int nbx = (io.res_x + 7) / 8, nblocks = nbx * ((io.res_y + 7) / 8), waves = kBlock / 64;
+    hipLaunchKernelGGL(k_temporal_error, dim3((nblocks + waves - 1) / waves), dim3(kBlock), 0, st, io, rec, max_history,
+                       nbx, nblocks);
+    return hipGetLastError();
+}
 
 hipError_t launch_temporal_accumulate(hipStream_t st, const TemporalIO& io) {
     const dim3 grid((io.res_x + kTX - 1) / kTX, (io.res_y + kTY - 1) / kTY);

@@ -288,20 +288,52 @@ class Renderer:
         self._chk("rt_temporal_begin", self.lib.rt_temporal_begin(self.h, C.byref(self._temporal_desc(**desc))))
 
     def temporal_frame(self, world_to_film, min_samples, step_samples=1, max_samples=None, rel_error=0.0,
-                       abs_floor=1e-3, denoise=None):
+                       abs_floor=1e-3, denoise=None, guided=False):
         """rt_temporal_frame of the current camera, whose matrix is world_to_film (scene.world_to_film): an adaptive
         frame (max_samples None: uniform, min_samples everywhere), accumulated against the session's history and,
         with denoise = a dict of rt_denoise_desc fields (may be empty: DENOISE_DEFAULTS), filtered.  Returns (film,
-        info dict)."""
+        info dict).  guided=True: rt_temporal_frame_guided, whose adaptive session estimates its block errors on the
+        accumulated film; info["session"] is that session's rt_adaptive_info as a dict."""
         ad = self._adaptive_desc(min_samples, step_samples, min_samples if max_samples is None else max_samples,
                                  rel_error, abs_floor)
         dd = None if denoise is None else self._denoise_desc(**denoise)
         m = self._matrix16(world_to_film)
         out, info = self.new_film(), capi.rt_temporal_info()
-        self._chk("rt_temporal_frame", self.lib.rt_temporal_frame(
-            self.h, C.byref(ad), None if dd is None else C.byref(dd), m.ctypes.data_as(C.POINTER(C.c_float)),
-            out.ctypes.data_as(C.POINTER(capi.rt_pixel)), C.byref(info)))
-        return out, self._adaptive_info(info)
+        args = (self.h, C.byref(ad), None if dd is None else C.byref(dd), m.ctypes.data_as(C.POINTER(C.c_float)),
+                out.ctypes.data_as(C.POINTER(capi.rt_pixel)), C.byref(info))
+        if not guided:
+            self._chk("rt_temporal_frame", self.lib.rt_temporal_frame(*args))
+            return out, self._adaptive_info(info)
+        session = capi.rt_adaptive_info()
+        self._chk("rt_temporal_frame_guided", self.lib.rt_temporal_frame_guided(*args, C.byref(session)))
+        return out, dict(self._adaptive_info(info), session=self._adaptive_info(session))
+
+    def temporal_block_error(self, film, mom, feat, pos, history=None, world_to_film_prev=None, res=None,
+                             rel_error=0.0, abs_floor=1e-3, **desc):
+        """rt_temporal_block_error on host arrays of `res` (default: the film's): the block errors a guided frame's
+        session estimates, k_adaptive_error of what temporal_accumulate gives for the same arguments.  Returns
+        (block_error [rows, columns], converged [rows, columns] int32)."""
+        W, H = res or self.res
+        n = W * H
+        cur = [np.ascontiguousarray(a, np.float32) for a in (film, mom, feat, pos)]
+        assert [a.shape for a in cur] == [(n, 4), (n, 2), (n, 4), (n, 4)]
+        types = [capi.rt_pixel, capi.rt_moment, capi.rt_feature, capi.rt_position]
+        args = [a.ctypes.data_as(C.POINTER(t)) for a, t in zip(cur, types)]
+        if history is None:
+            hist, args, m = [], args + [None] * 4, None
+        else:
+            hist = [np.ascontiguousarray(a, np.float32) for a in history]
+            assert [a.shape for a in hist] == [(n, 4), (n, 2), (n, 4), (n, 4)]
+            args += [a.ctypes.data_as(C.POINTER(t)) for a, t in zip(hist, types)]
+            m = self._matrix16(world_to_film_prev)
+        d = self._temporal_desc(**desc)
+        ad = self._adaptive_desc(rel_error=rel_error, abs_floor=abs_floor)
+        bx, by = (W + 7) // 8, (H + 7) // 8
+        err, conv = np.zeros((by, bx), np.float32), np.zeros((by, bx), np.int32)
+        self._chk("rt_temporal_block_error", self.lib.rt_temporal_block_error(
+            self.h, C.byref(d), C.byref(ad), W, H, *args, None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
+            err.ctypes.data_as(C.POINTER(C.c_float)), conv.ctypes.data_as(C.POINTER(C.c_int32))))
+        return err, conv
 
     def temporal_reset(self):
         """Drop the session's history: the next frame is a first frame."""

@@ -406,6 +406,19 @@ int rt_temporal_begin(rt_ctx* ctx, const rt_temporal_desc* desc);
  * world_to_film (this frame's camera) become the next frame's history.  info may be NULL.  Blocks. */
 int rt_temporal_frame(rt_ctx* ctx, const rt_adaptive_desc* adaptive, const rt_denoise_desc* denoise,
                       const float* world_to_film, rt_pixel* film_out, rt_temporal_info* info);
+/* rt_temporal_frame whose adaptive session estimates its block errors on the accumulated film.
+ * session_info (may be NULL): the frame's internal adaptive session as rt_adaptive_step last reported it. */
+int rt_temporal_frame_guided(rt_ctx* ctx, const rt_adaptive_desc* adaptive, const rt_denoise_desc* denoise,
+                             const float* world_to_film, rt_pixel* film_out, rt_temporal_info* info,
+                             rt_adaptive_info* session_info);
+/* The guided estimate alone on host arrays of any res_x x res_y: k_temporal_reproject + k_temporal_error.  Inputs as
+ * rt_temporal_accumulate (all four hist_* NULL: no history); only rel_error and abs_floor of `adaptive` are read.
+ * block_error, converged: ceil(res_x/8)*ceil(res_y/8) each, row-major blocks; either may be NULL. */
+int rt_temporal_block_error(rt_ctx* ctx, const rt_temporal_desc* desc, const rt_adaptive_desc* adaptive, int res_x,
+                            int res_y, const rt_pixel* film, const rt_moment* mom, const rt_feature* feat,
+                            const rt_position* pos, const rt_pixel* hist_film, const rt_moment* hist_mom,
+                            const rt_feature* hist_feat, const rt_position* hist_pos, const float* world_to_film_prev,
+                            float* block_error, int32_t* converged);
 /* Drop the history (a cut, or a change of the scene): the next frame is a first frame. */
 int rt_temporal_reset(rt_ctx* ctx);
 int rt_temporal_end(rt_ctx* ctx);
