@@ -1,6 +1,9 @@
 """CPU: known answers for the oracle's analytic shapes (Shapes.h:209-907), Fresnel/refraction, BK7 dispersion and
 the MIS weights of the build-defined path integrator.  These pin oracle/rtcore.hpp; the GPU
-kernels are then compared bit-for-bit against it (tests/test_gpu_parity.py)."""
+kernels are then compared bit-for-bit against it (tests/test_gpu_parity.py).  These are a dozen hand-picked rays; the
+shapes under rotation and non-uniform scale, silhouette rays and the scene's closest hit and occlusion are held to an
+independent float64 brute force in tests/test_geometry_reference.py (tests/geometry_reference.py), the kernels in
+tests/test_gpu_geometry.py."""
 import ctypes as C
 import math
 
