@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <queue>
 #include <string>
@@ -687,7 +688,6 @@ struct rt_ctx {
     // camera's world-to-film matrix); the staging of rt_temporal_accumulate's host arrays; the class counters
     struct Temporal {
         bool live = false;
-        bool in_frame = false;       // rt_temporal_frame is running its own adaptive session
         rt_temporal_desc desc{};
         int frames = 0;              // frames behind set `cur` (0: no history)
         int cur = 0;
@@ -700,11 +700,6 @@ struct rt_ctx {
         DevBuf<float4> rec;          // guided frames: the reprojected history, (nh, m1h, m2h, 0) per pixel;
                                      // also rt_temporal_block_error's
     } tp;
-    // what render_device_body renders: the full work list, or (inside rt_adaptive_step) the session's active list
-    // with its moment film
-    const int* pass_work = nullptr;
-    int pass_n = 0;
-    float2* pass_mom = nullptr;
 };
 
 namespace {
@@ -1123,28 +1118,59 @@ int mark_done(rt_ctx* c, hipStream_t st) {
     return RT_OK;
 }
 
-int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st);
-// one render pass over [ib, ie) into the device film
-int render_device(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) {
-    int rc = check_ready(c);
+// The bracket of a call that queues work on st: wait for the previous call, run body (a callable returning a status),
+// record `done` whatever body returned; the status is body's, or the record's when body succeeded.
+template <class Body>
+int ordered(rt_ctx* c, hipStream_t st, Body body) {
+    int rc = order_after_previous(c, st);
     if (rc) return rc;
-    if ((rc = order_after_previous(c, st))) return rc;
-    rc = render_device_body(c, ib, ie, film, st);
-    int rc2 = mark_done(c, st);
+    rc = body();
+    const int rc2 = mark_done(c, st);
     return rc ? rc : rc2;
 }
 
-int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) {
+// A caller's host array of n elements into a staging buffer (grow-only: a larger earlier call's block is reused), and a
+// buffer's first n elements out to a host array; both asynchronous on st.
+template <class T>
+int stage_in(rt_ctx* c, DevBuf<T>& buf, const void* host, size_t n, hipStream_t st) {
+    HIPCHK(c, buf.reserve(n));
+    HIPCHK(c, hipMemcpyAsync(buf.get(), host, n * sizeof(T), hipMemcpyHostToDevice, st));
+    return RT_OK;
+}
+template <class T>
+int stage_out(rt_ctx* c, void* host, const DevBuf<T>& buf, size_t n, hipStream_t st) {
+    HIPCHK(c, hipMemcpyAsync(host, buf.get(), n * sizeof(T), hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+
+// the pixels a pass renders and their order: the full work list, or an adaptive session's active list with the
+// session's moment film (mom null: no moments)
+struct PassTarget {
+    const int* work;
+    int n;
+    float2* mom;
+};
+
+int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, const PassTarget& pass);
+// one render pass over [ib, ie) of the full work list into the device film
+int render_device(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    return ordered(c, st, [&]() -> int {
+        if (int rc = build_work(c)) return rc;  // (may reallocate d_work: the target is formed after it)
+        return render_device_body(c, ib, ie, film, st, PassTarget{c->d_work.get(), c->n_work, nullptr});
+    });
+}
+
+int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, const PassTarget& pass) {
     int rc;
     if (ib < 0 || ie < ib) return fail(c, RT_E_ARG, "invalid index range");
     if ((rc = ensure_sobol(c))) return rc;
     DevSampler smp = dev_sampler(c);
     if (c->smp.kind == RT_SAMPLER_STRATIFIED && !c->smp.jitter && ie > smp.spp)
         return fail(c, RT_E_ARG, "StratifiedSampler without jitter supports indices < SamplesPerPixel (samplers.h:83-87)");
-    if ((rc = build_work(c))) return rc;
-    // the pixels of this pass and their order: the full work list, or an adaptive session's active list
-    const int* const work = c->pass_work ? c->pass_work : c->d_work.get();
-    const int n_work = c->pass_work ? c->pass_n : c->n_work;
+    const int* const work = pass.work;
+    const int n_work = pass.n;
     if (ie == ib || n_work == 0) return RT_OK;
     bool path = c->integ.kind == RT_INTEGRATOR_PATH || c->integ.kind == RT_INTEGRATOR_PATH_MIS;
     c->dsc.mis = c->integ.kind == RT_INTEGRATOR_PATH_MIS;
@@ -1180,7 +1206,7 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
             ev_mark(c, st, ST_TRACE, e0);
             r.sio.work_pixels = work; r.sio.n_pixels = n_work; r.sio.n_index = nIdx;
             r.sio.film = film;
-            r.sio.mom = c->pass_mom;
+            r.sio.mom = pass.mom;
             e0 = ev_start(c, st);
             HIPCHK(c, launch_ref_shade_film(st, 0, c->dsc, d_spec, fd, r.sio, d_ctr));
             ev_mark(c, st, ST_FILM, e0);
@@ -1429,7 +1455,7 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) 
             if (last_film >= 0 && last_film != l) HIPCHK(c, hipStreamWaitEvent(s, c->ws[last_film].film_done, 0));
             PathFilmIO fio{work, n_work, nIdx[l], rv, b.pdfA.get(), b.pdfB.get(), film};
             fio.lean = lean;
-            fio.mom = c->pass_mom;
+            fio.mom = pass.mom;
             hipEvent_t e0 = ev_start(c, s);
             HIPCHK(c, launch_path_film(s, 0, d_spec, fd, fio, d_ctr));
             ev_mark(c, s, ST_FILM, e0);
@@ -2372,10 +2398,9 @@ static int impl_rt_render_pass(rt_ctx* c, int ib, int ie, rt_pixel* film) {
     if (rc) return rc;
     hipSetDevice(c->device);
     size_t n = (size_t)c->film.res_x * c->film.res_y;
-    HIPCHK(c, c->d_film.reserve(n));
-    HIPCHK(c, hipMemcpyAsync(c->d_film.get(), film, n * 16, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage_in(c, c->d_film, film, n, c->stream))) return rc;
     if ((rc = render_multi(c, ib, ie, c->d_film.get(), c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(film, c->d_film.get(), n * 16, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stage_out(c, film, c->d_film, n, c->stream))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RT_OK;
 }
@@ -2436,7 +2461,9 @@ void adaptive_release(rt_ctx* c) {
 }
 }  // namespace
 
-static int impl_rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d) {
+// frame_owned: the session is the one a temporal frame runs (rt_temporal_frame), which alone may open one while a
+// temporal session is live; the public rt_adaptive_begin passes false
+static int impl_rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d, bool frame_owned) {
     if (!c) return RT_E_ARG;
     if (!d) return fail(c, RT_E_ARG, "adaptive: null descriptor");
     int rc = check_ready(c);
@@ -2444,7 +2471,7 @@ static int impl_rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d) {
     if (!c->peers.empty()) return fail(c, RT_E_STATE, "adaptive sampling supports one-device contexts only");
     rt_ctx::Adaptive& a = c->ad;
     if (a.live) return fail(c, RT_E_STATE, "an adaptive session is already open (rt_adaptive_end first)");
-    if (c->tp.live && !c->tp.in_frame)
+    if (c->tp.live && !frame_owned)
         return fail(c, RT_E_STATE, "a temporal session is open: its frames own the adaptive session (rt_temporal_end first)");
     if ((rc = adaptive_check_desc(c, d, true))) return rc;
     hipSetDevice(c->device);
@@ -2454,14 +2481,16 @@ static int impl_rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d) {
     HIPCHK(c, a.film.reserve(n));
     HIPCHK(c, a.mom.reserve(n));
     hipStream_t st = c->stream;
-    if ((rc = order_after_previous(c, st))) return rc;
-    HIPCHK(c, hipMemsetAsync(a.film.get(), 0, n * sizeof(float4), st));
-    HIPCHK(c, hipMemsetAsync(a.mom.get(), 0, n * sizeof(float2), st));
-    HIPCHK(c, hipMemsetAsync(a.block_error.get(), 0, (size_t)adaptive_blocks(c) * sizeof(float), st));
-    if (c->n_work)
-        HIPCHK(c, hipMemcpyAsync(a.active[0].get(), c->d_work.get(), (size_t)c->n_work * sizeof(int),
-                                 hipMemcpyDeviceToDevice, st));
-    if ((rc = mark_done(c, st))) return rc;
+    rc = ordered(c, st, [&]() -> int {
+        HIPCHK(c, hipMemsetAsync(a.film.get(), 0, n * sizeof(float4), st));
+        HIPCHK(c, hipMemsetAsync(a.mom.get(), 0, n * sizeof(float2), st));
+        HIPCHK(c, hipMemsetAsync(a.block_error.get(), 0, (size_t)adaptive_blocks(c) * sizeof(float), st));
+        if (c->n_work)
+            HIPCHK(c, hipMemcpyAsync(a.active[0].get(), c->d_work.get(), (size_t)c->n_work * sizeof(int),
+                                     hipMemcpyDeviceToDevice, st));
+        return RT_OK;
+    });
+    if (rc) return rc;
     a.cur = 0;
     a.desc = *d;
     a.info = rt_adaptive_info{};
@@ -2485,20 +2514,15 @@ static int impl_rt_adaptive_step(rt_ctx* c, rt_adaptive_info* info) {
         const int ie = ib + std::min(k, a.desc.max_samples - ib);
         const int n = a.info.active_pixels;
         hipStream_t st = c->stream;
-        if ((rc = order_after_previous(c, st))) return rc;
-        c->pass_work = a.active[a.cur].get();
-        c->pass_n = n;
-        c->pass_mom = a.mom.get();
-        rc = render_device_body(c, ib, ie, a.film.get(), st);
-        c->pass_work = nullptr;
-        c->pass_n = 0;
-        c->pass_mom = nullptr;
         int n_out = 0, n_blocks = 0;
-        if (!rc)  // (the estimate is all a guided frame's step does differently)
-            rc = adaptive_select(c, a.film.get(), a.mom.get(), a.desc, a.active[a.cur].get(), n,
-                                 a.active[a.cur ^ 1].get(), &n_out, &n_blocks, st, a.guide);
-        const int rc2 = mark_done(c, st);
-        if (rc || rc2) return rc ? rc : rc2;
+        rc = ordered(c, st, [&]() -> int {
+            const PassTarget active{a.active[a.cur].get(), n, a.mom.get()};
+            if (int rc = render_device_body(c, ib, ie, a.film.get(), st, active)) return rc;
+            // (the estimate is all a guided frame's step does differently)
+            return adaptive_select(c, a.film.get(), a.mom.get(), a.desc, active.work, n, a.active[a.cur ^ 1].get(), &n_out,
+                                   &n_blocks, st, a.guide);
+        });
+        if (rc) return rc;
         a.cur ^= 1;
         a.info.samples += (int64_t)n * (ie - ib);
         a.info.iterations += 1;
@@ -2540,7 +2564,7 @@ static int impl_rt_adaptive_end(rt_ctx* c) {
 
 static int impl_rt_render_adaptive(rt_ctx* c, const rt_adaptive_desc* d, rt_pixel* film, rt_moment* mom,
                                    rt_adaptive_info* info) {
-    int rc = impl_rt_adaptive_begin(c, d);
+    int rc = impl_rt_adaptive_begin(c, d, false);
     if (rc) return rc;
     rt_adaptive_info cur{};
     do {
@@ -2571,17 +2595,16 @@ static int impl_rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, c
     const size_t n = (size_t)c->film.res_x * c->film.res_y;
     DevBuf<float4> df;
     DevBuf<float2> dm;
-    HIPCHK(c, df.reserve(n));
-    HIPCHK(c, dm.reserve(n));
-    HIPCHK(c, hipMemcpy(df.get(), film, n * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dm.get(), mom, n * sizeof(float2), hipMemcpyHostToDevice));
     rt_ctx::Adaptive& a = c->ad;
     hipStream_t st = c->stream;
-    if ((rc = order_after_previous(c, st))) return rc;
     int n_out = 0, n_blocks = 0;
-    rc = adaptive_select(c, df.get(), dm.get(), *d, c->d_work.get(), c->n_work, a.active[0].get(), &n_out, &n_blocks, st);
-    const int rc2 = mark_done(c, st);
-    if (rc || rc2) return rc ? rc : rc2;
+    rc = ordered(c, st, [&]() -> int {
+        int rc;
+        if ((rc = stage_in(c, df, film, n, st)) || (rc = stage_in(c, dm, mom, n, st))) return rc;
+        return adaptive_select(c, df.get(), dm.get(), *d, c->d_work.get(), c->n_work, a.active[0].get(), &n_out, &n_blocks,
+                               st);
+    });
+    if (rc) return rc;
     if (block_error)
         HIPCHK(c, hipMemcpy(block_error, a.block_error.get(), (size_t)adaptive_blocks(c) * sizeof(float),
                             hipMemcpyDeviceToHost));
@@ -2748,11 +2771,30 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + nb && b0 < a0 + na;
 }
+
+// A call's host arrays (a null one takes no part).  overlap_kind: 1 when an output overlaps an input, else 2 when two
+// outputs overlap, else 0.
+struct HostRange {
+    const void* p;
+    size_t bytes;
+};
+int overlap_kind(std::initializer_list<HostRange> outs, std::initializer_list<HostRange> ins) {
+    const auto hit = [](const HostRange& a, const HostRange& b) {
+        return a.p && b.p && ranges_overlap(a.p, a.bytes, b.p, b.bytes);
+    };
+    for (const HostRange& o : outs)
+        for (const HostRange& i : ins)
+            if (hit(o, i)) return 1;
+    for (const HostRange* a = outs.begin(); a != outs.end(); ++a)
+        for (const HostRange* b = a + 1; b != outs.end(); ++b)
+            if (hit(*a, *b)) return 2;
+    return 0;
+}
 }  // namespace
 
 // rt_render_features (with_pos false: pos is not looked at), rt_render_features_pos and rt_render_features_chain
-static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos = nullptr,
-                                   bool with_pos = false, int chain_depth = 0) {
+static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos, bool with_pos,
+                                   int chain_depth) {
     if (!c || !feat || (with_pos && !pos)) return RT_E_ARG;
     int rc = chain_check_depth(c, chain_depth);
     if (rc) return rc;
@@ -2760,20 +2802,17 @@ static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat, 
     if (!c->peers.empty()) return fail(c, RT_E_STATE, "the feature pass supports one-device contexts only");
     hipSetDevice(c->device);
     const size_t n = (size_t)c->film.res_x * c->film.res_y;
-    if (with_pos && ranges_overlap(feat, n * sizeof(rt_feature), pos, n * sizeof(rt_position)))
+    if (overlap_kind({{feat, n * sizeof(rt_feature)}, {with_pos ? pos : nullptr, n * sizeof(rt_position)}}, {}))
         return fail(c, RT_E_ARG, "the feature film and the position film overlap");
-    HIPCHK(c, c->dn.feat.reserve(n));
-    if (with_pos) HIPCHK(c, c->tp.s_pos.reserve(n));
-    float4* const d_pos = with_pos ? c->tp.s_pos.get() : nullptr;
+    DevBuf<float4>& d_feat = c->dn.feat;  // (rt_denoise's feature staging, and the temporal entries' position staging)
+    DevBuf<float4>& d_pos = c->tp.s_pos;
     hipStream_t st = c->stream;
-    if ((rc = order_after_previous(c, st))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->dn.feat.get(), feat, n * sizeof(float4), hipMemcpyHostToDevice, st));
-    if (with_pos) HIPCHK(c, hipMemcpyAsync(d_pos, pos, n * sizeof(float4), hipMemcpyHostToDevice, st));
-    rc = features_device(c, ib, ie, c->dn.feat.get(), st, d_pos, chain_depth);
-    const int rc2 = mark_done(c, st);
-    if (rc || rc2) return rc ? rc : rc2;
-    HIPCHK(c, hipMemcpyAsync(feat, c->dn.feat.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
-    if (with_pos) HIPCHK(c, hipMemcpyAsync(pos, d_pos, n * sizeof(float4), hipMemcpyDeviceToHost, st));
+    rc = ordered(c, st, [&]() -> int {
+        int rc;
+        if ((rc = stage_in(c, d_feat, feat, n, st)) || (with_pos && (rc = stage_in(c, d_pos, pos, n, st)))) return rc;
+        return features_device(c, ib, ie, d_feat.get(), st, with_pos ? d_pos.get() : nullptr, chain_depth);
+    });
+    if (rc || (rc = stage_out(c, feat, d_feat, n, st)) || (with_pos && (rc = stage_out(c, pos, d_pos, n, st)))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -2788,28 +2827,22 @@ static int impl_rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int r
     int rc = denoise_check_desc(c, d);
     if (rc) return rc;
     const size_t n = (size_t)res_x * res_y;
-    const void* const in[3] = {film, mom, feat};
-    const size_t in_bytes[3] = {n * sizeof(rt_pixel), n * sizeof(rt_moment), n * sizeof(rt_feature)};
-    for (int i = 0; i < 3; ++i)
-        if (ranges_overlap(out, n * sizeof(rt_pixel), in[i], in_bytes[i]) ||
-            (variance_out && ranges_overlap(variance_out, n * sizeof(float), in[i], in_bytes[i])))
-            return fail(c, RT_E_ARG, "denoise: an output overlaps an input");
-    if (variance_out && ranges_overlap(variance_out, n * sizeof(float), out, n * sizeof(rt_pixel)))
-        return fail(c, RT_E_ARG, "denoise: variance_out overlaps out");
+    if (const int k = overlap_kind({{out, n * sizeof(rt_pixel)}, {variance_out, n * sizeof(float)}},
+                                   {{film, n * sizeof(rt_pixel)}, {mom, n * sizeof(rt_moment)}, {feat, n * sizeof(rt_feature)}}))
+        return fail(c, RT_E_ARG, k == 1 ? "denoise: an output overlaps an input" : "denoise: variance_out overlaps out");
     hipSetDevice(c->device);
     rt_ctx::Denoise& w = c->dn;
-    HIPCHK(c, w.film.reserve(n)); HIPCHK(c, w.mom.reserve(n)); HIPCHK(c, w.feat.reserve(n));
     HIPCHK(c, w.out.reserve(n)); HIPCHK(c, w.var.reserve(n));
     hipStream_t st = c->stream;
-    if ((rc = order_after_previous(c, st))) return rc;
-    HIPCHK(c, hipMemcpyAsync(w.film.get(), film, n * sizeof(float4), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(w.mom.get(), mom, n * sizeof(float2), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(w.feat.get(), feat, n * sizeof(float4), hipMemcpyHostToDevice, st));
-    rc = denoise_device(c, *d, res_x, res_y, w.film.get(), w.mom.get(), w.feat.get(), w.out.get(), w.var.get(), st);
-    const int rc2 = mark_done(c, st);
-    if (rc || rc2) return rc ? rc : rc2;
-    HIPCHK(c, hipMemcpyAsync(out, w.out.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
-    if (variance_out) HIPCHK(c, hipMemcpyAsync(variance_out, w.var.get(), n * sizeof(float), hipMemcpyDeviceToHost, st));
+    rc = ordered(c, st, [&]() -> int {
+        int rc;
+        if ((rc = stage_in(c, w.film, film, n, st)) || (rc = stage_in(c, w.mom, mom, n, st)) ||
+            (rc = stage_in(c, w.feat, feat, n, st)))
+            return rc;
+        return denoise_device(c, *d, res_x, res_y, w.film.get(), w.mom.get(), w.feat.get(), w.out.get(), w.var.get(), st);
+    });
+    if (rc || (rc = stage_out(c, out, w.out, n, st)) || (variance_out && (rc = stage_out(c, variance_out, w.var, n, st))))
+        return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -2829,24 +2862,20 @@ static int impl_rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixe
     HIPCHK(c, a.feat.reserve(n));
     HIPCHK(c, c->dn.out.reserve(n));
     hipStream_t st = c->stream;
-    if ((rc = order_after_previous(c, st))) return rc;
-    // once per session (again only if the caller changes k or the chain depth)
-    if (a.feat_k != d->feature_samples || a.feat_chain != d->chain_depth) {
-        a.feat_k = 0;
-        rc = hipMemsetAsync(a.feat.get(), 0, n * sizeof(float4), st) == hipSuccess ? RT_OK
-                                                                                   : fail(c, RT_E_HIP, "feature film memset");
-        if (!rc) rc = features_device(c, 0, d->feature_samples, a.feat.get(), st, nullptr, d->chain_depth);
-        if (!rc) {
+    rc = ordered(c, st, [&]() -> int {
+        // once per session (again only if the caller changes k or the chain depth)
+        if (a.feat_k != d->feature_samples || a.feat_chain != d->chain_depth) {
+            a.feat_k = 0;
+            if (hipMemsetAsync(a.feat.get(), 0, n * sizeof(float4), st) != hipSuccess)
+                return fail(c, RT_E_HIP, "feature film memset");
+            if (int rc = features_device(c, 0, d->feature_samples, a.feat.get(), st, nullptr, d->chain_depth)) return rc;
             a.feat_k = d->feature_samples;
             a.feat_chain = d->chain_depth;
         }
-    }
-    if (!rc)
-        rc = denoise_device(c, *d, c->film.res_x, c->film.res_y, a.film.get(), a.mom.get(), a.feat.get(),
-                            c->dn.out.get(), nullptr, st);
-    const int rc2 = mark_done(c, st);
-    if (rc || rc2) return rc ? rc : rc2;
-    HIPCHK(c, hipMemcpyAsync(film_out, c->dn.out.get(), n * sizeof(float4), hipMemcpyDeviceToHost, st));
+        return denoise_device(c, *d, c->film.res_x, c->film.res_y, a.film.get(), a.mom.get(), a.feat.get(),
+                              c->dn.out.get(), nullptr, st);
+    });
+    if (rc || (rc = stage_out(c, film_out, c->dn.out, n, st))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -2865,29 +2894,37 @@ int temporal_check_desc(rt_ctx* c, const rt_temporal_desc* d) {
     return RT_OK;
 }
 
-// the guides, the history and the descriptor's parameters of a kernel launch (hfilm null: no history, M not read)
-TemporalIO temporal_io(const rt_temporal_desc& d, int res_x, int res_y, const float4* feat, const float4* pos,
-                       const float4* hfilm, const float2* hmom, const float4* hfeat, const float4* hpos, const float* M) {
+// a frame's four device arrays: the current frame's, or a history's
+struct TemporalSet {
+    const float4* film;
+    const float2* mom;
+    const float4 *feat, *pos;
+};
+
+// the guides, the history and the descriptor's parameters of a kernel launch (hist null: no history, M not read)
+TemporalIO temporal_io(const rt_temporal_desc& d, int res_x, int res_y, const TemporalSet& cur, const TemporalSet* hist,
+                       const float* M) {
     TemporalIO io{};
     io.res_x = res_x; io.res_y = res_y;
-    io.feat = feat; io.pos = pos;
-    io.hfilm = hfilm; io.hmom = hmom; io.hfeat = hfeat; io.hpos = hpos;
-    if (hfilm) std::memcpy(io.M, M, sizeof(io.M));
+    io.feat = cur.feat; io.pos = cur.pos;
+    if (hist) {
+        io.hfilm = hist->film; io.hmom = hist->mom; io.hfeat = hist->feat; io.hpos = hist->pos;
+        std::memcpy(io.M, M, sizeof(io.M));
+    }
     io.kf = (float)d.feature_samples;
     io.normal_min = d.normal_min; io.plane_rel = d.plane_rel; io.max_history = d.max_history;
     return io;
 }
 
-// The stage over device arrays of res_x * res_y (hfilm null: no history, M not read); counts[T_NCLASSES] read back
+// The stage over device arrays of res_x * res_y (hist null: no history, M not read); counts[T_NCLASSES] read back
 // after the kernel (blocks until then).
-int temporal_device(rt_ctx* c, const rt_temporal_desc& d, int res_x, int res_y, const float4* film, const float2* mom,
-                    const float4* feat, const float4* pos, const float4* hfilm, const float2* hmom, const float4* hfeat,
-                    const float4* hpos, const float* M, float4* out_film, float2* out_mom, int* counts, hipStream_t st) {
+int temporal_device(rt_ctx* c, const rt_temporal_desc& d, int res_x, int res_y, const TemporalSet& cur,
+                    const TemporalSet* hist, const float* M, float4* out_film, float2* out_mom, int* counts, hipStream_t st) {
     rt_ctx::Temporal& t = c->tp;
     HIPCHK(c, t.ctr.reserve(kTemporalCtrWords));
     HIPCHK(c, hipMemsetAsync(t.ctr.get(), 0, kTemporalCtrWords * sizeof(unsigned long long), st));
-    TemporalIO io = temporal_io(d, res_x, res_y, feat, pos, hfilm, hmom, hfeat, hpos, M);
-    io.film = film; io.mom = mom;
+    TemporalIO io = temporal_io(d, res_x, res_y, cur, hist, M);
+    io.film = cur.film; io.mom = cur.mom;
     io.out_film = out_film; io.out_mom = out_mom;
     io.ctr = t.ctr.get();
     HIPCHK(c, launch_temporal_accumulate(st, io));
@@ -2910,15 +2947,20 @@ void temporal_fill_info(rt_temporal_info* info, int frames, const int* counts) {
     info->disoccluded = counts[T_DISOCCLUDED];
     info->background = counts[T_BACKGROUND];
 }
+
+// what rt_temporal_accumulate and rt_temporal_block_error ask of their host arrays' shape: the history is all four
+// arrays or none and comes with its matrix; the resolution.  *hist: a history is given.
+int temporal_check_arrays(rt_ctx* c, const void* hfilm, const void* hmom, const void* hfeat, const void* hpos,
+                          const float* M, int res_x, int res_y, bool* hist) {
+    const int n_hist = (hfilm != nullptr) + (hmom != nullptr) + (hfeat != nullptr) + (hpos != nullptr);
+    if (n_hist != 0 && n_hist != 4) return fail(c, RT_E_ARG, "temporal: the history is all four arrays or none");
+    *hist = n_hist == 4;
+    if (*hist && !M) return fail(c, RT_E_ARG, "temporal: a history needs its world-to-film matrix");
+    if (res_x <= 0 || res_y <= 0) return fail(c, RT_E_ARG, "temporal: the resolution must be positive");
+    if ((int64_t)res_x * res_y > ((int64_t)1 << 28)) return fail(c, RT_E_LIMIT, "temporal: more than 2^28 pixels");
+    return RT_OK;
+}
 }  // namespace
-
-static int impl_rt_render_features_pos(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos) {
-    return impl_rt_render_features(c, ib, ie, feat, pos, true);
-}
-
-static int impl_rt_render_features_chain(rt_ctx* c, int ib, int ie, int chain_depth, rt_feature* feat, rt_position* pos) {
-    return impl_rt_render_features(c, ib, ie, feat, pos, pos != nullptr, chain_depth);
-}
 
 static int impl_rt_temporal_accumulate(rt_ctx* c, const rt_temporal_desc* d, int res_x, int res_y, const rt_pixel* film,
                                        const rt_moment* mom, const rt_feature* feat, const rt_position* pos,
@@ -2928,50 +2970,33 @@ static int impl_rt_temporal_accumulate(rt_ctx* c, const rt_temporal_desc* d, int
     if (!c) return RT_E_ARG;
     if (!d || !film || !mom || !feat || !pos || !out_film || !out_mom)
         return fail(c, RT_E_ARG, "temporal: descriptor, film, moments, features, positions and both outputs are required");
-    const int n_hist = (hfilm != nullptr) + (hmom != nullptr) + (hfeat != nullptr) + (hpos != nullptr);
-    if (n_hist != 0 && n_hist != 4) return fail(c, RT_E_ARG, "temporal: the history is all four arrays or none");
-    const bool hist = n_hist == 4;
-    if (hist && !M) return fail(c, RT_E_ARG, "temporal: a history needs its world-to-film matrix");
-    if (res_x <= 0 || res_y <= 0) return fail(c, RT_E_ARG, "temporal: the resolution must be positive");
-    if ((int64_t)res_x * res_y > ((int64_t)1 << 28)) return fail(c, RT_E_LIMIT, "temporal: more than 2^28 pixels");
-    int rc = temporal_check_desc(c, d);
-    if (rc) return rc;
+    bool hist;
+    int rc = temporal_check_arrays(c, hfilm, hmom, hfeat, hpos, M, res_x, res_y, &hist);
+    if (rc || (rc = temporal_check_desc(c, d))) return rc;
     const size_t n = (size_t)res_x * res_y;
-    const void* const in[8] = {film, mom, feat, pos, hfilm, hmom, hfeat, hpos};
-    const size_t in_bytes[8] = {n * 16, n * 8, n * 16, n * 16, n * 16, n * 8, n * 16, n * 16};
-    for (int i = 0; i < (hist ? 8 : 4); ++i)
-        if (ranges_overlap(out_film, n * 16, in[i], in_bytes[i]) || ranges_overlap(out_mom, n * 8, in[i], in_bytes[i]))
-            return fail(c, RT_E_ARG, "temporal: an output overlaps an input");
-    if (ranges_overlap(out_film, n * 16, out_mom, n * 8)) return fail(c, RT_E_ARG, "temporal: out_film overlaps out_mom");
+    const size_t b4 = n * sizeof(float4), b2 = n * sizeof(float2);
+    if (const int k = overlap_kind({{out_film, b4}, {out_mom, b2}}, {{film, b4}, {mom, b2}, {feat, b4}, {pos, b4},
+                                                                     {hfilm, b4}, {hmom, b2}, {hfeat, b4}, {hpos, b4}}))
+        return fail(c, RT_E_ARG, k == 1 ? "temporal: an output overlaps an input" : "temporal: out_film overlaps out_mom");
     hipSetDevice(c->device);
     rt_ctx::Temporal& t = c->tp;
-    HIPCHK(c, t.s_film.reserve(n)); HIPCHK(c, t.s_mom.reserve(n)); HIPCHK(c, t.s_feat.reserve(n));
-    HIPCHK(c, t.s_pos.reserve(n)); HIPCHK(c, t.s_out.reserve(n)); HIPCHK(c, t.s_outm.reserve(n));
-    if (hist) {
-        HIPCHK(c, t.s_hfilm.reserve(n)); HIPCHK(c, t.s_hmom.reserve(n));
-        HIPCHK(c, t.s_hfeat.reserve(n)); HIPCHK(c, t.s_hpos.reserve(n));
-    }
+    HIPCHK(c, t.s_out.reserve(n)); HIPCHK(c, t.s_outm.reserve(n));
     hipStream_t st = c->stream;
-    if ((rc = order_after_previous(c, st))) return rc;
-    HIPCHK(c, hipMemcpyAsync(t.s_film.get(), film, n * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(t.s_mom.get(), mom, n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(t.s_feat.get(), feat, n * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(t.s_pos.get(), pos, n * 16, hipMemcpyHostToDevice, st));
-    if (hist) {
-        HIPCHK(c, hipMemcpyAsync(t.s_hfilm.get(), hfilm, n * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(t.s_hmom.get(), hmom, n * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(t.s_hfeat.get(), hfeat, n * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(t.s_hpos.get(), hpos, n * 16, hipMemcpyHostToDevice, st));
-    }
     int counts[T_NCLASSES] = {};
-    rc = temporal_device(c, *d, res_x, res_y, t.s_film.get(), t.s_mom.get(), t.s_feat.get(), t.s_pos.get(),
-                         hist ? t.s_hfilm.get() : nullptr, hist ? t.s_hmom.get() : nullptr,
-                         hist ? t.s_hfeat.get() : nullptr, hist ? t.s_hpos.get() : nullptr, M, t.s_out.get(),
-                         t.s_outm.get(), counts, st);
-    const int rc2 = mark_done(c, st);
-    if (rc || rc2) return rc ? rc : rc2;
-    HIPCHK(c, hipMemcpyAsync(out_film, t.s_out.get(), n * 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(out_mom, t.s_outm.get(), n * 8, hipMemcpyDeviceToHost, st));
+    rc = ordered(c, st, [&]() -> int {
+        int rc;
+        if ((rc = stage_in(c, t.s_film, film, n, st)) || (rc = stage_in(c, t.s_mom, mom, n, st)) ||
+            (rc = stage_in(c, t.s_feat, feat, n, st)) || (rc = stage_in(c, t.s_pos, pos, n, st)))
+            return rc;
+        if (hist && ((rc = stage_in(c, t.s_hfilm, hfilm, n, st)) || (rc = stage_in(c, t.s_hmom, hmom, n, st)) ||
+                     (rc = stage_in(c, t.s_hfeat, hfeat, n, st)) || (rc = stage_in(c, t.s_hpos, hpos, n, st))))
+            return rc;
+        const TemporalSet cur{t.s_film.get(), t.s_mom.get(), t.s_feat.get(), t.s_pos.get()};
+        const TemporalSet past{t.s_hfilm.get(), t.s_hmom.get(), t.s_hfeat.get(), t.s_hpos.get()};
+        return temporal_device(c, *d, res_x, res_y, cur, hist ? &past : nullptr, M, t.s_out.get(), t.s_outm.get(), counts,
+                               st);
+    });
+    if (rc || (rc = stage_out(c, out_film, t.s_out, n, st)) || (rc = stage_out(c, out_mom, t.s_outm, n, st))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     temporal_fill_info(info, hist ? 1 : 0, counts);
     return RT_OK;
@@ -2985,55 +3010,39 @@ static int impl_rt_temporal_block_error(rt_ctx* c, const rt_temporal_desc* d, co
     if (!c) return RT_E_ARG;
     if (!d || !ad || !film || !mom || !feat || !pos)
         return fail(c, RT_E_ARG, "temporal block error: both descriptors, film, moments, features and positions are required");
-    const int n_hist = (hfilm != nullptr) + (hmom != nullptr) + (hfeat != nullptr) + (hpos != nullptr);
-    if (n_hist != 0 && n_hist != 4) return fail(c, RT_E_ARG, "temporal: the history is all four arrays or none");
-    const bool hist = n_hist == 4;
-    if (hist && !M) return fail(c, RT_E_ARG, "temporal: a history needs its world-to-film matrix");
-    if (res_x <= 0 || res_y <= 0) return fail(c, RT_E_ARG, "temporal: the resolution must be positive");
-    if ((int64_t)res_x * res_y > ((int64_t)1 << 28)) return fail(c, RT_E_LIMIT, "temporal: more than 2^28 pixels");
-    int rc = temporal_check_desc(c, d);
-    if (rc) return rc;
-    if ((rc = adaptive_check_desc(c, ad, false))) return rc;
+    bool hist;
+    int rc = temporal_check_arrays(c, hfilm, hmom, hfeat, hpos, M, res_x, res_y, &hist);
+    if (rc || (rc = temporal_check_desc(c, d)) || (rc = adaptive_check_desc(c, ad, false))) return rc;
     const size_t n = (size_t)res_x * res_y, nb = (size_t)((res_x + 7) / 8) * ((res_y + 7) / 8);
     hipSetDevice(c->device);
     rt_ctx::Temporal& t = c->tp;
     DevBuf<float> d_err;
     DevBuf<int> d_conv;
     HIPCHK(c, d_err.reserve(nb)); HIPCHK(c, d_conv.reserve(nb));
-    HIPCHK(c, t.s_film.reserve(n)); HIPCHK(c, t.s_mom.reserve(n));
-    if (hist) {
-        HIPCHK(c, t.s_feat.reserve(n)); HIPCHK(c, t.s_pos.reserve(n)); HIPCHK(c, t.rec.reserve(n));
-        HIPCHK(c, t.s_hfilm.reserve(n)); HIPCHK(c, t.s_hmom.reserve(n));
-        HIPCHK(c, t.s_hfeat.reserve(n)); HIPCHK(c, t.s_hpos.reserve(n));
-    }
+    if (hist) HIPCHK(c, t.rec.reserve(n));
     hipStream_t st = c->stream;
-    if ((rc = order_after_previous(c, st))) return rc;
-    HIPCHK(c, hipMemcpyAsync(t.s_film.get(), film, n * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(t.s_mom.get(), mom, n * 8, hipMemcpyHostToDevice, st));
-    if (hist) {
-        HIPCHK(c, hipMemcpyAsync(t.s_feat.get(), feat, n * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(t.s_pos.get(), pos, n * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(t.s_hfilm.get(), hfilm, n * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(t.s_hmom.get(), hmom, n * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(t.s_hfeat.get(), hfeat, n * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(t.s_hpos.get(), hpos, n * 16, hipMemcpyHostToDevice, st));
-    }
-    rc = RT_OK;
-    if (hist) {
-        const TemporalIO io = temporal_io(*d, res_x, res_y, t.s_feat.get(), t.s_pos.get(), t.s_hfilm.get(), t.s_hmom.get(),
-                                          t.s_hfeat.get(), t.s_hpos.get(), M);
-        if (launch_temporal_reproject(st, io, t.rec.get()) != hipSuccess) rc = fail(c, RT_E_HIP, "k_temporal_reproject");
-    }
-    if (!rc) {
+    rc = ordered(c, st, [&]() -> int {
+        int rc;
+        if ((rc = stage_in(c, t.s_film, film, n, st)) || (rc = stage_in(c, t.s_mom, mom, n, st))) return rc;
+        if (hist) {  // (without one the guides take no part)
+            if ((rc = stage_in(c, t.s_feat, feat, n, st)) || (rc = stage_in(c, t.s_pos, pos, n, st)) ||
+                (rc = stage_in(c, t.s_hfilm, hfilm, n, st)) || (rc = stage_in(c, t.s_hmom, hmom, n, st)) ||
+                (rc = stage_in(c, t.s_hfeat, hfeat, n, st)) || (rc = stage_in(c, t.s_hpos, hpos, n, st)))
+                return rc;
+            const TemporalSet cur{t.s_film.get(), t.s_mom.get(), t.s_feat.get(), t.s_pos.get()};
+            const TemporalSet past{t.s_hfilm.get(), t.s_hmom.get(), t.s_hfeat.get(), t.s_hpos.get()};
+            if (launch_temporal_reproject(st, temporal_io(*d, res_x, res_y, cur, &past, M), t.rec.get()) != hipSuccess)
+                return fail(c, RT_E_HIP, "k_temporal_reproject");
+        }
         const AdaptiveIO io{res_x, res_y, t.s_film.get(), t.s_mom.get(), ad->rel_error, ad->abs_floor, d_err.get(),
                             d_conv.get(), nullptr};
         if (launch_temporal_error(st, io, hist ? t.rec.get() : nullptr, d->max_history) != hipSuccess)
-            rc = fail(c, RT_E_HIP, "k_temporal_error");
-    }
-    const int rc2 = mark_done(c, st);
-    if (rc || rc2) return rc ? rc : rc2;
-    if (block_error) HIPCHK(c, hipMemcpyAsync(block_error, d_err.get(), nb * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (converged) HIPCHK(c, hipMemcpyAsync(converged, d_conv.get(), nb * sizeof(int), hipMemcpyDeviceToHost, st));
+            return fail(c, RT_E_HIP, "k_temporal_error");
+        return RT_OK;
+    });
+    if (rc || (block_error && (rc = stage_out(c, block_error, d_err, nb, st))) ||
+        (converged && (rc = stage_out(c, converged, d_conv, nb, st))))
+        return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -3059,7 +3068,6 @@ static int impl_rt_temporal_begin(rt_ctx* c, const rt_temporal_desc* d) {
     t.desc = *d;
     t.frames = 0;
     t.cur = 0;
-    t.in_frame = false;
     t.live = true;
     return RT_OK;
 }
@@ -3088,19 +3096,21 @@ int temporal_frame_body(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_
     const int res_x = c->film.res_x, res_y = c->film.res_y, nx = t.cur ^ 1;
     const size_t n = (size_t)res_x * res_y;
     const bool hist = t.frames > 0;
+    // the frame (its film and moments are the adaptive session's) and the history it is accumulated against
+    const TemporalSet frame{a.film.get(), a.mom.get(), t.feat[nx].get(), t.pos[nx].get()};
+    const TemporalSet last{t.film[t.cur].get(), t.mom[t.cur].get(), t.feat[t.cur].get(), t.pos[t.cur].get()};
+    const TemporalSet* const past = hist ? &last : nullptr;
+    hipStream_t st = c->stream;
     if (guided) {
         if (hist) HIPCHK(c, t.rec.reserve(n));
-        hipStream_t st = c->stream;
-        if ((rc = order_after_previous(c, st))) return rc;
-        rc = temporal_frame_guides(c, st);
-        if (!rc && hist) {
-            const TemporalIO io = temporal_io(t.desc, res_x, res_y, t.feat[nx].get(), t.pos[nx].get(), t.film[t.cur].get(),
-                                              t.mom[t.cur].get(), t.feat[t.cur].get(), t.pos[t.cur].get(), t.M);
-            rc = launch_temporal_reproject(st, io, t.rec.get()) == hipSuccess ? RT_OK
-                                                                             : fail(c, RT_E_HIP, "k_temporal_reproject");
-        }
-        const int rc2 = mark_done(c, st);
-        if (rc || rc2) return rc ? rc : rc2;
+        rc = ordered(c, st, [&]() -> int {
+            if (int rc = temporal_frame_guides(c, st)) return rc;
+            if (hist && launch_temporal_reproject(st, temporal_io(t.desc, res_x, res_y, frame, past, t.M), t.rec.get()) !=
+                            hipSuccess)
+                return fail(c, RT_E_HIP, "k_temporal_reproject");
+            return RT_OK;
+        });
+        if (rc) return rc;
         a.guide.on = true;
         a.guide.rec = hist ? t.rec.get() : nullptr;
         a.guide.max_history = t.desc.max_history;
@@ -3111,21 +3121,16 @@ int temporal_frame_body(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_
     } while (cur.active_pixels > 0 && cur.index_done < ad->max_samples);
     if (session) *session = cur;
     if (dd) HIPCHK(c, c->dn.out.reserve(n));
-    hipStream_t st = c->stream;
-    if ((rc = order_after_previous(c, st))) return rc;
-    rc = guided ? RT_OK : temporal_frame_guides(c, st);
-    if (!rc)
-        rc = temporal_device(c, t.desc, res_x, res_y, a.film.get(), a.mom.get(), t.feat[nx].get(), t.pos[nx].get(),
-                             hist ? t.film[t.cur].get() : nullptr, hist ? t.mom[t.cur].get() : nullptr,
-                             hist ? t.feat[t.cur].get() : nullptr, hist ? t.pos[t.cur].get() : nullptr, t.M,
-                             t.film[nx].get(), t.mom[nx].get(), counts, st);
-    if (!rc && dd)
-        rc = denoise_device(c, *dd, res_x, res_y, t.film[nx].get(), t.mom[nx].get(), t.feat[nx].get(), c->dn.out.get(),
-                            nullptr, st);
-    const int rc2 = mark_done(c, st);
-    if (rc || rc2) return rc ? rc : rc2;
-    HIPCHK(c, hipMemcpyAsync(film_out, dd ? c->dn.out.get() : t.film[nx].get(), n * sizeof(float4),
-                             hipMemcpyDeviceToHost, st));
+    rc = ordered(c, st, [&]() -> int {
+        int rc;
+        if (!guided && (rc = temporal_frame_guides(c, st))) return rc;
+        if ((rc = temporal_device(c, t.desc, res_x, res_y, frame, past, t.M, t.film[nx].get(), t.mom[nx].get(), counts, st)))
+            return rc;
+        return dd ? denoise_device(c, *dd, res_x, res_y, t.film[nx].get(), t.mom[nx].get(), t.feat[nx].get(),
+                                   c->dn.out.get(), nullptr, st)
+                  : RT_OK;
+    });
+    if (rc || (rc = stage_out(c, film_out, dd ? c->dn.out : t.film[nx], n, st))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -3133,8 +3138,7 @@ int temporal_frame_body(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_
 
 // rt_temporal_frame and rt_temporal_frame_guided (guided; session: its adaptive session's last info, may be null)
 static int impl_rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* ad, const rt_denoise_desc* dd, const float* M,
-                                  rt_pixel* film_out, rt_temporal_info* info, bool guided = false,
-                                  rt_adaptive_info* session = nullptr) {
+                                  rt_pixel* film_out, rt_temporal_info* info, bool guided, rt_adaptive_info* session) {
     if (!c) return RT_E_ARG;
     rt_ctx::Temporal& t = c->tp;
     if (!t.live) return fail(c, RT_E_STATE, "no temporal session is open (rt_temporal_begin first)");
@@ -3152,10 +3156,7 @@ static int impl_rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* ad, const r
     if (t.desc.feature_samples > dev_sampler(c).spp)
         return fail(c, RT_E_ARG, "temporal: feature_samples exceeds the sampler's samples per pixel");
     if (c->ad.live) adaptive_release(c);  // (only a frame that ended in an exception leaves its session behind)
-    t.in_frame = true;
-    rc = impl_rt_adaptive_begin(c, ad);
-    t.in_frame = false;
-    if (rc) return rc;
+    if ((rc = impl_rt_adaptive_begin(c, ad, /*frame_owned=*/true))) return rc;
     int counts[T_NCLASSES] = {};
     rt_adaptive_info cur{};
     rc = temporal_frame_body(c, ad, dd, film_out, counts, guided, &cur);
@@ -3196,7 +3197,7 @@ int film_resolve(rt_ctx* c, const rt_pixel* film, uint8_t* out, int srgb) {
     HIPCHK(c, df.reserve(n));
     if (dout.reserve(3 * n) != hipSuccess) return fail(c, RT_E_OOM, "resolve buffer");
     const float* const m = c->d_resolve.get();
-    if (hipMemcpy(df.get(), film, n * 16, hipMemcpyHostToDevice) != hipSuccess ||
+    if (hipMemcpy(df.get(), film, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
         launch_resolve(c->stream, (int)n, df.get(), m, m + 9, dout.get(), srgb) != hipSuccess ||
         hipMemcpyAsync(out, dout.get(), 3 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
@@ -3204,9 +3205,6 @@ int film_resolve(rt_ctx* c, const rt_pixel* film, uint8_t* out, int srgb) {
     return RT_OK;
 }
 }  // namespace
-
-static int impl_rt_film_resolve(rt_ctx* c, const rt_pixel* film, uint8_t* out) { return film_resolve(c, film, out, 0); }
-static int impl_rt_film_resolve_srgb(rt_ctx* c, const rt_pixel* film, uint8_t* out) { return film_resolve(c, film, out, 1); }
 
 static int get_stats_one(rt_ctx* c, rt_stats* out) {
     if (!c || !out) return RT_E_ARG;
@@ -3338,30 +3336,33 @@ static int impl_rt_debug_trace(rt_ctx* c, int n, const float* ro, const float* r
     // cooperative BFS for the undecided rays (or k_trace_fallback without coop_ok) — instead of the per-thread one
     const bool path_kernel = c->knobs.debug_path && c->dsc.qcap != 1;
     int rc = ensure_ring(c, c->ws[0]);
-    if (!rc) rc = order_after_previous(c, c->stream);
     if (rc) return rc;
-    DevBuf<float4> dO, dD, dH;
-    DevBuf<int> dP, dT, dF;
-    if (dO.reserve(n) || dD.reserve(n) || dH.reserve(n) || dP.reserve(n) ||
-        (path_kernel && (dT.reserve(2 * kQStride) || dF.reserve(n))))
-        return fail(c, RT_E_OOM, "debug trace buffers");
-    TraceIO io{dO.get(), dD.get(), QueueView{nullptr, shard_stride(n, 1), n, 1}, (use_cull && c->cull) ? 1 : 0, dH.get(),
-               dP.get()};
-    if (path_kernel) {  // (ticket counter at dT[0], fallback list length at dT[kQStride])
-        io.ticket = dT.get();
-        io.fb_pos = dF.get();
-        io.fb_len = dT.get() + kQStride;
-    }
-    const DevScene ls = lane_scene(c, c->ws[0]);
-    if ((path_kernel && hipMemsetAsync(dT.get(), 0, 2 * kQStride * sizeof(int), c->stream) != hipSuccess) ||
-        upload_rays(n, ro, rd, nullptr, dO.get(), dD.get()) != hipSuccess ||
-        launch_trace_closest(c->stream, 0, c->dsc.qcap, ls, io, c->d_ctr.get()) != hipSuccess ||
-        (path_kernel && !c->dsc.coop_ok &&
-         launch_trace_fallback(c->stream, 64, c->dsc.qcap, ls, io, c->d_ctr.get()) != hipSuccess) ||
-        hipStreamSynchronize(c->stream) != hipSuccess ||
-        hipMemcpy(prim, dP.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(bt, dH.get(), 16 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RT_E_HIP, std::string("debug trace: ") + hipGetErrorString(hipGetLastError()));
+    rc = ordered(c, c->stream, [&]() -> int {
+        DevBuf<float4> dO, dD, dH;
+        DevBuf<int> dP, dT, dF;
+        if (dO.reserve(n) || dD.reserve(n) || dH.reserve(n) || dP.reserve(n) ||
+            (path_kernel && (dT.reserve(2 * kQStride) || dF.reserve(n))))
+            return fail(c, RT_E_OOM, "debug trace buffers");
+        TraceIO io{dO.get(), dD.get(), QueueView{nullptr, shard_stride(n, 1), n, 1}, (use_cull && c->cull) ? 1 : 0,
+                   dH.get(), dP.get()};
+        if (path_kernel) {  // (ticket counter at dT[0], fallback list length at dT[kQStride])
+            io.ticket = dT.get();
+            io.fb_pos = dF.get();
+            io.fb_len = dT.get() + kQStride;
+        }
+        const DevScene ls = lane_scene(c, c->ws[0]);
+        if ((path_kernel && hipMemsetAsync(dT.get(), 0, 2 * kQStride * sizeof(int), c->stream) != hipSuccess) ||
+            upload_rays(n, ro, rd, nullptr, dO.get(), dD.get()) != hipSuccess ||
+            launch_trace_closest(c->stream, 0, c->dsc.qcap, ls, io, c->d_ctr.get()) != hipSuccess ||
+            (path_kernel && !c->dsc.coop_ok &&
+             launch_trace_fallback(c->stream, 64, c->dsc.qcap, ls, io, c->d_ctr.get()) != hipSuccess) ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(prim, dP.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(bt, dH.get(), 16 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("debug trace: ") + hipGetErrorString(hipGetLastError()));
+        return RT_OK;
+    });
+    if (rc) return rc;
     for (int i = 0; i < n; ++i)
         if (prim[i] < 0) bt[4 * i] = bt[4 * i + 1] = bt[4 * i + 2] = bt[4 * i + 3] = 0.f;
     return RT_OK;
@@ -3373,18 +3374,19 @@ static int impl_rt_debug_occluded(rt_ctx* c, int n, const float* ro, const float
     if (n == 0) return RT_OK;
     hipSetDevice(c->device);
     int rc = ensure_ring(c, c->ws[0]);
-    if (!rc) rc = order_after_previous(c, c->stream);
     if (rc) return rc;
-    DevBuf<float4> dO, dD;
-    DevBuf<int> dP;
-    if (dO.reserve(n) || dD.reserve(n) || dP.reserve(n)) return fail(c, RT_E_OOM, "debug occlusion buffers");
-    if (upload_rays(n, ro, rd, tmax, dO.get(), dD.get()) != hipSuccess ||
-        launch_occluded(c->stream, c->dsc.qcap, lane_scene(c, c->ws[0]), n, dO.get(), dD.get(), dP.get(), c->d_ctr.get(),
-                        c->knobs.debug_path && c->dsc.coop_ok) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess ||
-        hipMemcpy(occluded, dP.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RT_E_HIP, std::string("debug occlusion: ") + hipGetErrorString(hipGetLastError()));
-    return RT_OK;
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float4> dO, dD;
+        DevBuf<int> dP;
+        if (dO.reserve(n) || dD.reserve(n) || dP.reserve(n)) return fail(c, RT_E_OOM, "debug occlusion buffers");
+        if (upload_rays(n, ro, rd, tmax, dO.get(), dD.get()) != hipSuccess ||
+            launch_occluded(c->stream, c->dsc.qcap, lane_scene(c, c->ws[0]), n, dO.get(), dD.get(), dP.get(),
+                            c->d_ctr.get(), c->knobs.debug_path && c->dsc.coop_ok) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(occluded, dP.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("debug occlusion: ") + hipGetErrorString(hipGetLastError()));
+        return RT_OK;
+    });
 }
 
 // The coherence sorts alone (rt_sort.hip) on a synthetic sharded queue: kShards shards of stride S, shard j holding
@@ -3403,39 +3405,40 @@ static int impl_rt_debug_sort(rt_ctx* c, int which, int S, const int32_t* shard_
     if (bits_a < 0 || bits_a > (which == 0 ? 4 : 9) || bits_b < 0 || bits_b > 9 || kb < 1 || kb > 30)
         return fail(c, RT_E_ARG, "debug sort: key bits out of range");
     hipSetDevice(c->device);
-    int rc = order_after_previous(c, c->stream);
-    if (rc) return rc;
-    const size_t cap = (size_t)kShards * S;
-    DevBuf<unsigned> dkey, k0, k1;
-    DevBuf<int> dslot, dlen, dout, v0, v1;
-    DevBuf<unsigned char> temp;
-    if (dkey.reserve(cap) || dslot.reserve(cap) || dlen.reserve((size_t)kShards * kQStride) || dout.reserve(cap) ||
-        k0.reserve(cap) || k1.reserve(cap) || v0.reserve(cap) || v1.reserve(cap) || temp.reserve(sort_temp_bytes()))
-        return fail(c, RT_E_OOM, "debug sort buffers");
-    std::vector<int> hlen((size_t)kShards * kQStride, 0);
-    for (int j = 0; j < kShards; ++j) hlen[(size_t)j * kQStride] = shard_len[j];
-    std::vector<int> hs(cap, -1);
-    if (which == 1) std::memcpy(hs.data(), slots, cap * 4);
-    hipError_t e = hipMemcpy(dkey.get(), keys, cap * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dslot.get(), hs.data(), cap * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dlen.get(), hlen.data(), hlen.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dout.get(), 0xff, cap * 4);
-    if (e == hipSuccess) {
-        if (which == 0) {
-            SortRaysIO so{dkey.get(), dout.get(), k0.get(), k1.get(), v0.get(), v1.get(), temp.get(), bits_a, bits_b,
-                          dlen.get(), S};
-            e = launch_sort_rays(c->stream, so);
-        } else {
-            SortNeeIO so{dslot.get(), dlen.get(), S, dkey.get(), k0.get(), k1.get(), v0.get(), v1.get(), temp.get(), bits_a};
-            e = launch_sort_nee(c->stream, so);
+    return ordered(c, c->stream, [&]() -> int {
+        const size_t cap = (size_t)kShards * S;
+        DevBuf<unsigned> dkey, k0, k1;
+        DevBuf<int> dslot, dlen, dout, v0, v1;
+        DevBuf<unsigned char> temp;
+        if (dkey.reserve(cap) || dslot.reserve(cap) || dlen.reserve((size_t)kShards * kQStride) || dout.reserve(cap) ||
+            k0.reserve(cap) || k1.reserve(cap) || v0.reserve(cap) || v1.reserve(cap) || temp.reserve(sort_temp_bytes()))
+            return fail(c, RT_E_OOM, "debug sort buffers");
+        std::vector<int> hlen((size_t)kShards * kQStride, 0);
+        for (int j = 0; j < kShards; ++j) hlen[(size_t)j * kQStride] = shard_len[j];
+        std::vector<int> hs(cap, -1);
+        if (which == 1) std::memcpy(hs.data(), slots, cap * 4);
+        hipError_t e = hipMemcpy(dkey.get(), keys, cap * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dslot.get(), hs.data(), cap * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dlen.get(), hlen.data(), hlen.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(dout.get(), 0xff, cap * 4);
+        if (e == hipSuccess) {
+            if (which == 0) {
+                SortRaysIO so{dkey.get(), dout.get(), k0.get(), k1.get(), v0.get(), v1.get(), temp.get(), bits_a, bits_b,
+                              dlen.get(), S};
+                e = launch_sort_rays(c->stream, so);
+            } else {
+                SortNeeIO so{dslot.get(), dlen.get(), S, dkey.get(), k0.get(), k1.get(), v0.get(), v1.get(), temp.get(),
+                             bits_a};
+                e = launch_sort_nee(c->stream, so);
+            }
         }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, which == 0 ? dout.get() : dslot.get(), cap * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hlen.data(), dlen.get(), hlen.size() * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(c, RT_E_HIP, std::string("debug sort: ") + hipGetErrorString(e));
-    for (int j = 0; j < kShards; ++j) out_len[j] = hlen[(size_t)j * kQStride];
-    return mark_done(c, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(out, which == 0 ? dout.get() : dslot.get(), cap * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(hlen.data(), dlen.get(), hlen.size() * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(c, RT_E_HIP, std::string("debug sort: ") + hipGetErrorString(e));
+        for (int j = 0; j < kShards; ++j) out_len[j] = hlen[(size_t)j * kQStride];
+        return RT_OK;
+    });
 }
 
 static int impl_rt_debug_samples(rt_ctx* c, int n, const int32_t* pixel_ids, const int32_t* indices, rt_sample_record* out) {
@@ -3455,25 +3458,26 @@ static int impl_rt_debug_samples(rt_ctx* c, int n, const int32_t* pixel_ids, con
     hipSetDevice(c->device);
     Work& w = c->ws[0];
     if ((rc = ensure_workspace(c, w, (size_t)n, false))) return rc;
-    if ((rc = order_after_previous(c, c->stream))) return rc;
-    DevBuf<int> dp, di;
-    DevBuf<float> dout;
-    static_assert(sizeof(rt_sample_record) == 39 * 4, "record layout");
-    if (dp.reserve(n) || di.reserve(n) || dout.reserve((size_t)n * 39)) return fail(c, RT_E_OOM, "record buffers");
-    hipMemcpy(dp.get(), pixel_ids, 4 * (size_t)n, hipMemcpyHostToDevice);
-    hipMemcpy(di.get(), indices, 4 * (size_t)n, hipMemcpyHostToDevice);
-    SampleIds ids{nullptr, 1, 0, dp.get(), di.get()};
-    const RefIO r = ref_io(c, w.b, n, 1);
-    DevFilm fd = dev_film(c);
-    RecordIO rio{n, r.go.rayO, r.go.rayD, r.go.lamA, r.go.lamB, r.go.pdfA, r.go.pdfB, r.tio.hitB, r.tio.hitPrim, dout.get(),
-                 39, 1};
-    if (launch_generate(c->stream, 0, n, ids, dev_camera(c->cam), smp, fd, r.go) != hipSuccess ||
-        launch_trace_closest(c->stream, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()) != hipSuccess ||
-        launch_records(c->stream, c->dsc, c->d_spec.get(), fd, r.sio, rio) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess ||
-        hipMemcpy(out, dout.get(), sizeof(rt_sample_record) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(c, RT_E_HIP, std::string("debug samples: ") + hipGetErrorString(hipGetLastError()));
-    return RT_OK;
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<int> dp, di;
+        DevBuf<float> dout;
+        static_assert(sizeof(rt_sample_record) == 39 * 4, "record layout");
+        if (dp.reserve(n) || di.reserve(n) || dout.reserve((size_t)n * 39)) return fail(c, RT_E_OOM, "record buffers");
+        hipMemcpy(dp.get(), pixel_ids, 4 * (size_t)n, hipMemcpyHostToDevice);
+        hipMemcpy(di.get(), indices, 4 * (size_t)n, hipMemcpyHostToDevice);
+        SampleIds ids{nullptr, 1, 0, dp.get(), di.get()};
+        const RefIO r = ref_io(c, w.b, n, 1);
+        DevFilm fd = dev_film(c);
+        RecordIO rio{n, r.go.rayO, r.go.rayD, r.go.lamA, r.go.lamB, r.go.pdfA, r.go.pdfB, r.tio.hitB, r.tio.hitPrim,
+                     dout.get(), 39, 1};
+        if (launch_generate(c->stream, 0, n, ids, dev_camera(c->cam), smp, fd, r.go) != hipSuccess ||
+            launch_trace_closest(c->stream, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()) != hipSuccess ||
+            launch_records(c->stream, c->dsc, c->d_spec.get(), fd, r.sio, rio) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(out, dout.get(), sizeof(rt_sample_record) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("debug samples: ") + hipGetErrorString(hipGetLastError()));
+        return RT_OK;
+    });
 }
 
 // ---- multi-device wrappers: configuration goes to every device of the context -------------------------------
@@ -3595,158 +3599,119 @@ static int impl_rt_set_shard(rt_ctx* c, int tile_size, int n_shards, int shard_i
 }  // extern "C"
 
 // ---- the exception firewall around every entry point (rt_guard.h)
+namespace {
+// an entry point with a context: impl(c, args...) inside the firewall, an exception's message to rt_last_error
+template <class Impl, class... Args>
+int entry(rt_ctx* c, Impl impl, Args... args) {
+    return guarded([&] { return impl(c, args...); }, [&](const std::string& m) { set_error(c, m); });
+}
+}  // namespace
+
 extern "C" {
 int rt_film_matrices(rt_ctx* c, float* xyz_from_sensor9, float* rgb_from_xyz9) {
-    return guarded([&] { return impl_rt_film_matrices(c, xyz_from_sensor9, rgb_from_xyz9); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_film_matrices, xyz_from_sensor9, rgb_from_xyz9);
 }
 int rt_render_pass_device(rt_ctx* c, int ib, int ie, void* d_film, void* stream) {
-    return guarded([&] { return impl_rt_render_pass_device(c, ib, ie, d_film, stream); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_render_pass_device, ib, ie, d_film, stream);
 }
-int rt_render_pass(rt_ctx* c, int ib, int ie, rt_pixel* film) {
-    return guarded([&] { return impl_rt_render_pass(c, ib, ie, film); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d) {
-    return guarded([&] { return impl_rt_adaptive_begin(c, d); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_adaptive_step(rt_ctx* c, rt_adaptive_info* info) {
-    return guarded([&] { return impl_rt_adaptive_step(c, info); }, [&](const std::string& m) { set_error(c, m); });
-}
+int rt_render_pass(rt_ctx* c, int ib, int ie, rt_pixel* film) { return entry(c, impl_rt_render_pass, ib, ie, film); }
+int rt_adaptive_begin(rt_ctx* c, const rt_adaptive_desc* d) { return entry(c, impl_rt_adaptive_begin, d, false); }
+int rt_adaptive_step(rt_ctx* c, rt_adaptive_info* info) { return entry(c, impl_rt_adaptive_step, info); }
 int rt_adaptive_read(rt_ctx* c, rt_pixel* film, rt_moment* mom, float* block_error, int32_t* active, int* n_active) {
-    return guarded([&] { return impl_rt_adaptive_read(c, film, mom, block_error, active, n_active); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_adaptive_read, film, mom, block_error, active, n_active);
 }
-int rt_adaptive_end(rt_ctx* c) {
-    return guarded([&] { return impl_rt_adaptive_end(c); }, [&](const std::string& m) { set_error(c, m); });
-}
+int rt_adaptive_end(rt_ctx* c) { return entry(c, impl_rt_adaptive_end); }
 int rt_render_adaptive(rt_ctx* c, const rt_adaptive_desc* d, rt_pixel* film, rt_moment* mom, rt_adaptive_info* info) {
-    return guarded([&] { return impl_rt_render_adaptive(c, d, film, mom, info); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_render_adaptive, d, film, mom, info);
 }
 int rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, const rt_pixel* film, const rt_moment* mom,
                              float* block_error, int32_t* active, int* n_active) {
-    return guarded([&] { return impl_rt_debug_adaptive_select(c, d, film, mom, block_error, active, n_active); },
-                   [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_debug_adaptive_select, d, film, mom, block_error, active, n_active);
 }
 int rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat) {
-    return guarded([&] { return impl_rt_render_features(c, ib, ie, feat); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_render_features, ib, ie, feat, nullptr, false, 0);
 }
 int rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int res_y, const rt_pixel* film, const rt_moment* mom,
                const rt_feature* feat, rt_pixel* out, float* variance_out) {
-    return guarded([&] { return impl_rt_denoise(c, d, res_x, res_y, film, mom, feat, out, variance_out); },
-                   [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_denoise, d, res_x, res_y, film, mom, feat, out, variance_out);
 }
 int rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixel* film_out) {
-    return guarded([&] { return impl_rt_adaptive_denoise(c, d, film_out); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_adaptive_denoise, d, film_out);
 }
 int rt_render_features_chain(rt_ctx* c, int ib, int ie, int chain_depth, rt_feature* feat, rt_position* pos) {
-    return guarded([&] { return impl_rt_render_features_chain(c, ib, ie, chain_depth, feat, pos); },
-                   [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_render_features, ib, ie, feat, pos, pos != nullptr, chain_depth);
 }
 int rt_render_features_pos(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos) {
-    return guarded([&] { return impl_rt_render_features_pos(c, ib, ie, feat, pos); },
-                   [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_render_features, ib, ie, feat, pos, true, 0);
 }
 int rt_temporal_accumulate(rt_ctx* c, const rt_temporal_desc* d, int res_x, int res_y, const rt_pixel* film,
                            const rt_moment* mom, const rt_feature* feat, const rt_position* pos, const rt_pixel* hist_film,
                            const rt_moment* hist_mom, const rt_feature* hist_feat, const rt_position* hist_pos,
                            const float* world_to_film_prev, rt_pixel* out_film, rt_moment* out_mom, rt_temporal_info* info) {
-    return guarded(
-        [&] {
-            return impl_rt_temporal_accumulate(c, d, res_x, res_y, film, mom, feat, pos, hist_film, hist_mom, hist_feat,
-                                               hist_pos, world_to_film_prev, out_film, out_mom, info);
-        },
-        [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_temporal_accumulate, d, res_x, res_y, film, mom, feat, pos, hist_film, hist_mom, hist_feat,
+                 hist_pos, world_to_film_prev, out_film, out_mom, info);
 }
-int rt_temporal_begin(rt_ctx* c, const rt_temporal_desc* d) {
-    return guarded([&] { return impl_rt_temporal_begin(c, d); }, [&](const std::string& m) { set_error(c, m); });
-}
+int rt_temporal_begin(rt_ctx* c, const rt_temporal_desc* d) { return entry(c, impl_rt_temporal_begin, d); }
 int rt_temporal_frame(rt_ctx* c, const rt_adaptive_desc* adaptive, const rt_denoise_desc* denoise, const float* world_to_film,
                       rt_pixel* film_out, rt_temporal_info* info) {
-    return guarded([&] { return impl_rt_temporal_frame(c, adaptive, denoise, world_to_film, film_out, info); },
-                   [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_temporal_frame, adaptive, denoise, world_to_film, film_out, info, false, nullptr);
 }
 int rt_temporal_frame_guided(rt_ctx* c, const rt_adaptive_desc* adaptive, const rt_denoise_desc* denoise,
                              const float* world_to_film, rt_pixel* film_out, rt_temporal_info* info,
                              rt_adaptive_info* session_info) {
-    return guarded(
-        [&] { return impl_rt_temporal_frame(c, adaptive, denoise, world_to_film, film_out, info, true, session_info); },
-        [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_temporal_frame, adaptive, denoise, world_to_film, film_out, info, true, session_info);
 }
 int rt_temporal_block_error(rt_ctx* c, const rt_temporal_desc* d, const rt_adaptive_desc* adaptive, int res_x, int res_y,
                             const rt_pixel* film, const rt_moment* mom, const rt_feature* feat, const rt_position* pos,
                             const rt_pixel* hist_film, const rt_moment* hist_mom, const rt_feature* hist_feat,
                             const rt_position* hist_pos, const float* world_to_film_prev, float* block_error,
                             int32_t* converged) {
-    return guarded(
-        [&] {
-            return impl_rt_temporal_block_error(c, d, adaptive, res_x, res_y, film, mom, feat, pos, hist_film, hist_mom,
-                                                hist_feat, hist_pos, world_to_film_prev, block_error, converged);
-        },
-        [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_temporal_block_error, d, adaptive, res_x, res_y, film, mom, feat, pos, hist_film, hist_mom,
+                 hist_feat, hist_pos, world_to_film_prev, block_error, converged);
 }
-int rt_temporal_reset(rt_ctx* c) {
-    return guarded([&] { return impl_rt_temporal_reset(c); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_temporal_end(rt_ctx* c) {
-    return guarded([&] { return impl_rt_temporal_end(c); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_film_resolve(rt_ctx* c,const rt_pixel* film, uint8_t* out) {
-    return guarded([&] { return impl_rt_film_resolve(c, film, out); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_film_resolve_srgb(rt_ctx* c, const rt_pixel* film, uint8_t* out) {
-    return guarded([&] { return impl_rt_film_resolve_srgb(c, film, out); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_octree_get_info(rt_ctx* c, rt_octree_info* out) {
-    return guarded([&] { return impl_rt_octree_get_info(c, out); }, [&](const std::string& m) { set_error(c, m); });
-}
+int rt_temporal_reset(rt_ctx* c) { return entry(c, impl_rt_temporal_reset); }
+int rt_temporal_end(rt_ctx* c) { return entry(c, impl_rt_temporal_end); }
+int rt_film_resolve(rt_ctx* c, const rt_pixel* film, uint8_t* out) { return entry(c, film_resolve, film, out, 0); }
+int rt_film_resolve_srgb(rt_ctx* c, const rt_pixel* film, uint8_t* out) { return entry(c, film_resolve, film, out, 1); }
+int rt_octree_get_info(rt_ctx* c, rt_octree_info* out) { return entry(c, impl_rt_octree_get_info, out); }
 int rt_octree_export(rt_ctx* c, float* bounds, int32_t* child, int32_t* leaf_first, int32_t* leaf_count, int32_t* refs) {
-    return guarded([&] { return impl_rt_octree_export(c, bounds, child, leaf_first, leaf_count, refs); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_octree_export, bounds, child, leaf_first, leaf_count, refs);
 }
 int rt_bvh_export(rt_ctx* c, int set, int* n_nodes, int* n_tiles, float* consts, float* nodes, float* tiles) {
-    return guarded([&] { return impl_rt_bvh_export(c, set, n_nodes, n_tiles, consts, nodes, tiles); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_bvh_export, set, n_nodes, n_tiles, consts, nodes, tiles);
 }
+// (no context: no message to keep)
 int rt_debug_bvh_build(const rt_scene_desc* s, int set, int* n_nodes, int* n_tiles, float* consts, float* nodes, float* tiles) {
     return guarded([&] { return impl_rt_debug_bvh_build(s, set, n_nodes, n_tiles, consts, nodes, tiles); }, [](const std::string&) {});
 }
 int rt_debug_trace(rt_ctx* c, int n, const float* ro, const float* rd, int use_cull, int32_t* prim, float* bt) {
-    return guarded([&] { return impl_rt_debug_trace(c, n, ro, rd, use_cull, prim, bt); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_debug_trace, n, ro, rd, use_cull, prim, bt);
 }
 int rt_debug_occluded(rt_ctx* c, int n, const float* ro, const float* rd, const float* tmax, int32_t* occluded) {
-    return guarded([&] { return impl_rt_debug_occluded(c, n, ro, rd, tmax, occluded); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_debug_occluded, n, ro, rd, tmax, occluded);
 }
 int rt_debug_samples(rt_ctx* c, int n, const int32_t* pixel_ids, const int32_t* indices, rt_sample_record* out) {
-    return guarded([&] { return impl_rt_debug_samples(c, n, pixel_ids, indices, out); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_debug_samples, n, pixel_ids, indices, out);
 }
 int rt_debug_sort(rt_ctx* c, int which, int S, const int32_t* shard_len, const uint32_t* keys, const int32_t* slots,
                   int bits_a, int bits_b, int32_t* out, int32_t* out_len) {
-    return guarded([&] { return impl_rt_debug_sort(c, which, S, shard_len, keys, slots, bits_a, bits_b, out, out_len); },
-                   [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_debug_sort, which, S, shard_len, keys, slots, bits_a, bits_b, out, out_len);
 }
+// (no context yet)
 int rt_create(const rt_options* opt, rt_ctx** out) {
     return guarded([&] { return impl_rt_create(opt, out); }, [&](const std::string& m) { set_error(nullptr, m); });
 }
-int rt_scene_upload(rt_ctx* c, const rt_scene_desc* s) {
-    return guarded([&] { return impl_rt_scene_upload(c, s); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_camera_set(rt_ctx* c, const rt_camera_desc* d) {
-    return guarded([&] { return impl_rt_camera_set(c, d); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_sampler_set(rt_ctx* c, const rt_sampler_desc* d) {
-    return guarded([&] { return impl_rt_sampler_set(c, d); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_film_set(rt_ctx* c, const rt_film_desc* d) {
-    return guarded([&] { return impl_rt_film_set(c, d); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_integrator_set(rt_ctx* c, const rt_integrator_desc* d) {
-    return guarded([&] { return impl_rt_integrator_set(c, d); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_reset_stats(rt_ctx* c) {
-    return guarded([&] { return impl_rt_reset_stats(c); }, [&](const std::string& m) { set_error(c, m); });
-}
-int rt_get_stats(rt_ctx* c, rt_stats* out) {
-    return guarded([&] { return impl_rt_get_stats(c, out); }, [&](const std::string& m) { set_error(c, m); });
-}
+int rt_scene_upload(rt_ctx* c, const rt_scene_desc* s) { return entry(c, impl_rt_scene_upload, s); }
+int rt_camera_set(rt_ctx* c, const rt_camera_desc* d) { return entry(c, impl_rt_camera_set, d); }
+int rt_sampler_set(rt_ctx* c, const rt_sampler_desc* d) { return entry(c, impl_rt_sampler_set, d); }
+int rt_film_set(rt_ctx* c, const rt_film_desc* d) { return entry(c, impl_rt_film_set, d); }
+int rt_integrator_set(rt_ctx* c, const rt_integrator_desc* d) { return entry(c, impl_rt_integrator_set, d); }
+int rt_reset_stats(rt_ctx* c) { return entry(c, impl_rt_reset_stats); }
+int rt_get_stats(rt_ctx* c, rt_stats* out) { return entry(c, impl_rt_get_stats, out); }
 int rt_set_shard(rt_ctx* c, int tile_size, int n_shards, int shard_id) {
-    return guarded([&] { return impl_rt_set_shard(c, tile_size, n_shards, shard_id); }, [&](const std::string& m) { set_error(c, m); });
+    return entry(c, impl_rt_set_shard, tile_size, n_shards, shard_id);
 }
+// (exempt from fault injection: an injected fault would only leak what it frees)
 void rt_destroy(rt_ctx* c) {
     guarded([&] { impl_rt_destroy(c); return 0; }, [](const std::string&) {}, /*inject=*/false);
 }
