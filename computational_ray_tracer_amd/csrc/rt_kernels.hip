@@ -16,6 +16,7 @@
 #include <mutex>
 #include <type_traits>
 #include <unordered_map>
+#include <utility>
 
 #include "rt_device.h"
 
@@ -739,12 +740,271 @@ __device__ __forceinline__ int cluster_tris(uint32_t hm, int ncl, int n) {
     return t;
 }
 // ===================================================================================== K2 traverse
+// One triangle of a walk in the reference's order: a hit with t < tMax is accepted ("t < tMax": the first hit found
+// wins ties).  Closest hit: tMax shrinks to it and its barycentrics are kept.  True: an any-hit query is answered.
+template <int KZ, bool ANYHIT>
+__device__ __forceinline__ bool accept_hit(const TriRay& R, const float4& A, const float4& B, const float4& Cc,
+                                           float& tMax, int& best, float& rb0, float& rb1, float& rb2, float& rt) {
+    float b0, b1, b2, t;
+    if (tri_intersect<KZ>(R, tMax, A, B, Cc, b0, b1, b2, t) && t < tMax) {
+        best = __float_as_int(Cc.y);
+        if (ANYHIT) return true;
+        tMax = t; rb0 = b0; rb1 = b1; rb2 = b2; rt = t;
+    }
+    return false;
+}
+// Candidate bits of cluster c (bit u: leaf tile 2 c + u) of the single leaf r for ray R, from the LDS tiles; fp bit k:
+// leaf tiles k, k+1 share vertices (a,b,c),(a,c,d)
+template <int KZ>
+__device__ __forceinline__ unsigned cluster_candidates(const TriRay& R, const float4* tiles, int2 r, int c,
+                                                       uint64_t fp) {
+    const float4* tp = RT_LEAF1(tiles, r.x, 2 * c);
+    if ((fp >> (2 * c)) & 1) return tri_candidate_pair<KZ>(R, tp[0], tp[1], tp[2], tp[4], tp[5]);
+    unsigned bits = tri_candidate<KZ>(R, tp[0], tp[1], tp[2]) ? 1u : 0u;
+    if (2 * c + 1 < r.y && tri_candidate<KZ>(R, tp[3], tp[4], tp[5])) bits |= 2u;
+    return bits;
+}
+// The whole octree is one leaf (e.g. the 36-triangle Cornell box: 36 < TRIANGLE_CAPACITY): every
+// lane walks the same triangle list, so it is read through the scalar cache into SGPRs once per
+// wave; four triangles (12 x s_load_dwordx4) are fetched per scalar-cache round trip.
+template <bool ANYHIT, int KZ>
+__device__ __forceinline__ int leaf1_walk(const DevScene& sc, int set, V3 o, V3 d, float tMaxInit, float& rb0,
+                                          float& rb1, float& rb2, float& rt, ctr_t& nn, ctr_t& nt) {
+    V3 inv = v3(1 / d.x, 1 / d.y, 1 / d.z);
+    TriRay R = make_triray<KZ>(o, d);
+    float tMax = tMaxInit;
+    int best = -1;
+    const float4* __restrict__ tiles = sc.tiles[set];
+    ++nn;
+    bool inside = box_hit(ldc4(sc.nodeA, 0), ldc4(sc.nodeB, 0), o, inv, tMax);
+    int2 r = ldc2i(sc.leafRange[set], 0);
+    if (inside) {
+        auto test = [&](float4 A, float4 B, float4 Cc) -> bool {
+            ++nt;
+            return accept_hit<KZ, ANYHIT>(R, A, B, Cc, tMax, best, rb0, rb1, rb2, rt);
+        };
+        constexpr int U = kTriUnroll;
+        static_assert(U % 2 == 0, "pass 1 walks fan pairs");
+        if (r.y <= 64) {
+            // pass 1: every triangle's tMax-independent rejections (scalar-cache batches); pass 2: the full
+            // test, in leaf order with the running tMax, on the survivors only — so the division and the
+            // error-bound tail run per candidate, not once per triangle for whichever lane reached it
+            uint64_t cand = 0;
+            int k = 0;
+            const uint64_t fp = sc.fan_pairs[set];  // bit k: leaf tiles k, k+1 share vertices (a,b,c),(a,c,d)
+            // conservative cluster boxes first: a cluster no lane of the wave reaches is skipped whole
+            // (closest hit: the box over [0, inf); any hit: over [0, tMax], exact for a fixed tMax).  Shadow rays
+            // and coherent closest-hit waves (shared dominant axis: camera rays) cull by wave ballot; incoherent
+            // closest-hit waves compact the passing (ray, cluster) pairs (culling every cluster: -2 %).
+            const float4* cl = sc.clusters[set];
+            const int ncl = sc.n_clusters[set];
+            // (shadow rays compacted too: Cornell -7 % in r01, -6.5 % in r04)
+            constexpr bool kCompact = !ANYHIT && KZ < 0;
+            constexpr bool kCull = ANYHIT || KZ >= 0 || kCompact;
+            const bool ncl_ok = ncl * kClusterTris >= r.y && ncl <= 32;  // the clusters cover the leaf
+            auto far1 = [&](V3 p) {  // the pad is not sized for rays starting this far out: no cluster is skipped
+                const float gx = p.x - sc.cl_guard.x, gy = p.y - sc.cl_guard.y, gz = p.z - sc.cl_guard.z;
+                return gx * gx + gy * gy + gz * gz > sc.cl_guard.w;
+            };
+            if (kCull && ncl_ok) {
+                const float cl_t = ANYHIT ? tMax : 3.402823466e+38f;
+                const bool far = far1(o);
+                if (ANYHIT && kClusterTris == 2) {
+                    // Shadow rays: each lane walks its own hit clusters, the tiles read from LDS (g_leaf1), so
+                    // the wave runs as many candidate steps as its busiest lane has hit clusters instead of one
+                    // per cluster any lane of the wave hit (Cornell bounce vertices: 0.75 hit clusters per shadow
+                    // ray, but most of the 18 hit by some lane; r06_ab2: shade stage -10 %, Cornell +4.5 %).
+                    // The candidate mask is exactly the per-cluster loop's, so pass 2 is unchanged.  Closest-hit
+                    // bounce rays keep the compacted pairs below (this loop measured trace +8 % for them).
+                    uint32_t hm = cluster_mask(cl, ncl, far, o, inv, cl_t);
+                    nt += cluster_tris(hm, ncl, r.y);
+                    while (hm) {
+                        const int c = __builtin_ctz(hm);
+                        hm &= hm - 1;
+                        cand |= (uint64_t)cluster_candidates<KZ>(R, tiles, r, c, fp) << (2 * c);
+                    }
+                    k = r.y;
+                } else if (kCompact && kClusterTris == 2 && ncl <= kCompactMaxClusters) {
+                    // Each lane box-tests every cluster against its own ray; the passing (lane, cluster) pairs
+                    // are appended to the wave's LDS list in cluster order (ballot + mbcnt), and the active
+                    // lanes then split the list evenly: lane j runs the candidate tests of pairs j, j + n, ...
+                    // on the pair's ray (staged in LDS) and ORs the result bits into that ray's mask.  The
+                    // per-(ray, triangle) test is unchanged, so the mask — and pass 2 — are exactly as before;
+                    // only the SIMD no longer runs tests for lanes whose box missed (Cornell bounce rays: 2.7
+                    // of 18 cluster boxes hit, but 17.7 of 18 hit by some lane of a wave).
+                    CompactWave& cw = g_cmp[threadIdx.x >> 6];
+                    const int ln = lane_id();
+                    const uint64_t act = __ballot(true);
+                    cw.ra[ln] = make_float4(R.Sx, R.Sy, R.Sz, R.ox);
+                    cw.rb[ln] = make_float4(R.oy, R.oz, __int_as_float(R.kz), 0.f);
+                    cw.cand[ln] = 0;
+                    int np = 0;
+                    const uint32_t hm = cluster_mask(cl, ncl, far, o, inv, cl_t);
+                    nt += cluster_tris(hm, ncl, r.y);  // executed tests: the hit clusters' (the reference: all)
+                    for (int c = 0; c < ncl; ++c) {
+                        const bool hb = (hm >> c) & 1u;
+                        uint64_t m = __ballot(hb);
+                        if (hb) cw.pair[np + mbcnt64(m)] = (unsigned short)(ln | (c << 6));
+                        np += __popcll(m);
+                    }
+                    wave_lds_sync();
+                    const int nact = __popcll(act);
+                    for (int p = mbcnt64(act); p < np; p += nact) {
+                        const unsigned v = cw.pair[p];
+                        const int L = v & 63, c = v >> 6;
+                        const float4 ra = cw.ra[L], rb = cw.rb[L];
+                        TriRay Q;
+                        Q.Sx = ra.x; Q.Sy = ra.y; Q.Sz = ra.z; Q.ox = ra.w; Q.oy = rb.x; Q.oz = rb.y;
+                        Q.kz = KZ >= 0 ? KZ : __float_as_int(rb.z);
+                        Q.kx = Q.kz + 1; if (Q.kx == 3) Q.kx = 0;
+                        Q.ky = Q.kx + 1; if (Q.ky == 3) Q.ky = 0;
+                        const unsigned bits = cluster_candidates<KZ>(Q, tiles, r, c, fp);
+                        if (bits) atomicOr(&cw.cand[L], (unsigned long long)bits << (2 * c));
+                    }
+                    wave_lds_sync();
+                    cand = cw.cand[ln];
+                    k = r.y;
+                } else {
+                const uint32_t hm = cluster_mask(cl, ncl, far, o, inv, cl_t);
+                nt += cluster_tris(hm, ncl, r.y);  // executed tests: the hit clusters' (the reference: all)
+                for (int c = 0; c < ncl; ++c) {
+                    const bool hb = (hm >> c) & 1u;
+                    if (__ballot(hb) == 0) continue;
+                    if (kClusterTris == 2 && ((fp >> (2 * c)) & 1)) {
+                        int e = 3 * (r.x + 2 * c);
+                        if (hb)
+                            cand |= (uint64_t)tri_candidate_pair<KZ>(R, ldc4(tiles, e), ldc4(tiles, e + 1),
+                                                                     ldc4(tiles, e + 2), ldc4(tiles, e + 4),
+                                                                     ldc4(tiles, e + 5)) << (2 * c);
+                        continue;
+                    }
+#pragma unroll
+                    for (int u = 0; u < kClusterTris; ++u) {
+                        int kk = c * kClusterTris + u;
+                        if (kk >= r.y) break;
+                        int e = 3 * (r.x + kk);
+                        if (hb && tri_candidate<KZ>(R, ldc4(tiles, e), ldc4(tiles, e + 1), ldc4(tiles, e + 2)))
+                            cand |= 1ull << kk;
+                    }
+                }
+                k = r.y;
+                }
+            }
+            nt += r.y - k;  // unculled: every triangle's candidate test runs
+            for (; k + U <= r.y; k += U) {
+                int e = 3 * (r.x + k);
+                float4 T[3 * U];
+#pragma unroll
+                for (int j = 0; j < 3 * U; ++j) T[j] = ldc4(tiles, e + j);
+#pragma unroll
+                for (int u = 0; u < U; u += 2) {
+                    if ((fp >> (k + u)) & 1) {  // wave-uniform: a scalar branch
+                        cand |= (uint64_t)tri_candidate_pair<KZ>(R, T[3 * u], T[3 * u + 1], T[3 * u + 2],
+                                                                 T[3 * u + 4], T[3 * u + 5]) << (k + u);
+                    } else {
+                        if (tri_candidate<KZ>(R, T[3 * u], T[3 * u + 1], T[3 * u + 2])) cand |= 1ull << (k + u);
+                        if (tri_candidate<KZ>(R, T[3 * u + 3], T[3 * u + 4], T[3 * u + 5]))
+                            cand |= 1ull << (k + u + 1);
+                    }
+                }
+            }
+            for (; k < r.y; ++k) {
+                int e = 3 * (r.x + k);
+                if (tri_candidate<KZ>(R, ldc4(tiles, e), ldc4(tiles, e + 1), ldc4(tiles, e + 2))) cand |= 1ull << k;
+            }
+            // Closest hit, nearest cluster first (the canonical rule of §6b on the single leaf).  The leaf-order
+            // pass below tests every candidate; here a lane tests the candidate cluster its ray enters first,
+            // then only the clusters entered within cut = t1 + 2 W(t1), and keeps the two smallest t.  If the
+            // runner-up lies beyond t1 + W(t1) the leaf-order pass must end on t1's triangle with the same
+            // (b, t): it is accepted robustly whatever hit came before it, and no later hit can be accepted.
+            // The skipped clusters' triangles lie beyond their padded boxes' entry, so beyond t1 + W.  Near
+            // ties (shared edges, coplanar faces) fall through to the exact leaf-order pass.
+            if (!ANYHIT && kClusterTris == 2 && cand && ncl_ok) {
+                const bool far_o = far1(o);
+                auto entry = [&](int c) {
+                    if (far_o) return 0.f;
+                    const float4 A = g_cl1[2 * c], B = g_cl1[2 * c + 1];
+                    const float x0 = (A.x - o.x) * inv.x, x1 = (B.x - o.x) * inv.x;
+                    const float y0 = (A.y - o.y) * inv.y, y1 = (B.y - o.y) * inv.y;
+                    const float z0 = (A.z - o.z) * inv.z, z1 = (B.z - o.z) * inv.z;
+                    return fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), 0.f));
+                };
+                float t1 = __builtin_inff(), t2 = __builtin_inff(), cut = __builtin_inff();
+                int w1 = -1;
+                float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+                auto test_cluster = [&](int c) {
+                    uint32_t bits = (uint32_t)(cand >> (2 * c)) & 3u;
+                    while (bits) {
+                        const int j = 2 * c + __builtin_ctz(bits);
+                        bits &= bits - 1;
+                        const float4* tp = RT_LEAF1(tiles, r.x, j);
+                        float b0, b1, b2, t;
+                        if (tri_intersect<KZ>(R, tMaxInit, tp[0], tp[1], tp[2], b0, b1, b2, t) && t < tMaxInit) {
+                            if (t < t1) {
+                                t2 = t1; t1 = t; w1 = j; c0 = b0; c1 = b1; c2 = b2;
+                                cut = t1 + 2.f * (t1 * 0x1p-16f + sc.wabs);
+                            } else if (t < t2) {
+                                t2 = t;
+                            }
+                        }
+                    }
+                };
+                uint64_t cm = (cand | (cand >> 1)) & 0x5555555555555555ull;  // bit 2c: cluster c has candidates
+                int cn = -1;
+                float en = __builtin_inff();
+                for (uint64_t m = cm; m; m &= m - 1) {
+                    const int c = __builtin_ctzll(m) >> 1;
+                    const float e = entry(c);
+                    if (e < en || cn < 0) { en = e; cn = c; }
+                }
+                test_cluster(cn);
+                cm &= ~(1ull << (2 * cn));
+                for (; cm; cm &= cm - 1) {
+                    const int c = __builtin_ctzll(cm) >> 1;
+                    if (!(entry(c) > cut)) test_cluster(c);
+                }
+                // decided.  (No hit at all: t1 = t2 = inf, inf <= inf, so such a ray is not decided here but
+                // takes the leaf-order pass, which rejects the same candidates again; an exact early-out
+                // `if (w1 < 0) return -1` measured no gain on the Cornell box, r07_ab2)
+                if (!(t2 <= t1 + (t1 * 0x1p-16f + sc.wabs))) {
+                    if (w1 >= 0) {
+                        rb0 = c0; rb1 = c1; rb2 = c2; rt = t1;
+                        return __float_as_int(RT_LEAF1(tiles, r.x, w1)[2].y);
+                    }
+                    return -1;
+                }
+            }
+            while (cand) {
+                int j = __builtin_ctzll(cand);
+                cand &= cand - 1;
+                const float4* tp = RT_LEAF1(tiles, r.x, j);
+                if (accept_hit<KZ, ANYHIT>(R, tp[0], tp[1], tp[2], tMax, best, rb0, rb1, rb2, rt)) return best;
+            }
+            return best;
+        }
+        int k = 0;
+        for (; k + U <= r.y; k += U) {
+            int e = 3 * (r.x + k);
+            float4 T[3 * U];
+#pragma unroll
+            for (int j = 0; j < 3 * U; ++j) T[j] = ldc4(tiles, e + j);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (test(T[3 * u], T[3 * u + 1], T[3 * u + 2])) return best;
+        }
+        for (; k < r.y; ++k) {
+            int e = 3 * (r.x + k);
+            if (test(ldc4(tiles, e), ldc4(tiles, e + 1), ldc4(tiles, e + 2))) return best;
+        }
+    }
+    return best;
+}
 // Octtree_Model.h:66-127 — FIFO BFS.  The 8 children of an internal node are contiguous, so the queue
 // holds one entry per child *group*; popping a group visits its 8 nodes in order, which reproduces the
 // reference's node-level FIFO order exactly.  tMax shrinks on every accepted hit ("t < tMax": the first
 // hit found in BFS order wins ties), so hit ids, barycentrics and t are bit-identical to the reference's.
-template <int QCAP, bool ANYHIT, int KZ, bool DFS = false>
-__device__ __forceinline__ int traverse(const DevScene& sc, int set, V3 o, V3 d, float tMaxInit, float& rb0, float& rb1,
+template <int QCAP, bool ANYHIT, int KZ, bool DFS>
+__device__ __forceinline__ int bfs_walk(const DevScene& sc, int set, V3 o, V3 d, float tMaxInit, float& rb0, float& rb1,
                                         float& rb2, float& rt, ctr_t& nn, ctr_t& nt) {
     V3 inv = v3(1 / d.x, 1 / d.y, 1 / d.z);
     TriRay R = make_triray<KZ>(o, d);
@@ -752,260 +1012,6 @@ __device__ __forceinline__ int traverse(const DevScene& sc, int set, V3 o, V3 d,
     int best = -1;
     const int2* __restrict__ lr = sc.leafRange[set];
     const float4* __restrict__ tiles = sc.tiles[set];
-    if constexpr (QCAP == 1) {
-        // The whole octree is one leaf (e.g. the 36-triangle Cornell box: 36 < TRIANGLE_CAPACITY): every
-        // lane walks the same triangle list, so it is read through the scalar cache into SGPRs once per
-        // wave; four triangles (12 x s_load_dwordx4) are fetched per scalar-cache round trip.
-        ++nn;
-        bool inside = box_hit(ldc4(sc.nodeA, 0), ldc4(sc.nodeB, 0), o, inv, tMax);
-        int2 r = ldc2i(lr, 0);
-        if (inside) {
-            auto test = [&](float4 A, float4 B, float4 Cc) -> bool {
-                ++nt;
-                float b0, b1, b2, t;
-                if (tri_intersect<KZ>(R, tMax, A, B, Cc, b0, b1, b2, t) && t < tMax) {
-                    best = __float_as_int(Cc.y);
-                    if (ANYHIT) return true;
-                    tMax = t; rb0 = b0; rb1 = b1; rb2 = b2; rt = t;
-                }
-                return false;
-            };
-            constexpr int U = kTriUnroll;
-            static_assert(U % 2 == 0, "pass 1 walks fan pairs");
-            if (r.y <= 64) {
-                // pass 1: every triangle's tMax-independent rejections (scalar-cache batches); pass 2: the full
-                // test, in leaf order with the running tMax, on the survivors only — so the division and the
-                // error-bound tail run per candidate, not once per triangle for whichever lane reached it
-                uint64_t cand = 0;
-                int k = 0;
-                const uint64_t fp = sc.fan_pairs[set];  // bit k: leaf tiles k, k+1 share vertices (a,b,c),(a,c,d)
-                // conservative cluster boxes first: a cluster no lane of the wave reaches is skipped whole
-                // (closest hit: the box over [0, inf); any hit: over [0, tMax], exact for a fixed tMax).  Shadow rays
-                // and coherent closest-hit waves (shared dominant axis: camera rays) cull by wave ballot; incoherent
-                // closest-hit waves compact the passing (ray, cluster) pairs (culling every cluster: -2 %).
-                const float4* cl = sc.clusters[set];
-                const int ncl = sc.n_clusters[set];
-                // (shadow rays compacted too: Cornell -7 % in r01, -6.5 % in r04)
-                constexpr bool kCompact = !ANYHIT && KZ < 0;
-                constexpr bool kCull = ANYHIT || KZ >= 0 || kCompact;
-                const bool ncl_ok = ncl * kClusterTris >= r.y && ncl <= 32;  // the clusters cover the leaf
-                auto far1 = [&](V3 p) {  // the pad is not sized for rays starting this far out: no cluster is skipped
-                    const float gx = p.x - sc.cl_guard.x, gy = p.y - sc.cl_guard.y, gz = p.z - sc.cl_guard.z;
-                    return gx * gx + gy * gy + gz * gz > sc.cl_guard.w;
-                };
-                if (kCull && ncl_ok) {
-                    const float cl_t = ANYHIT ? tMax : 3.402823466e+38f;
-                    const bool far = far1(o);
-                    if (ANYHIT && kClusterTris == 2) {
-                        // Shadow rays: each lane walks its own hit clusters, the tiles read from LDS (g_leaf1), so
-                        // the wave runs as many candidate steps as its busiest lane has hit clusters instead of one
-                        // per cluster any lane of the wave hit (Cornell bounce vertices: 0.75 hit clusters per shadow
-                        // ray, but most of the 18 hit by some lane; r06_ab2: shade stage -10 %, Cornell +4.5 %).
-                        // The candidate mask is exactly the per-cluster loop's, so pass 2 is unchanged.  Closest-hit
-                        // bounce rays keep the compacted pairs below (this loop measured trace +8 % for them).
-                        uint32_t hm = cluster_mask(cl, ncl, far, o, inv, cl_t);
-                        nt += cluster_tris(hm, ncl, r.y);
-                        while (hm) {
-                            const int c = __builtin_ctz(hm);
-                            hm &= hm - 1;
-                            const float4* tp = RT_LEAF1(tiles, r.x, 2 * c);
-                            unsigned bits;
-                            if ((fp >> (2 * c)) & 1) {
-                                bits = tri_candidate_pair<KZ>(R, tp[0], tp[1], tp[2], tp[4], tp[5]);
-                            } else {
-                                bits = tri_candidate<KZ>(R, tp[0], tp[1], tp[2]) ? 1u : 0u;
-                                if (2 * c + 1 < r.y && tri_candidate<KZ>(R, tp[3], tp[4], tp[5])) bits |= 2u;
-                            }
-                            cand |= (uint64_t)bits << (2 * c);
-                        }
-                        k = r.y;
-                    } else if (kCompact && kClusterTris == 2 && ncl <= kCompactMaxClusters) {
-                        // Each lane box-tests every cluster against its own ray; the passing (lane, cluster) pairs
-                        // are appended to the wave's LDS list in cluster order (ballot + mbcnt), and the active
-                        // lanes then split the list evenly: lane j runs the candidate tests of pairs j, j + n, ...
-                        // on the pair's ray (staged in LDS) and ORs the result bits into that ray's mask.  The
-                        // per-(ray, triangle) test is unchanged, so the mask — and pass 2 — are exactly as before;
-                        // only the SIMD no longer runs tests for lanes whose box missed (Cornell bounce rays: 2.7
-                        // of 18 cluster boxes hit, but 17.7 of 18 hit by some lane of a wave).
-                        CompactWave& cw = g_cmp[threadIdx.x >> 6];
-                        const int ln = lane_id();
-                        const uint64_t act = __ballot(true);
-                        cw.ra[ln] = make_float4(R.Sx, R.Sy, R.Sz, R.ox);
-                        cw.rb[ln] = make_float4(R.oy, R.oz, __int_as_float(R.kz), 0.f);
-                        cw.cand[ln] = 0;
-                        int np = 0;
-                        const uint32_t hm = cluster_mask(cl, ncl, far, o, inv, cl_t);
-                        nt += cluster_tris(hm, ncl, r.y);  // executed tests: the hit clusters' (the reference: all)
-                        for (int c = 0; c < ncl; ++c) {
-                            const bool hb = (hm >> c) & 1u;
-                            uint64_t m = __ballot(hb);
-                            if (hb) cw.pair[np + mbcnt64(m)] = (unsigned short)(ln | (c << 6));
-                            np += __popcll(m);
-                        }
-                        wave_lds_sync();
-                        const int nact = __popcll(act);
-                        for (int p = mbcnt64(act); p < np; p += nact) {
-                            const unsigned v = cw.pair[p];
-                            const int L = v & 63, c = v >> 6;
-                            const float4 ra = cw.ra[L], rb = cw.rb[L];
-                            TriRay Q;
-                            Q.Sx = ra.x; Q.Sy = ra.y; Q.Sz = ra.z; Q.ox = ra.w; Q.oy = rb.x; Q.oz = rb.y;
-                            Q.kz = KZ >= 0 ? KZ : __float_as_int(rb.z);
-                            Q.kx = Q.kz + 1; if (Q.kx == 3) Q.kx = 0;
-                            Q.ky = Q.kx + 1; if (Q.ky == 3) Q.ky = 0;
-                            const float4* tp = RT_LEAF1(tiles, r.x, 2 * c);
-                            unsigned bits;
-                            if ((fp >> (2 * c)) & 1) {
-                                bits = tri_candidate_pair<KZ>(Q, tp[0], tp[1], tp[2], tp[4], tp[5]);
-                            } else {
-                                bits = tri_candidate<KZ>(Q, tp[0], tp[1], tp[2]) ? 1u : 0u;
-                                if (2 * c + 1 < r.y && tri_candidate<KZ>(Q, tp[3], tp[4], tp[5])) bits |= 2u;
-                            }
-                            if (bits) atomicOr(&cw.cand[L], (unsigned long long)bits << (2 * c));
-                        }
-                        wave_lds_sync();
-                        cand = cw.cand[ln];
-                        k = r.y;
-                    } else {
-                    const uint32_t hm = cluster_mask(cl, ncl, far, o, inv, cl_t);
-                    nt += cluster_tris(hm, ncl, r.y);  // executed tests: the hit clusters' (the reference: all)
-                    for (int c = 0; c < ncl; ++c) {
-                        const bool hb = (hm >> c) & 1u;
-                        if (__ballot(hb) == 0) continue;
-                        if (kClusterTris == 2 && ((fp >> (2 * c)) & 1)) {
-                            int e = 3 * (r.x + 2 * c);
-                            if (hb)
-                                cand |= (uint64_t)tri_candidate_pair<KZ>(R, ldc4(tiles, e), ldc4(tiles, e + 1),
-                                                                         ldc4(tiles, e + 2), ldc4(tiles, e + 4),
-                                                                         ldc4(tiles, e + 5)) << (2 * c);
-                            continue;
-                        }
-#pragma unroll
-                        for (int u = 0; u < kClusterTris; ++u) {
-                            int kk = c * kClusterTris + u;
-                            if (kk >= r.y) break;
-                            int e = 3 * (r.x + kk);
-                            if (hb && tri_candidate<KZ>(R, ldc4(tiles, e), ldc4(tiles, e + 1), ldc4(tiles, e + 2)))
-                                cand |= 1ull << kk;
-                        }
-                    }
-                    k = r.y;
-                    }
-                }
-                nt += r.y - k;  // unculled: every triangle's candidate test runs
-                for (; k + U <= r.y; k += U) {
-                    int e = 3 * (r.x + k);
-                    float4 T[3 * U];
-#pragma unroll
-                    for (int j = 0; j < 3 * U; ++j) T[j] = ldc4(tiles, e + j);
-#pragma unroll
-                    for (int u = 0; u < U; u += 2) {
-                        if ((fp >> (k + u)) & 1) {  // wave-uniform: a scalar branch
-                            cand |= (uint64_t)tri_candidate_pair<KZ>(R, T[3 * u], T[3 * u + 1], T[3 * u + 2],
-                                                                     T[3 * u + 4], T[3 * u + 5]) << (k + u);
-                        } else {
-                            if (tri_candidate<KZ>(R, T[3 * u], T[3 * u + 1], T[3 * u + 2])) cand |= 1ull << (k + u);
-                            if (tri_candidate<KZ>(R, T[3 * u + 3], T[3 * u + 4], T[3 * u + 5]))
-                                cand |= 1ull << (k + u + 1);
-                        }
-                    }
-                }
-                for (; k < r.y; ++k) {
-                    int e = 3 * (r.x + k);
-                    if (tri_candidate<KZ>(R, ldc4(tiles, e), ldc4(tiles, e + 1), ldc4(tiles, e + 2))) cand |= 1ull << k;
-                }
-                // Closest hit, nearest cluster first (the canonical rule of §6b on the single leaf).  The leaf-order
-                // pass below tests every candidate; here a lane tests the candidate cluster its ray enters first,
-                // then only the clusters entered within cut = t1 + 2 W(t1), and keeps the two smallest t.  If the
-                // runner-up lies beyond t1 + W(t1) the leaf-order pass must end on t1's triangle with the same
-                // (b, t): it is accepted robustly whatever hit came before it, and no later hit can be accepted.
-                // The skipped clusters' triangles lie beyond their padded boxes' entry, so beyond t1 + W.  Near
-                // ties (shared edges, coplanar faces) fall through to the exact leaf-order pass.
-                if (!ANYHIT && kClusterTris == 2 && cand && ncl_ok) {
-                    const bool far_o = far1(o);
-                    auto entry = [&](int c) {
-                        if (far_o) return 0.f;
-                        const float4 A = g_cl1[2 * c], B = g_cl1[2 * c + 1];
-                        const float x0 = (A.x - o.x) * inv.x, x1 = (B.x - o.x) * inv.x;
-                        const float y0 = (A.y - o.y) * inv.y, y1 = (B.y - o.y) * inv.y;
-                        const float z0 = (A.z - o.z) * inv.z, z1 = (B.z - o.z) * inv.z;
-                        return fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), 0.f));
-                    };
-                    float t1 = __builtin_inff(), t2 = __builtin_inff(), cut = __builtin_inff();
-                    int w1 = -1;
-                    float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-                    auto test_cluster = [&](int c) {
-                        uint32_t bits = (uint32_t)(cand >> (2 * c)) & 3u;
-                        while (bits) {
-                            const int j = 2 * c + __builtin_ctz(bits);
-                            bits &= bits - 1;
-                            const float4* tp = RT_LEAF1(tiles, r.x, j);
-                            float b0, b1, b2, t;
-                            if (tri_intersect<KZ>(R, tMaxInit, tp[0], tp[1], tp[2], b0, b1, b2, t) && t < tMaxInit) {
-                                if (t < t1) {
-                                    t2 = t1; t1 = t; w1 = j; c0 = b0; c1 = b1; c2 = b2;
-                                    cut = t1 + 2.f * (t1 * 0x1p-16f + sc.wabs);
-                                } else if (t < t2) {
-                                    t2 = t;
-                                }
-                            }
-                        }
-                    };
-                    uint64_t cm = (cand | (cand >> 1)) & 0x5555555555555555ull;  // bit 2c: cluster c has candidates
-                    int cn = -1;
-                    float en = __builtin_inff();
-                    for (uint64_t m = cm; m; m &= m - 1) {
-                        const int c = __builtin_ctzll(m) >> 1;
-                        const float e = entry(c);
-                        if (e < en || cn < 0) { en = e; cn = c; }
-                    }
-                    test_cluster(cn);
-                    cm &= ~(1ull << (2 * cn));
-                    for (; cm; cm &= cm - 1) {
-                        const int c = __builtin_ctzll(cm) >> 1;
-                        if (!(entry(c) > cut)) test_cluster(c);
-                    }
-                    // decided.  (No hit at all: t1 = t2 = inf, inf <= inf, so such a ray is not decided here but
-                    // takes the leaf-order pass, which rejects the same candidates again; an exact early-out
-                    // `if (w1 < 0) return -1` measured no gain on the Cornell box, r07_ab2)
-                    if (!(t2 <= t1 + (t1 * 0x1p-16f + sc.wabs))) {
-                        if (w1 >= 0) {
-                            rb0 = c0; rb1 = c1; rb2 = c2; rt = t1;
-                            return __float_as_int(RT_LEAF1(tiles, r.x, w1)[2].y);
-                        }
-                        return -1;
-                    }
-                }
-                while (cand) {
-                    int j = __builtin_ctzll(cand);
-                    cand &= cand - 1;
-                    const float4* tp = RT_LEAF1(tiles, r.x, j);
-                    float b0, b1, b2, t;
-                    if (tri_intersect<KZ>(R, tMax, tp[0], tp[1], tp[2], b0, b1, b2, t) && t < tMax) {
-                        best = __float_as_int(tp[2].y);
-                        if (ANYHIT) return best;
-                        tMax = t; rb0 = b0; rb1 = b1; rb2 = b2; rt = t;
-                    }
-                }
-                return best;
-            }
-            int k = 0;
-            for (; k + U <= r.y; k += U) {
-                int e = 3 * (r.x + k);
-                float4 T[3 * U];
-#pragma unroll
-                for (int j = 0; j < 3 * U; ++j) T[j] = ldc4(tiles, e + j);
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (test(T[3 * u], T[3 * u + 1], T[3 * u + 2]) && ANYHIT) return best;
-            }
-            for (; k < r.y; ++k) {
-                int e = 3 * (r.x + k);
-                if (test(ldc4(tiles, e), ldc4(tiles, e + 1), ldc4(tiles, e + 2)) && ANYHIT) return best;
-            }
-        }
-        return best;
-    }
     if constexpr (ANYHIT && DFS) {
         if (sc.depth <= kDfsDepth)  // the upload's octree depth; deeper trees keep the BFS FIFO below
             return occluded_dfs<KZ>(sc, set, o, d, tMax, nn, nt) ? 0 : -1;  // any-hit: 0 = occluded
@@ -1124,12 +1130,7 @@ __device__ __forceinline__ int traverse(const DevScene& sc, int set, V3 o, V3 d,
                 A = tp[0]; B = tp[1]; Cc = tp[2];
             }
             ++nt;
-            float b0, b1, b2, t;
-            if (tri_intersect<KZ>(R, tMax, A, B, Cc, b0, b1, b2, t) && t < tMax) {
-                best = __float_as_int(Cc.y);
-                if (ANYHIT) return best;
-                tMax = t; rb0 = b0; rb1 = b1; rb2 = b2; rt = t;
-            }
+            if (accept_hit<KZ, ANYHIT>(R, A, B, Cc, tMax, best, rb0, rb1, rb2, rt)) return best;
         }
         lf += m;
         lc -= m;
@@ -1140,6 +1141,13 @@ __device__ __forceinline__ int traverse(const DevScene& sc, int set, V3 o, V3 d,
         pm &= keep;
     }
     return best;
+}
+// the name the callers use: the single-leaf walk or the multi-level group-FIFO BFS
+template <int QCAP, bool ANYHIT, int KZ, bool DFS = false>
+__device__ __forceinline__ int traverse(const DevScene& sc, int set, V3 o, V3 d, float tMaxInit, float& rb0, float& rb1,
+                                        float& rb2, float& rt, ctr_t& nn, ctr_t& nt) {
+    if constexpr (QCAP == 1) return leaf1_walk<ANYHIT, KZ>(sc, set, o, d, tMaxInit, rb0, rb1, rb2, rt, nn, nt);
+    else return bfs_walk<QCAP, ANYHIT, KZ, DFS>(sc, set, o, d, tMaxInit, rb0, rb1, rb2, rt, nn, nt);
 }
 
 // The reference BFS (Octtree_Model.h:66-127) for ONE ray, run by a whole wave (every lane holds the same ray; all 64
@@ -1212,10 +1220,7 @@ __device__ __forceinline__ bool bfs_coop(const DevScene& sc, int set, V3 o, V3 d
                     m &= m - 1;
                     const float4* tp = tiles + 3 * (lf + base + l);
                     const float4 A = tp[0], B = tp[1], Cc = tp[2];
-                    if (tri_intersect<-1>(R, tMax, A, B, Cc, b0, b1, b2, t) && t < tMax) {
-                        best = __float_as_int(Cc.y);
-                        tMax = t; rb0 = b0; rb1 = b1; rb2 = b2; rt = t;
-                    }
+                    accept_hit<-1, false>(R, A, B, Cc, tMax, best, rb0, rb1, rb2, rt);
                 }
             }
         }
@@ -1271,6 +1276,28 @@ __device__ __forceinline__ bool bfs_coop(const DevScene& sc, int set, V3 o, V3 d
     nn += cn;
     nt += ct;
     return ok;
+}
+// The wave resolves the lanes of `am` (the rays its own walks left undecided) one after the other: the lowest lane's
+// ray is broadcast, every lane runs bfs_coop on it, and the owning lane takes the answer with
+// done(prim, ok, nodes, tris) — closest hit: done(prim, ok, nodes, tris, b0, b1, b2, t).  Called by every lane that
+// formed `am`.  tMax is the lane's own for ANY; closest hit starts every ray from the same (wave-uniform) tMax.
+template <bool ANY, class Done>
+__device__ __forceinline__ void coop_resolve(const DevScene& sc, int set, uint64_t am, V3 o, V3 d, float tMax,
+                                             const CoopFifo& Q, Done&& done) {
+    while (am) {
+        const int L = __builtin_ctzll(am);
+        am &= am - 1;
+        const V3 oL = v3(__shfl(o.x, L), __shfl(o.y, L), __shfl(o.z, L));
+        const V3 dL = v3(__shfl(d.x, L), __shfl(d.y, L), __shfl(d.z, L));
+        int cp = -1;
+        float c0 = 0.f, c1 = 0.f, c2 = 0.f, ct = 0.f;  // (a miss stores zeros, as the BFS does; ANY: never written)
+        ctr_t cnn = 0, cnt = 0;
+        const bool ok = bfs_coop<ANY>(sc, set, oL, dL, ANY ? __shfl(tMax, L) : tMax, Q, cp, c0, c1, c2, ct, cnn, cnt);
+        if (lane_id() == L) {
+            if constexpr (ANY) done(cp, ok, cnn, cnt);
+            else done(cp, ok, cnn, cnt, c0, c1, c2, ct);
+        }
+    }
 }
 
 // ============================================================= fast multi-level traversal
@@ -1782,25 +1809,15 @@ __global__ void __launch_bounds__(kBlock) RT_WAVES_ATTR(QCAP) k_trace_closest(De
                 }
                 // (coop_ok == 0: the octree's BFS queue may exceed the FIFO, and the host launches k_trace_fallback:
                 // the ambiguous rays are listed for it directly)
-                uint64_t am = sc.coop_ok ? __ballot(live && amb) : 0ull;
-                while (am) {
-                    const int L = __builtin_ctzll(am);
-                    am &= am - 1;
-                    const V3 oL = v3(__shfl(o4.x, L), __shfl(o4.y, L), __shfl(o4.z, L));
-                    const V3 dL = v3(__shfl(d4.x, L), __shfl(d4.y, L), __shfl(d4.z, L));
-                    int cp = -1;
-                    float c0 = 0.f, c1 = 0.f, c2 = 0.f, ctt = 0.f;  // (a miss stores zeros, as the BFS does)
-                    ctr_t cnn = 0, cnt = 0;
-                    const bool ok = bfs_coop<false>(sc, io.set, oL, dL, 3.402823466e+38f, coop_fifo_bstk(), cp, c0, c1,
-                                                    c2, ctt, cnn, cnt);
-                    if (lane_id() == L) {
-                        ++nfb;
-                        nn += cnn;
-                        nt += cnt;
-                        if (ok) { prim = cp; b0 = c0; b1 = c1; b2 = c2; t = ctt; amb = false; }
-                        else ++novf;
-                    }
-                }
+                coop_resolve<false>(sc, io.set, sc.coop_ok ? __ballot(live && amb) : 0ull, v3(o4.x, o4.y, o4.z),
+                                    v3(d4.x, d4.y, d4.z), 3.402823466e+38f, coop_fifo_bstk(),
+                                    [&](int cp, bool ok, ctr_t cnn, ctr_t cnt, float c0, float c1, float c2, float ct) {
+                                        ++nfb;
+                                        nn += cnn;
+                                        nt += cnt;
+                                        if (ok) { prim = cp; b0 = c0; b1 = c1; b2 = c2; t = ct; amb = false; }
+                                        else ++novf;
+                                    });
                 if (live) {
                     if (amb) {  // (coop_ok == 0: k_trace_fallback's per-thread BFS decides the ray)
                         io.fb_pos[atomicAdd(io.fb_len, 1)] = p;
@@ -2117,6 +2134,32 @@ __device__ __forceinline__ bool cosine_bounce(float u0, float u1, V3 nrm, V3& wi
     return true;
 }
 
+// A shadow-queue record (ShadowQueueIO): the ray (origin, tMax), (direction, slot) and its pending contribution Ld.
+__device__ __forceinline__ void shadow_push(const ShadowQueueIO& shq, int pos, V3 so, V3 sd, float stmax, int slot,
+                                            const float Ld[8]) {
+    shq.shO[pos] = make_float4(so.x, so.y, so.z, stmax);
+    shq.shD[pos] = make_float4(sd.x, sd.y, sd.z, __int_as_float(slot));
+    shq.shLA[pos] = make_float4(Ld[0], Ld[1], Ld[2], Ld[3]);
+    shq.shLB[pos] = make_float4(Ld[4], Ld[5], Ld[6], Ld[7]);
+}
+__device__ __forceinline__ void shadow_ld(const ShadowQueueIO& shq, int k, float Ld[8]) {
+    load8(shq.shLA, shq.shLB, k, Ld);
+}
+// L += Ld on a slot's radiance (zero_first: lean depth 0, L starts as zero in registers)
+__device__ __forceinline__ void add_to_L(const RecView& rec, int slot, const float Ld[8], bool zero_first) {
+    float L[8];
+    rload8_or_zero(rec, slot, R_L, L, zero_first);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) L[i] += Ld[i];
+    rstore8(rec, slot, R_L, L);
+}
+// a bounce ray at position pos of the next queue: its origin carries its slot; multi-level scenes: its sort key
+__device__ __forceinline__ void push_bounce(const PathIO& io, int pos, float4 nO, float4 nD, int slot) {
+    nO.w = __int_as_float(slot);
+    io.nO[2 * pos] = nO; io.nD[2 * pos] = nD;
+    if (io.nkey.key) io.nkey.key[pos] = ray_sort_key(nO, nD, io.nkey);
+}
+
 // HQ (single leaf, PathIO hq_d): the items are the trace kernel's compacted hit records instead of queue positions.
 template <int QCAP, bool HQ = false>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCAP == 1 ? RT_SHADE1_WAVES : RT_SHADE_WAVES))) k_path_shade(DevScene sc, const DevSpectra* sp, DevSampler smp,
@@ -2284,15 +2327,11 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             } else {
                 int p0, p1;
                 block_append2(io.nCount, pend0, wantNext, lds, p0, p1);
-                if (pend0) {
+                if (pend0) {  // (the parked ray's origin holds the first item's slot)
                     const float4 o0 = pend[2 * threadIdx.x], d0v = pend[2 * threadIdx.x + 1];
-                    io.nO[2 * p0] = o0; io.nD[2 * p0] = d0v;
-                    if (io.nkey.key) io.nkey.key[p0] = ray_sort_key(o0, d0v, io.nkey);
+                    push_bounce(io, p0, o0, d0v, __float_as_int(o0.w));
                 }
-                if (wantNext) {
-                    io.nO[2 * p1] = nO; io.nD[2 * p1] = nD;
-                    if (io.nkey.key) io.nkey.key[p1] = ray_sort_key(nO, nD, io.nkey);
-                }
+                if (wantNext) push_bounce(io, p1, nO, nD, slot);
             }
         }
         if constexpr (QCAP != 1) {  // shadow queue: the ray and its pending contribution go to k_path_shadow
@@ -2301,10 +2340,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                               : block_append(shq.shCount + qj * kQStride, wantShadow, lds);
                 sp += qj * io.q.S;
                 if (wantShadow) {
-                    shq.shO[sp] = make_float4(so.x, so.y, so.z, stmax);
-                    shq.shD[sp] = make_float4(sd.x, sd.y, sd.z, __int_as_float(slot));
-                    shq.shLA[sp] = make_float4(Ld[0], Ld[1], Ld[2], Ld[3]);
-                    shq.shLB[sp] = make_float4(Ld[4], Ld[5], Ld[6], Ld[7]);
+                    shadow_push(shq, sp, so, sd, stmax, slot, Ld);
                     wantShadow = false;  // at depth 0 L is written as zero below; the shadow kernel adds to it
                 }
             }
@@ -2323,48 +2359,27 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
         if constexpr (QCAP != 1) {
             // the shadow rays the BVH could not decide: the wave resolves them one at a time with the cooperative
             // any-hit BFS (exact), so no k_path_shadow launch follows when the octree's queue bound fits its FIFO
-            if (shq.defer && sc.coop_ok) {
-                uint64_t am = __ballot(deferShadow);
-                while (am) {
-                    const int Ls = __builtin_ctzll(am);
-                    am &= am - 1;
-                    const V3 oL = v3(__shfl(so.x, Ls), __shfl(so.y, Ls), __shfl(so.z, Ls));
-                    const V3 dL = v3(__shfl(sd.x, Ls), __shfl(sd.y, Ls), __shfl(sd.z, Ls));
-                    int cp = -1;
-                    float c0, c1, c2, ct;
-                    ctr_t cnn = 0, cnt = 0;
-                    const bool ok =
-                        bfs_coop<true>(sc, 0, oL, dL, __shfl(stmax, Ls), coop_fifo_astk(), cp, c0, c1, c2, ct, cnn, cnt);
-                    if (lane_id() == Ls) {
-                        novf += !ok;  // (coop_ok: never; counted, C_COOPOVF)
-                        hit = cp;
-                        deferShadow = false;
-                        ++sfb;
-                        snn += cnn;
-                        snt += cnt;
-                    }
-                }
-            }
+            if (shq.defer && sc.coop_ok)
+                coop_resolve<true>(sc, 0, __ballot(deferShadow), so, sd, stmax, coop_fifo_astk(),
+                                   [&](int cp, bool ok, ctr_t cnn, ctr_t cnt) {
+                                       novf += !ok;  // (coop_ok: never; counted, C_COOPOVF)
+                                       hit = cp;
+                                       deferShadow = false;
+                                       ++sfb;
+                                       snn += cnn;
+                                       snt += cnt;
+                                   });
         }
         if (wantShadow && !deferShadow) {
             ++nsh;
             if (hit < 0) {
-                float L[8];
-                rload8_or_zero(io.rec, slot, R_L, L, d0);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) L[i] += Ld[i];
-                rstore8(io.rec, slot, R_L, L);
+                add_to_L(io.rec, slot, Ld, d0);
                 storedL = true;
             }
         }
         if constexpr (QCAP != 1) {
             const int sp = wave_append(shq.shCount + qj * kQStride, deferShadow) + qj * io.q.S;
-            if (deferShadow) {
-                shq.shO[sp] = make_float4(so.x, so.y, so.z, stmax);
-                shq.shD[sp] = make_float4(sd.x, sd.y, sd.z, __int_as_float(slot));
-                shq.shLA[sp] = make_float4(Ld[0], Ld[1], Ld[2], Ld[3]);
-                shq.shLB[sp] = make_float4(Ld[4], Ld[5], Ld[6], Ld[7]);
-            }
+            if (deferShadow) shadow_push(shq, sp, so, sd, stmax, slot, Ld);
         }
         if (d0 && slot >= 0 && !storedL) {
             const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -2372,11 +2387,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
         }
         if constexpr (QCAP == 1) continue;  // (its bounce ray was appended above)
         const int pn = queue_append<WAVE>(io.nCount + qj * kQStride, wantNext, lds) + qj * io.q.S;
-        if (wantNext) {
-            nO.w = __int_as_float(slot);  // the ray's origin carries its slot
-            io.nO[2 * pn] = nO; io.nD[2 * pn] = nD;
-            if (io.nkey.key) io.nkey.key[pn] = ray_sort_key(nO, nD, io.nkey);
-        }
+        if (wantNext) push_bounce(io, pn, nO, nD, slot);
     }
     count_add(ctr, C_SNODES, snn);
     count_add(ctr, C_STRIS, snt);
@@ -2403,69 +2414,37 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LEA
     WaveTickets tk(shq.shTicket, QueueView{shq.shCount, io.q.S, 0, io.q.ns});
     int qj, base;
     while (tk.next(qj, base)) {
-        if constexpr (LEAN && QCAP != 1) {
-            const bool live = base + lane_id() < tk.len;
-            const int k = qj * io.q.S + base + lane_id();
-            float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = o4;
-            int hit = -1;
-            bool amb = false;
-            if (live) {
-                o4 = shq.shO[k];
-                d4 = shq.shD[k];
-                float b0, b1, b2, t;
-                hit = traverse_bvh<true>(sc, 0, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), o4.w, b0, b1, b2, t, snn,
-                                         snt, amb);
-            }
-            uint64_t am = __ballot(live && amb);
-            while (am) {
-                const int Ls = __builtin_ctzll(am);
-                am &= am - 1;
-                const V3 oL = v3(__shfl(o4.x, Ls), __shfl(o4.y, Ls), __shfl(o4.z, Ls));
-                const V3 dL = v3(__shfl(d4.x, Ls), __shfl(d4.y, Ls), __shfl(d4.z, Ls));
-                int cp = -1;
-                float c0 = 0.f, c1 = 0.f, c2 = 0.f, ct = 0.f;  // (any hit: only the primitive is written)
-                ctr_t cnn = 0, cnt = 0;
-                const bool ok = bfs_coop<true>(sc, 0, oL, dL, __shfl(o4.w, Ls), coop_fifo_astk(), cp, c0, c1, c2, ct,
-                                               cnn, cnt);
-                if (lane_id() == Ls) {
-                    novf += !ok;  // (coop_ok: never; counted, C_COOPOVF)
-                    hit = cp;
-                    ++sfb;
-                    snn += cnn;
-                    snt += cnt;
-                }
-            }
-            if (live) {
-                ++nsh;
-                if (hit < 0) {
-                    const int slot = __float_as_int(d4.w);
-                    const float4 la = shq.shLA[k], lb = shq.shLB[k];
-                    const float Ld[8] = {la.x, la.y, la.z, la.w, lb.x, lb.y, lb.z, lb.w};
-                    float L[8];
-                    rload8(io.rec, slot, R_L, L);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) L[i] += Ld[i];
-                    rstore8(io.rec, slot, R_L, L);
-                }
-            }
-            continue;
-        }
-        if (base + lane_id() >= tk.len) continue;  // (reconverges at the loop latch, before the next ticket)
+        const bool live = base + lane_id() < tk.len;
         const int k = qj * io.q.S + base + lane_id();
-        float4 o4 = shq.shO[k], d4 = shq.shD[k];
+        float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = o4;
+        if (live) {
+            o4 = shq.shO[k];
+            d4 = shq.shD[k];
+        }
+        const V3 o = v3(o4.x, o4.y, o4.z), d = v3(d4.x, d4.y, d4.z);
         float b0, b1, b2, t;
-        int hit = traverse_any<QCAP, true, DFS>(sc, 0, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), o4.w, b0, b1, b2,
-                                                t, snn, snt, sfb);
-        ++nsh;
-        if (hit < 0) {
-            int slot = __float_as_int(d4.w);
-            float4 la = shq.shLA[k], lb = shq.shLB[k];
-            const float Ld[8] = {la.x, la.y, la.z, la.w, lb.x, lb.y, lb.z, lb.w};
-            float L[8];
-            rload8(io.rec, slot, R_L, L);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) L[i] += Ld[i];
-            rstore8(io.rec, slot, R_L, L);
+        int hit = -1;
+        if constexpr (LEAN && QCAP != 1) {
+            bool amb = false;
+            if (live) hit = traverse_bvh<true>(sc, 0, o, d, o4.w, b0, b1, b2, t, snn, snt, amb);
+            coop_resolve<true>(sc, 0, __ballot(live && amb), o, d, o4.w, coop_fifo_astk(),
+                               [&](int cp, bool ok, ctr_t cnn, ctr_t cnt) {
+                                   novf += !ok;  // (coop_ok: never; counted, C_COOPOVF)
+                                   hit = cp;
+                                   ++sfb;
+                                   snn += cnn;
+                                   snt += cnt;
+                               });
+        } else if (live) {
+            hit = traverse_any<QCAP, true, DFS>(sc, 0, o, d, o4.w, b0, b1, b2, t, snn, snt, sfb);
+        }
+        if (live) {
+            ++nsh;
+            if (hit < 0) {
+                float Ld[8];
+                shadow_ld(shq, k, Ld);
+                add_to_L(io.rec, __float_as_int(d4.w), Ld, false);
+            }
         }
     }
     count_add(ctr, C_SNODES, snn);
@@ -2480,11 +2459,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LEA
 // shapes, mirror and BK7/constant-eta glass (TerminateSecondary rewrites the sample's pdf), point / distant /
 // disk / quad lights (one sample each, shadow rays traced inline in light order), and MIS (power heuristic).
 // Semantics and sample-dimension order: oracle/rtcore.hpp LiPath, DESIGN.md §5.
-template <int QCAP>
-__device__ __forceinline__ bool scene_occluded(const DevScene& sc, V3 o, V3 d, float tmax, ctr_t& nn,
-                                               ctr_t& nt, ctr_t& nfb) {
-    float b0, b1, b2, t;
-    if (traverse_any<QCAP, true>(sc, 0, o, d, tmax, b0, b1, b2, t, nn, nt, nfb) >= 0) return true;
+// the analytic shapes' part of a shadow query (any hit within tmax)
+__device__ __forceinline__ bool shapes_occluded(const DevScene& sc, V3 o, V3 d, float tmax) {
     for (int si = 0; si < sc.n_shapes; ++si) {
         DevShape sh = ldconst(sc.shapes, si);
         V3 ph;
@@ -2492,6 +2468,13 @@ __device__ __forceinline__ bool scene_occluded(const DevScene& sc, V3 o, V3 d, f
         if (shape_isect(sh, o, d, tmax, ph, th)) return true;
     }
     return false;
+}
+template <int QCAP>
+__device__ __forceinline__ bool scene_occluded(const DevScene& sc, V3 o, V3 d, float tmax, ctr_t& nn,
+                                               ctr_t& nt, ctr_t& nfb) {
+    float b0, b1, b2, t;
+    if (traverse_any<QCAP, true>(sc, 0, o, d, tmax, b0, b1, b2, t, nn, nt, nfb) >= 0) return true;
+    return shapes_occluded(sc, o, d, tmax);
 }
 
 // parity entry: the shadow query of the path kernels on explicit rays (d.w = tmax)
@@ -2792,11 +2775,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             }
         }
         const int pn = queue_append<WAVE>(io.nCount + qj * kQStride, wantNext, lds) + qj * io.q.S;
-        if (wantNext) {
-            nO.w = __int_as_float(slot);  // the ray's origin carries its slot
-            io.nO[2 * pn] = nO; io.nD[2 * pn] = nD;
-            if (io.nkey.key) io.nkey.key[pn] = ray_sort_key(nO, nD, io.nkey);
-        }
+        if (wantNext) push_bounce(io, pn, nO, nD, slot);
     }
 }
 
@@ -2804,15 +2783,6 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
 // tMax, then the analytic shapes: scene_occluded), then L += ((x (Le D65(λ))) wgt) for the visible lights in the
 // same order — the inline loop's arithmetic term for term.  Only the shadow rays and L are live here.
 // scene_occluded over the BVH alone (multi-level octrees): amb = the canonical rule could not decide
-__device__ __forceinline__ bool shapes_occluded(const DevScene& sc, V3 o, V3 d, float tmax) {
-    for (int si = 0; si < sc.n_shapes; ++si) {
-        DevShape sh = ldconst(sc.shapes, si);
-        V3 ph;
-        float th;
-        if (shape_isect(sh, o, d, tmax, ph, th)) return true;
-    }
-    return false;
-}
 __device__ __forceinline__ bool scene_occluded_bvh(const DevScene& sc, V3 o, V3 d, float tmax, ctr_t& nn, ctr_t& nt,
                                                    bool& amb) {
     float b0, b1, b2, t;
@@ -2840,24 +2810,15 @@ __global__ void __launch_bounds__(kBlock) k_occluded_path(DevScene sc, int n, co
             d4 = d[k];
             occ = scene_occluded_bvh(sc, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), d4.w, nn, nt, amb);
         }
-        uint64_t am = __ballot(live && amb);
-        while (am) {
-            const int Ls = __builtin_ctzll(am);
-            am &= am - 1;
-            const V3 oL = v3(__shfl(o4.x, Ls), __shfl(o4.y, Ls), __shfl(o4.z, Ls));
-            const V3 dL = v3(__shfl(d4.x, Ls), __shfl(d4.y, Ls), __shfl(d4.z, Ls));
-            int cp = -1;
-            float c0 = 0.f, c1 = 0.f, c2 = 0.f, ct = 0.f;
-            ctr_t cnn = 0, cnt = 0;
-            const bool ok = bfs_coop<true>(sc, 0, oL, dL, __shfl(d4.w, Ls), coop_fifo_astk(), cp, c0, c1, c2, ct, cnn, cnt);
-            if (lane_id() == Ls) {
-                novf += !ok;
-                occ = cp >= 0 || shapes_occluded(sc, oL, dL, d4.w);
-                ++nfb;
-                nn += cnn;
-                nt += cnt;
-            }
-        }
+        const V3 ro = v3(o4.x, o4.y, o4.z), rd = v3(d4.x, d4.y, d4.z);
+        coop_resolve<true>(sc, 0, __ballot(live && amb), ro, rd, d4.w, coop_fifo_astk(),
+                           [&](int cp, bool ok, ctr_t cnn, ctr_t cnt) {
+                               novf += !ok;
+                               occ = cp >= 0 || shapes_occluded(sc, ro, rd, d4.w);
+                               ++nfb;
+                               nn += cnn;
+                               nt += cnt;
+                           });
         if (live) {
             out[k] = occ ? 1 : 0;
             ++ns;
@@ -2922,28 +2883,17 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                 else occ = scene_occluded<QCAP>(sc, po, lr.wi, lr.tmax, snn, snt, sfb);
             }
             if constexpr (COOP) {
-                if (sc.coop_ok) {
-                    uint64_t am = __ballot(amb);
-                    while (am) {
-                        const int Ls = __builtin_ctzll(am);
-                        am &= am - 1;
-                        const V3 oL = v3(__shfl(po.x, Ls), __shfl(po.y, Ls), __shfl(po.z, Ls));
-                        const V3 dL = v3(__shfl(lr.wi.x, Ls), __shfl(lr.wi.y, Ls), __shfl(lr.wi.z, Ls));
-                        int cp = -1;
-                        float c0, c1, c2, ct;
-                        ctr_t cnn = 0, cnt = 0;
-                        const bool ok = bfs_coop<true>(sc, 0, oL, dL, __shfl(lr.tmax, Ls), coop_fifo_astk(), cp, c0,
-                                                       c1, c2, ct, cnn, cnt);
-                        if (lane_id() == Ls) {  // the octree's answer, then the analytic shapes (scene_occluded_bvh)
-                            novf += !ok;        // (coop_ok: never; counted, C_COOPOVF)
-                            occ = cp >= 0 || shapes_occluded(sc, po, lr.wi, lr.tmax);
-                            amb = false;
-                            ++sfb;
-                            snn += cnn;
-                            snt += cnt;
-                        }
-                    }
-                }
+                if (sc.coop_ok)
+                    coop_resolve<true>(sc, 0, __ballot(amb), po, lr.wi, lr.tmax, coop_fifo_astk(),
+                                       [&](int cp, bool ok, ctr_t cnn, ctr_t cnt) {
+                                           // the octree's answer, then the analytic shapes (scene_occluded_bvh)
+                                           novf += !ok;  // (coop_ok: never; counted, C_COOPOVF)
+                                           occ = cp >= 0 || shapes_occluded(sc, po, lr.wi, lr.tmax);
+                                           amb = false;
+                                           ++sfb;
+                                           snn += cnn;
+                                           snt += cnt;
+                                       });
                 if (amb) defer = true;  // (coop_ok == 0: the vertex goes to k_path_nee<Q, true>)
             }
             if (act && !defer && !occ) vis |= 1ull << li;
@@ -3165,6 +3115,17 @@ static int resident_grid(F kern, int gb, int grid) {
     return gb;
 }
 
+// One launch of a persistent kernel: the grid clamped to the kernel's resident block count.
+template <class K, class... A>
+static hipError_t launch_resident(K kern, int gb, int grid, hipStream_t st, A&&... a) {
+    hipLaunchKernelGGL(kern, dim3(resident_grid(kern, gb, grid)), dim3(kBlock), 0, st, std::forward<A>(a)...);
+    return hipGetLastError();
+}
+// QCAP == 0 (the FIFO spills to the HBM ring): one ring per resident thread
+static inline int ring_clamp(int gb, int qcap, const DevScene& sc) {
+    return qcap == 0 ? std::min(gb, sc.ring_threads / kBlock) : gb;
+}
+
 hipError_t launch_emitter_filter(hipStream_t st, int grid, const DevScene& sc, const EmitIO& io) {
     if (sc.n_emit_tris < 0 || sc.n_emit_tris > kMaxEmitTris) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_emitter_filter, dim3(grid_for(io.q.n ? io.q.n : grid * kBlock, grid)), dim3(kBlock), 0, st,
@@ -3180,49 +3141,35 @@ hipError_t launch_generate(hipStream_t st, int grid, int nS, const SampleIds& id
 
 hipError_t launch_trace_closest(hipStream_t st, int grid, int qcap, const DevScene& sc, const TraceIO& io,
                                 unsigned long long* ctr) {
-    int gb = grid_for(io.q.len ? grid * kBlock : io.q.n, grid);
-    if (qcap == 0) gb = std::min(gb, sc.ring_threads / kBlock);  // one ring per resident thread
-    dim3 b(kBlock);
+    const int gb = ring_clamp(grid_for(io.q.len ? grid * kBlock : io.q.n, grid), qcap, sc);
     const bool fbl = io.fb_pos != nullptr;
     if (fbl && (!io.fb_len || qcap == 1)) return hipErrorInvalidValue;
-#define RT_TRACE_CASE(Q)                                                                                          \
-    case Q:                                                                                                       \
-        if (fbl)                                                                                                  \
-            hipLaunchKernelGGL((k_trace_closest<Q, true>), dim3(resident_grid(k_trace_closest<Q, true>, gb, grid)), b, \
-                               0, st, sc, io, ctr);                                                               \
-        else                                                                                                      \
-            hipLaunchKernelGGL((k_trace_closest<Q, false>), dim3(resident_grid(k_trace_closest<Q, false>, gb, grid)), \
-                               b, 0, st, sc, io, ctr);                                                            \
-        break;
+    void (*k)(DevScene, TraceIO, unsigned long long*);
     switch (qcap) {
-        RT_TRACE_CASE(0)
+        case 0: k = fbl ? k_trace_closest<0, true> : k_trace_closest<0, false>; break;
         case 1:
             if (io.hq_len) {  // compacted hits: static chunks of a one-shard queue only
                 if (io.ticket || io.q.ns != 1 || !io.hq_d) return hipErrorInvalidValue;
-                hipLaunchKernelGGL((k_trace_closest<1, false, true>), dim3(resident_grid(k_trace_closest<1, false, true>, gb, grid)), b, 0, st, sc, io, ctr);
+                k = k_trace_closest<1, false, true>;
             } else {
-                hipLaunchKernelGGL((k_trace_closest<1, false>), dim3(resident_grid(k_trace_closest<1, false>, gb, grid)), b, 0, st, sc, io, ctr);
+                k = k_trace_closest<1, false>;
             }
             break;
-        RT_TRACE_CASE(16)
+        case 16: k = fbl ? k_trace_closest<16, true> : k_trace_closest<16, false>; break;
         default: return hipErrorInvalidValue;
     }
-#undef RT_TRACE_CASE
-    return hipGetLastError();
+    return launch_resident(k, gb, grid, st, sc, io, ctr);
 }
 
 hipError_t launch_trace_fallback(hipStream_t st, int grid, int qcap, const DevScene& sc, const TraceIO& io,
                                  unsigned long long* ctr) {
     if (!io.fb_pos || !io.fb_len) return hipErrorInvalidValue;
-    int gb = std::min(grid > 0 ? grid : 1, kFallbackBlocks);
-    if (qcap == 0) gb = std::min(gb, sc.ring_threads / kBlock);  // one ring per resident thread
-    dim3 b(kBlock);
+    const int gb = ring_clamp(std::min(grid > 0 ? grid : 1, kFallbackBlocks), qcap, sc);
     switch (qcap) {
-        case 0: hipLaunchKernelGGL(k_trace_fallback<0>, dim3(resident_grid(k_trace_fallback<0>, gb, grid)), b, 0, st, sc, io, ctr); break;
-        case 16: hipLaunchKernelGGL(k_trace_fallback<16>, dim3(resident_grid(k_trace_fallback<16>, gb, grid)), b, 0, st, sc, io, ctr); break;
+        case 0: return launch_resident(k_trace_fallback<0>, gb, grid, st, sc, io, ctr);
+        case 16: return launch_resident(k_trace_fallback<16>, gb, grid, st, sc, io, ctr);
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_ref_shade_film(hipStream_t st, int grid, const DevScene& sc, const DevSpectra* sp, const DevFilm& film,
@@ -3245,98 +3192,69 @@ hipError_t launch_path_shadow(hipStream_t st, int grid, int qcap, bool dfs, cons
                               const ShadowQueueIO& shq, unsigned long long* ctr) {
     int gb = grid > 0 ? grid : 1;
     if (shq.defer) gb = std::min(gb, kFallbackBlocks);
-    if (qcap == 0) gb = std::min(gb, sc.ring_threads / kBlock);  // one ring per resident thread
-    dim3 b(kBlock);
-#define RT_SHADOW_CASE(Q)                                                                                        \
-    case Q:                                                                                                      \
-        if (!shq.defer && sc.coop_ok)                                                                            \
-            hipLaunchKernelGGL((k_path_shadow<Q, false, true>), dim3(resident_grid(k_path_shadow<Q, false, true>, gb, grid)), \
-                               b, 0, st, sc, io, shq, ctr);                                                           \
-        else if (dfs)                                                                                            \
-            hipLaunchKernelGGL((k_path_shadow<Q, true>), dim3(resident_grid(k_path_shadow<Q, true>, gb, grid)), b, \
-                               0, st, sc, io, shq, ctr);                                                              \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_path_shadow<Q, false>), dim3(resident_grid(k_path_shadow<Q, false>, gb, grid)), \
-                               b, 0, st, sc, io, shq, ctr);                                                           \
-        break;
+    gb = ring_clamp(gb, qcap, sc);
+    const int v = !shq.defer && sc.coop_ok ? 2 : dfs ? 1 : 0;  // LEAN, DFS, BFS
+    void (*k)(DevScene, PathIO, ShadowQueueIO, unsigned long long*);
     switch (qcap) {
-        RT_SHADOW_CASE(0)
-        RT_SHADOW_CASE(16)
+        case 0: k = v == 2 ? k_path_shadow<0, false, true> : v == 1 ? k_path_shadow<0, true> : k_path_shadow<0, false>; break;
+        case 16: k = v == 2 ? k_path_shadow<16, false, true> : v == 1 ? k_path_shadow<16, true> : k_path_shadow<16, false>; break;
         default: return hipErrorInvalidValue;
     }
-#undef RT_SHADOW_CASE
-    return hipGetLastError();
+    return launch_resident(k, gb, grid, st, sc, io, shq, ctr);
 }
 
 hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,
                              const DevSampler& smp, const DevFilm& film, const SampleIds& ids, const PathIO& io,
                              unsigned long long* ctr, const ShadowQueueIO& shq, const NeeIO& nee, int matclass) {
-    int gb = grid > 0 ? grid : 1;
-    if (qcap == 0) gb = std::min(gb, sc.ring_threads / kBlock);  // one ring per resident thread
-    dim3 b(kBlock);
+    const int gb = ring_clamp(grid > 0 ? grid : 1, qcap, sc);
     if (sc.full && sc.n_lights > 0 && !nee.rec) return hipErrorInvalidValue;  // NEE records are required
     if (!sc.full && qcap != 1 && !shq.shO) return hipErrorInvalidValue;       // so is the shadow queue
-#define RT_SHADE_CASE(Q)                                                                                         \
-    case Q:                                                                                                      \
-        if (sc.full && Q != 1 && matclass == 1)                                                                 \
-            hipLaunchKernelGGL((k_path_shade_full<Q, 1>), dim3(resident_grid(k_path_shade_full<Q, 1>, gb, grid)), b, 0, \
-                               st, sc, sp, smp, film, ids, io, nee);                                             \
-        else if (sc.full && Q != 1 && matclass == 2)                                                            \
-            hipLaunchKernelGGL((k_path_shade_full<Q, 2>), dim3(resident_grid(k_path_shade_full<Q, 2>, gb, grid)), b, 0, \
-                               st, sc, sp, smp, film, ids, io, nee);                                             \
-        else if (sc.full)                                                                                        \
-            hipLaunchKernelGGL((k_path_shade_full<Q, 0>), dim3(resident_grid(k_path_shade_full<Q, 0>, gb, grid)), b, 0, \
-                               st, sc, sp, smp, film, ids, io, nee);                                             \
-        else if (Q == 1 && io.hq_d)                                                                              \
-            hipLaunchKernelGGL((k_path_shade<1, true>), dim3(resident_grid(k_path_shade<1, true>, gb, grid)), b, 0, \
-                               st, sc, sp, smp, film, ids, io, ctr, shq);                                        \
-        else                                                                                                     \
-            hipLaunchKernelGGL(k_path_shade<Q>, dim3(resident_grid(k_path_shade<Q>, gb, grid)), b, 0, st, sc, sp,  \
-                               smp, film, ids, io, ctr, shq);                                                    \
-        break;
+    if (sc.full) {  // (the material bins exist on multi-level scenes only: a single leaf shades every material)
+        void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, NeeIO);
+        switch (qcap) {
+            case 0: k = matclass == 1 ? k_path_shade_full<0, 1> : matclass == 2 ? k_path_shade_full<0, 2> : k_path_shade_full<0, 0>; break;
+            case 1: k = k_path_shade_full<1, 0>; break;
+            case 16: k = matclass == 1 ? k_path_shade_full<16, 1> : matclass == 2 ? k_path_shade_full<16, 2> : k_path_shade_full<16, 0>; break;
+            default: return hipErrorInvalidValue;
+        }
+        return launch_resident(k, gb, grid, st, sc, sp, smp, film, ids, io, nee);
+    }
+    void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, unsigned long long*, ShadowQueueIO);
     switch (qcap) {
-        RT_SHADE_CASE(0)
-        RT_SHADE_CASE(1)
-        RT_SHADE_CASE(16)
+        case 0: k = k_path_shade<0>; break;
+        case 1: k = io.hq_d ? k_path_shade<1, true> : k_path_shade<1>; break;
+        case 16: k = k_path_shade<16>; break;
         default: return hipErrorInvalidValue;
     }
-#undef RT_SHADE_CASE
-    return hipGetLastError();
+    return launch_resident(k, gb, grid, st, sc, sp, smp, film, ids, io, ctr, shq);
 }
 
 hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,
                            const PathIO& io, const NeeIO& nee, unsigned long long* ctr) {
-    int gb = grid > 0 ? grid : 1;
-    if (qcap == 0) gb = std::min(gb, sc.ring_threads / kBlock);  // one ring per resident thread
-    dim3 b(kBlock);
+    const int gb = ring_clamp(grid > 0 ? grid : 1, qcap, sc);
     if (qcap != 1 && (!nee.fb_slot || !nee.fb_len)) return hipErrorInvalidValue;  // the fallback list is required
     switch (qcap) {
-        case 0: hipLaunchKernelGGL((k_path_nee<0, false>), dim3(resident_grid(k_path_nee<0, false>, gb, grid)), b, 0, st, sc, sp, io, nee, ctr); break;
-        case 1: hipLaunchKernelGGL((k_path_nee<1, false>), dim3(resident_grid(k_path_nee<1, false>, gb, grid)), b, 0, st, sc, sp, io, nee, ctr); break;
-        case 16: hipLaunchKernelGGL((k_path_nee<16, false>), dim3(resident_grid(k_path_nee<16, false>, gb, grid)), b, 0, st, sc, sp, io, nee, ctr); break;
+        case 0: return launch_resident(k_path_nee<0, false>, gb, grid, st, sc, sp, io, nee, ctr);
+        case 1: return launch_resident(k_path_nee<1, false>, gb, grid, st, sc, sp, io, nee, ctr);
+        case 16: return launch_resident(k_path_nee<16, false>, gb, grid, st, sc, sp, io, nee, ctr);
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 // the vertices k_path_nee listed (multi-level octrees only; a resident grid, the list's length read on the device)
 hipError_t launch_path_nee_fallback(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,
                                     const PathIO& io, const NeeIO& nee, unsigned long long* ctr) {
-    int gb = std::min(grid > 0 ? grid : 1, kFallbackBlocks);
-    if (qcap == 0) gb = std::min(gb, sc.ring_threads / kBlock);  // one ring per resident thread
-    dim3 b(kBlock);
+    const int gb = ring_clamp(std::min(grid > 0 ? grid : 1, kFallbackBlocks), qcap, sc);
     switch (qcap) {
-        case 0: hipLaunchKernelGGL((k_path_nee<0, true>), dim3(resident_grid(k_path_nee<0, true>, gb, grid)), b, 0, st, sc, sp, io, nee, ctr); break;
-        case 16: hipLaunchKernelGGL((k_path_nee<16, true>), dim3(resident_grid(k_path_nee<16, true>, gb, grid)), b, 0, st, sc, sp, io, nee, ctr); break;
+        case 0: return launch_resident(k_path_nee<0, true>, gb, grid, st, sc, sp, io, nee, ctr);
+        case 16: return launch_resident(k_path_nee<16, true>, gb, grid, st, sc, sp, io, nee, ctr);
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_occluded(hipStream_t st, int qcap, const DevScene& sc, int n, const float4* o, const float4* d,
                            int* out, unsigned long long* ctr, bool path) {
-    int gb = grid_for(n, 0);
-    if (qcap == 0) gb = std::min(gb, sc.ring_threads / kBlock);
+    const int gb = ring_clamp(grid_for(n, 0), qcap, sc);
     dim3 g(gb > 0 ? gb : 1), b(kBlock);
     if (path && qcap != 1) {
         if (!sc.coop_ok) return hipErrorInvalidValue;
@@ -3356,11 +3274,8 @@ hipError_t launch_occluded(hipStream_t st, int qcap, const DevScene& sc, int n, 
 
 hipError_t launch_path_film(hipStream_t st, int grid, const DevSpectra* sp, const DevFilm& film, const PathFilmIO& io,
                             unsigned long long* ctr) {
-    if (io.mom)
-        hipLaunchKernelGGL(k_path_film<true>, dim3(resident_grid(k_path_film<true>, grid_for(io.n_pixels, grid), grid)), dim3(kBlock), 0, st, sp, film, io, ctr);
-    else
-        hipLaunchKernelGGL(k_path_film<false>, dim3(resident_grid(k_path_film<false>, grid_for(io.n_pixels, grid), grid)), dim3(kBlock), 0, st, sp, film, io, ctr);
-    return hipGetLastError();
+    return launch_resident(io.mom ? k_path_film<true> : k_path_film<false>, grid_for(io.n_pixels, grid), grid, st, sp,
+                           film, io, ctr);
 }
 
 hipError_t launch_resolve(hipStream_t st, int n, const float4* film, const float* a, const float* b, unsigned char* out,
@@ -3380,9 +3295,7 @@ hipError_t launch_film_scatter(hipStream_t st, int n, const int* work, const flo
 }
 
 hipError_t launch_bin_materials(hipStream_t st, int grid, const DevScene& sc, const BinIO& io) {
-    hipLaunchKernelGGL(k_bin_materials, dim3(resident_grid(k_bin_materials, grid, grid)), dim3(kBlock), 0, st, sc, io);
-    return hipGetLastError();
+    return launch_resident(k_bin_materials, grid, grid, st, sc, io);
 }
-
 
 }  // namespace rtmi
