@@ -28,6 +28,7 @@ RT_INTEGRATOR_REFERENCE, RT_INTEGRATOR_PATH, RT_INTEGRATOR_PATH_MIS = 0, 1, 2
 ABI_VERSION = 10
 RT_MAX_DEVICES = 16
 RT_CHAIN_MAX = 4
+RT_CHAIN_CURVED = 0x100
 QUEUE_SHARDS = 8  # RT_QUEUE_SHARDS
 
 F16 = C.c_float * 16

@@ -14,8 +14,13 @@
 // global arrays that only a reflection writes and only the chain's end reads.  The state has to outlive a kernel
 // launch per level, so it cannot stay in LDS or registers; a chain without a reflection touches none of it.
 //
+// k_chain_level<true> (RT_CHAIN_CURVED) replaces the chain's length D = sum of the segments by the curvature-aware
+// virtual distance: a continuing item also writes one record (c_c, c_f, mu, kappa) and its segment length to per-slot
+// global arrays, and the chain's end carries the image distance backwards over them (chain_curved_distance).
+// k_chain_level<false> is the kernel without any of it.
+//
 // Everything is float32 in the order written (the build's -ffp-contract=off), so a numpy float32 restatement gives
-// the same bits (tests/chain_reference.py).
+// the same bits (tests/chain_reference.py; with the flag and on analytic shapes tests/chain_curved_reference.py).
 #include "rt_device.h"
 #include "rt_internal.h"
 
@@ -49,6 +54,43 @@ RT_DEV int q_len(const QueueView& q, int j) {
     return c < 0 ? 0 : (c > q.S ? q.S : c);
 }
 
+// The curvature-aware virtual distance of a chain of K continuation surfaces that ends after a segment of length tK
+// (DESIGN.md §3e "curved"): the surfaces' records, last first, carry the tangential and the sagittal image distance
+// back to surface 0.  Dsum: the plain sum, returned for a chain of planar reflections and when an image is not virtual.
+RT_DEV float chain_curved_distance(const ChainIO& io, int slot, int K, float tK, float Dsum) {
+    const float4 L = io.seg[slot];  // t_0 .. t_3
+    float sT = 0.f, sS = 0.f, tn = tK;
+    bool flat = true, ok = true;
+    for (int k = K - 1; k >= 0; --k) {
+        const float4 r = io.rec[k][slot];  // (c_c, c_f, mu, kappa)
+        const float uT = tn + sT, uS = tn + sS;
+        if (r.z == 0.f && r.w == 0.f) {
+            sT = uT;
+            sS = uS;
+        } else {
+            flat = false;
+            float aT, aS;
+            if (r.z == 0.f) {
+                const float k2 = 2.0f * r.w;
+                aT = 1.0f / uT + k2 / r.x;
+                aS = 1.0f / uS + k2 * r.x;
+            } else {
+                const float gk = (r.x - r.z * r.y) * r.w;
+                aT = (((r.z * r.y) * r.y) / uT + gk) / (r.x * r.x);
+                aS = r.z / uS + gk;
+            }
+            if (!(aT > 0.f) || !(aS > 0.f)) ok = false;
+            sT = 1.0f / aT;
+            sS = 1.0f / aS;
+        }
+        tn = k == 3 ? L.w : (k == 2 ? L.z : (k == 1 ? L.y : L.x));  // t_k
+    }
+    if (flat || !ok) return Dsum;
+    const float DT = tn + sT, DS = tn + sS;
+    return ((2.0f * DT) * DS) / (DT + DS);
+}
+
+template <bool CURVED>
 __global__ void __launch_bounds__(kBlock) k_chain_level(DevScene sc, ChainIO io) {
     // 64-item chunks of the shards (a shard stride is a multiple of 64), chunk c = shard c / cps: a wave's items are
     // of one shard, so its continuations take one append on that shard's length
@@ -78,6 +120,7 @@ __global__ void __launch_bounds__(kBlock) k_chain_level(DevScene sc, ChainIO io)
                 // ---- surface (k_path_shade_full)
                 V3 pt, nrm, nout;
                 int mid;
+                float kap = 0.f;  // (CURVED) the surface's signed curvature
                 if (prim < sc.n_tris) {
                     const V3 p0 = xyz(sc.triWorld[3 * prim]), p1 = xyz(sc.triWorld[3 * prim + 1]),
                              p2 = xyz(sc.triWorld[3 * prim + 2]);
@@ -99,6 +142,10 @@ __global__ void __launch_bounds__(kBlock) k_chain_level(DevScene sc, ChainIO io)
                     nrm = nw;
                     nout = flip ? v3(-nw.x, -nw.y, -nw.z) : nw;
                     mid = s.material;
+                    if constexpr (CURVED) {
+                        const float km = io.kappa[prim - sc.n_tris];
+                        kap = flip ? -km : km;
+                    }
                 }
                 const DevMaterial mt = sc.materials[mid];
                 // the emitter check comes first, as in the shade kernel
@@ -106,6 +153,7 @@ __global__ void __launch_bounds__(kBlock) k_chain_level(DevScene sc, ChainIO io)
                     const float off = 1e-4f * (1.0f + max3f(fabsf(pt.x), fabsf(pt.y), fabsf(pt.z)));
                     bool refl = mt.type == 1;
                     V3 po, wi;
+                    float4 rec = make_float4(-vdot(rayd, nrm), 0.f, 0.f, kap);
                     if (!refl) {  // smooth dielectric: the refraction whenever it exists (no sampler draw)
                         const float eta = mt.eta != 0 ? mt.eta : io.eta_bk7;
                         V3 wt;
@@ -113,6 +161,10 @@ __global__ void __launch_bounds__(kBlock) k_chain_level(DevScene sc, ChainIO io)
                         if (refract_dir(v3(-rayd.x, -rayd.y, -rayd.z), nout, eta, etap, wt)) {
                             po = vsub(pt, vmul(nrm, off));
                             wi = wt;
+                            if constexpr (CURVED) {
+                                rec.y = -vdot(wt, nrm);
+                                rec.z = etap;
+                            }
                         } else {
                             refl = true;
                         }
@@ -124,6 +176,10 @@ __global__ void __launch_bounds__(kBlock) k_chain_level(DevScene sc, ChainIO io)
                         dst[slot] = make_float4(nrm.x, nrm.y, nrm.z, 0.f);
                         m += 1;
                     }
+                    if constexpr (CURVED) {  // surface `level` of the chain (level < depth <= kChainMax)
+                        io.rec[io.level][slot] = rec;
+                        reinterpret_cast<float*>(io.seg)[4 * (size_t)slot + io.level] = hb.w;
+                    }
                     go = true;
                     nO = make_float4(po.x, po.y, po.z, __int_as_float(slot | (m << kChainSlotBits)));
                     nD = make_float4(wi.x, wi.y, wi.z, D);
@@ -133,7 +189,11 @@ __global__ void __launch_bounds__(kBlock) k_chain_level(DevScene sc, ChainIO io)
                     if (m > 2) v = reflect_dir(v, xyz(io.n[2][slot]));
                     if (m > 1) v = reflect_dir(v, xyz(io.n[1][slot]));
                     if (m > 0) v = reflect_dir(v, xyz(io.n[0][slot]));
-                    io.res[slot] = make_float4(v.x, v.y, v.z, D);
+                    float Dv = D;
+                    if constexpr (CURVED) {
+                        if (io.level > 0) Dv = chain_curved_distance(io, slot, io.level, hb.w, D);
+                    }
+                    io.res[slot] = make_float4(v.x, v.y, v.z, Dv);
                 }
             }
         }
@@ -183,7 +243,13 @@ hipError_t launch_chain_level(hipStream_t st, int grid, const DevScene& sc, cons
     const long long chunks = io.q.len ? (long long)io.q.ns * (io.q.S >> 6) : ((long long)io.q.n + 63) / 64 + io.q.ns;
     long long gb = (chunks * 64 + kBlock - 1) / kBlock;
     if (grid > 0 && gb > grid) gb = grid;
-    hipLaunchKernelGGL(k_chain_level, dim3((unsigned)(gb < 1 ? 1 : gb)), dim3(kBlock), 0, st, sc, io);
+    const dim3 g((unsigned)(gb < 1 ? 1 : gb)), blk(kBlock);
+    if (io.curved) {
+        if (!io.kappa || !io.seg || !io.rec[0] || !io.rec[1] || !io.rec[2] || !io.rec[3]) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_chain_level<true>, g, blk, 0, st, sc, io);
+    } else {
+        hipLaunchKernelGGL(k_chain_level<false>, g, blk, 0, st, sc, io);
+    }
     return hipGetLastError();
 }
 

@@ -481,6 +481,8 @@ struct Batch {
     NeeSlots nee;                          // neeSlot's regions for the current queue capacity
     // specular-chain guides: two ping-pong queues of continuation rays, interleaved pairs like ray
     DevBuf<float4> chainRay;
+    // RT_CHAIN_CURVED: kChainMax surface records and one float4 of segment lengths per sample slot, array after array
+    DevBuf<float4> chainRec;
 
     float4* rayO() const { return ray.get(); }
     float4* rayD() const { return ray.get() + 1; }
@@ -610,6 +612,7 @@ struct rt_ctx {
     bool scene_full = false;   // the scene needs the general path-shade kernel
     DevScene dsc{};
     std::vector<DevBuf<unsigned char>> scene_allocs;  // the arrays dsc points to
+    const float* d_kappa = nullptr;  // per analytic shape: the curvature the curved chain guides use (in scene_allocs)
     // spectra + resolve matrices
     HostSpectra hs;
     DevBuf<DevSpectra> d_spec;
@@ -722,6 +725,7 @@ int fail(rt_ctx* c, int code, const std::string& msg) {
 void free_scene(rt_ctx* c) {
     c->scene_allocs.clear();
     c->dsc = DevScene{};
+    c->d_kappa = nullptr;
     c->have_scene = false;
 }
 
@@ -2038,12 +2042,33 @@ struct ShadingArrays {
     std::vector<int> tm;            // material per triangle
     std::vector<DevMaterial> mats;
     std::vector<DevShape> shapes;
+    std::vector<float> kappa;       // per shape: shape_curvature
     std::vector<DevLight> lights;
     // the emissive surfaces, for the last depth's emitter filter (EmitIO): non-degenerate triangles and shapes whose
     // material emits
     std::vector<int> etris, eshapes;
     bool full = false;              // the scene needs the general path-shade kernel
 };
+// The curvature magnitude the curved chain guides give a shape: 1 / (radius sigma) for a sphere whose
+// object_to_render linear part L is a rotation times a uniform scale sigma, 0 for every other shape.  In float64:
+// G = L^T L, sigma^2 = tr G / 3, uniform iff max |G - sigma^2 I| <= 1e-5 sigma^2; the result is rounded to float.
+static float shape_curvature(const rt_shape& h) {
+    if (h.type != RT_SHAPE_SPHERE) return 0.f;
+    double G[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double g = 0;  // columns i and j of the column-major matrix
+            for (int r = 0; r < 3; ++r) g += (double)h.object_to_render[4 * i + r] * (double)h.object_to_render[4 * j + r];
+            G[i][j] = g;
+        }
+    const double s2 = (G[0][0] + G[1][1] + G[2][2]) / 3.0;
+    double dev = 0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) dev = std::max(dev, std::fabs(G[i][j] - (i == j ? s2 : 0.0)));
+    if (!(s2 > 0) || !(dev <= 1e-5 * s2)) return 0.f;
+    const double rs = (double)h.radius * std::sqrt(s2);
+    return rs > 0 ? (float)(1.0 / rs) : 0.f;
+}
 static void shading_arrays(const rt_scene_desc* s, const SceneWorld& sw, ShadingArrays& a) {
     const int nt = s->n_triangles;
     a.tw.resize(3 * (size_t)nt); a.tn.resize(3 * (size_t)nt);
@@ -2079,6 +2104,7 @@ static void shading_arrays(const rt_scene_desc* s, const SceneWorld& sw, Shading
         std::memcpy(d.n2r, h.normal_to_render, 36);
         std::memcpy(d.p1, h.p, 12); std::memcpy(d.p2, h.p + 3, 12); std::memcpy(d.p3, h.p + 6, 12);
         shape_bound(d);
+        a.kappa.push_back(shape_curvature(h));
     }
     a.lights.resize(s->n_lights);
     bool full = s->n_shapes > 0 || s->n_lights != 1;
@@ -2179,7 +2205,8 @@ static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, 
         (rc = upload_array(c, f.tiles[0], d.tiles[0])) || (rc = upload_array(c, f.tiles[1], d.tiles[1])) ||
         (rc = upload_array(c, a.tw, d.triWorld)) || (rc = upload_array(c, a.tn, d.triNormal)) ||
         (rc = upload_array(c, a.tm, d.triMaterial)) || (rc = upload_array(c, a.mats, d.materials)) ||
-        (rc = upload_array(c, a.shapes, d.shapes)) || (rc = upload_array(c, a.lights, d.lights)))
+        (rc = upload_array(c, a.shapes, d.shapes)) || (rc = upload_array(c, a.lights, d.lights)) ||
+        (rc = upload_array(c, a.kappa, c->d_kappa)))
         return rc;
     if (qcap == 1) {
         d.cl_guard = cl.guard;
@@ -2618,8 +2645,14 @@ static int impl_rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, c
 // ---- denoiser: the feature pass reuses the reference-mode workspace and the generate / trace kernels;
 // the filter runs on device arrays (an adaptive session's own, or staged copies of the caller's host arrays).
 namespace {
+// chain_depth as the public calls take it: d or d | RT_CHAIN_CURVED with d in 0..RT_CHAIN_MAX
+bool chain_depth_valid(int chain_depth) {
+    const int d = chain_depth & ~RT_CHAIN_CURVED;
+    return d >= 0 && d <= kChainMax;
+}
 int chain_check_depth(rt_ctx* c, int chain_depth) {
-    if (chain_depth < 0 || chain_depth > kChainMax) return fail(c, RT_E_ARG, "chain_depth must be 0..RT_CHAIN_MAX");
+    if (!chain_depth_valid(chain_depth))
+        return fail(c, RT_E_ARG, "chain_depth must be 0..RT_CHAIN_MAX, optionally | RT_CHAIN_CURVED");
     return RT_OK;
 }
 
@@ -2632,9 +2665,11 @@ int chain_check_depth(rt_ctx* c, int chain_depth) {
 // k_chain_film.  The chain's per-slot state uses the reference workspace's wavelength and pdf arrays, which k_generate
 // fills and the feature pass never reads.
 int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, float4* pos = nullptr,
-                    int chain_depth = 0) {
+                    int chain_arg = 0) {
     int rc;
-    if ((rc = chain_check_depth(c, chain_depth))) return rc;
+    if ((rc = chain_check_depth(c, chain_arg))) return rc;
+    const int chain_depth = chain_arg & ~RT_CHAIN_CURVED;
+    const bool curved = (chain_arg & RT_CHAIN_CURVED) != 0;  // (without effect at depth 0)
     if (ib < 0 || ie < ib) return fail(c, RT_E_ARG, "invalid index range");
     if ((rc = ensure_sobol(c))) return rc;
     DevSampler smp = dev_sampler(c);
@@ -2663,6 +2698,7 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
     if (chain) {
         if (ncap > ((size_t)1 << kChainSlotBits)) return fail(c, RT_E_LIMIT, "chain pass: more than 2^28 samples per batch");
         HIPCHK(c, w.b.chainRay.reserve(4 * ncap));
+        if (curved) HIPCHK(c, w.b.chainRec.reserve((size_t)(kChainMax + 1) * ncap));
         HIPCHK(c, w.chain_ctr.reserve((size_t)(kChainMax + 1) * kQRegion));
         if (dyn) HIPCHK(c, w.tfb.reserve(ncap));
         eta_bk7 = c->hs.BK7.query(550.f);
@@ -2695,6 +2731,12 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
         cio.eta_bk7 = eta_bk7;
         cio.n[0] = b.lamB.get(); cio.n[1] = b.pdfA.get(); cio.n[2] = b.pdfB.get();
         cio.res = b.lamA.get();
+        if (curved) {
+            cio.curved = 1;
+            cio.kappa = c->d_kappa;
+            for (int k = 0; k < kChainMax; ++k) cio.rec[k] = b.chainRec.get() + (size_t)k * ncap;
+            cio.seg = b.chainRec.get() + (size_t)kChainMax * ncap;
+        }
         const int S = shard_stride(nS, nsh);
         for (int level = 0; level <= chain_depth; ++level) {
             int* const reg = level > 0 ? ctr + (size_t)(level - 1) * kQRegion : nullptr;  // this level's queue
@@ -2733,8 +2775,8 @@ int denoise_check_desc(rt_ctx* c, const rt_denoise_desc* d) {
         return fail(c, RT_E_ARG, "denoise: sigma_l and sigma_z must be finite and > 0");
     if (!std::isfinite(d->lum_floor) || d->lum_floor < 0 || !std::isfinite(d->depth_floor) || d->depth_floor < 0)
         return fail(c, RT_E_ARG, "denoise: lum_floor and depth_floor must be finite and >= 0");
-    if (d->chain_depth < 0 || d->chain_depth > kChainMax)
-        return fail(c, RT_E_ARG, "denoise: chain_depth must be 0..RT_CHAIN_MAX");
+    if (!chain_depth_valid(d->chain_depth))
+        return fail(c, RT_E_ARG, "denoise: chain_depth must be 0..RT_CHAIN_MAX, optionally | RT_CHAIN_CURVED");
     return RT_OK;
 }
 
@@ -2889,8 +2931,8 @@ int temporal_check_desc(rt_ctx* c, const rt_temporal_desc* d) {
     if (!std::isfinite(d->plane_rel) || d->plane_rel < 0) return fail(c, RT_E_ARG, "temporal: plane_rel must be finite and >= 0");
     if (!(d->max_history >= 1.f)) return fail(c, RT_E_ARG, "temporal: max_history must be at least 1");
     if (d->feature_samples < 1) return fail(c, RT_E_ARG, "temporal: feature_samples must be at least 1");
-    if (d->chain_depth < 0 || d->chain_depth > kChainMax)
-        return fail(c, RT_E_ARG, "temporal: chain_depth must be 0..RT_CHAIN_MAX");
+    if (!chain_depth_valid(d->chain_depth))
+        return fail(c, RT_E_ARG, "temporal: chain_depth must be 0..RT_CHAIN_MAX, optionally | RT_CHAIN_CURVED");
     return RT_OK;
 }
 

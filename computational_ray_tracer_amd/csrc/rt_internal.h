@@ -567,7 +567,16 @@ struct ChainIO {
     float4* res;
     float4* nray;                 // the next level's queue (same shard stride), lengths at nlen + j kQStride (zeroed)
     int* nlen;
+    // curved != 0 (RT_CHAIN_CURVED, DESIGN.md §3e "curved"): the curvature-aware virtual distance.  Per sample slot and
+    // continuation surface k < kChainMax a record rec[k] = (c_c, c_f, mu, kappa), mu = 0 for a reflection, and the
+    // length t_k of the segment that reached the surface in component k of seg; only a chain that continues writes
+    // them, only its end reads them.  kappa: per analytic shape the curvature magnitude (0: planar), set at upload.
+    int curved;
+    const float* kappa;
+    float4* rec[4];
+    float4* seg;
 };
+static_assert(kChainMax == 4, "ChainIO::rec and the components of ChainIO::seg hold kChainMax entries");
 hipError_t launch_chain_level(hipStream_t st, int grid, const DevScene& sc, const ChainIO& io);
 // Per owned pixel, in increasing index order: feat += res[s] and, when pos is set, pos += (o0 + D d0, 1), for the
 // samples s = i * n_pixels + j whose chain ended in a hit; (o0, d0) at ray[2s], ray[2s + 1].

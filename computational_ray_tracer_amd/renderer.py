@@ -18,6 +18,14 @@ TEMPORAL_DEFAULTS = dict(normal_min=0.9, plane_rel=0.01, max_history=512.0, feat
 # chain_depth of rt_denoise_desc and rt_temporal_desc: 0 = first-surface guides.  Accepted next to the
 # fields above by every call that takes them; kept apart because the two dicts above are pinned to the numpy references'.
 CHAIN_DEFAULTS = dict(chain_depth=0)
+# chain_curved (same calls): True sets capi.RT_CHAIN_CURVED in the descriptor's chain_depth, the curvature-aware
+# virtual distance of DESIGN.md §3e.  Opt-in; kept out of CHAIN_DEFAULTS, which is pinned to the ABI's one field.
+CHAIN_CURVED_DEFAULT = False
+
+
+def chain_arg(chain_depth, chain_curved=CHAIN_CURVED_DEFAULT):
+    """The chain_depth value of the C ABI: the depth, with capi.RT_CHAIN_CURVED set when chain_curved."""
+    return int(chain_depth) | (capi.RT_CHAIN_CURVED if chain_curved else 0)
 
 
 class Renderer:
@@ -152,7 +160,7 @@ class Renderer:
     # ---- denoiser (rt_render_features, rt_denoise, rt_adaptive_denoise) ------------------------
     @staticmethod
     def _denoise_desc(**kw):
-        unknown = set(kw) - set(DENOISE_DEFAULTS) - set(CHAIN_DEFAULTS)
+        unknown = set(kw) - set(DENOISE_DEFAULTS) - set(CHAIN_DEFAULTS) - {"chain_curved"}
         if unknown:
             raise TypeError(f"unknown denoise parameters: {sorted(unknown)}")
         p = {**DENOISE_DEFAULTS, **CHAIN_DEFAULTS, **kw}
@@ -161,7 +169,7 @@ class Renderer:
         d.normal_power_log2 = int(p["normal_power_log2"])
         d.sigma_l, d.sigma_z = float(p["sigma_l"]), float(p["sigma_z"])
         d.lum_floor, d.depth_floor = float(p["lum_floor"]), float(p["depth_floor"])
-        d.chain_depth = int(p["chain_depth"])
+        d.chain_depth = chain_arg(p["chain_depth"], p.get("chain_curved", CHAIN_CURVED_DEFAULT))
         return d
 
     def render_features(self, index_begin, index_end, feat=None):
@@ -216,14 +224,14 @@ class Renderer:
     # ---- temporal accumulation (rt_render_features_pos, rt_temporal_*) -------------------------
     @staticmethod
     def _temporal_desc(**kw):
-        unknown = set(kw) - set(TEMPORAL_DEFAULTS) - set(CHAIN_DEFAULTS)
+        unknown = set(kw) - set(TEMPORAL_DEFAULTS) - set(CHAIN_DEFAULTS) - {"chain_curved"}
         if unknown:
             raise TypeError(f"unknown temporal parameters: {sorted(unknown)}")
         p = {**TEMPORAL_DEFAULTS, **CHAIN_DEFAULTS, **kw}
         d = capi.rt_temporal_desc()
         d.normal_min, d.plane_rel, d.max_history = float(p["normal_min"]), float(p["plane_rel"]), float(p["max_history"])
         d.feature_samples = int(p["feature_samples"])
-        d.chain_depth = int(p["chain_depth"])
+        d.chain_depth = chain_arg(p["chain_depth"], p.get("chain_curved", CHAIN_CURVED_DEFAULT))
         return d
 
     @staticmethod
@@ -244,17 +252,19 @@ class Renderer:
             pos.ctypes.data_as(C.POINTER(capi.rt_position))))
         return feat, pos
 
-    def render_features_chain(self, index_begin, index_end, chain_depth, feat=None, pos=None, with_pos=True):
+    def render_features_chain(self, index_begin, index_end, chain_depth, feat=None, pos=None, with_pos=True,
+                              chain_curved=CHAIN_CURVED_DEFAULT):
         """rt_render_features_chain: render_features_pos whose samples follow mirrors and dielectrics for up to
         chain_depth continuation rays (0..capi.RT_CHAIN_MAX) and describe the end of that chain.
-        Returns (feat, pos); with_pos=False: the feature film alone (pos_inout NULL), returns feat."""
+        Returns (feat, pos); with_pos=False: the feature film alone (pos_inout NULL), returns feat.
+        chain_curved=True: the curvature-aware virtual distance (capi.RT_CHAIN_CURVED)."""
         feat = self.new_film() if feat is None else feat
         if with_pos:
             pos = self.new_film() if pos is None else pos
         for a in (feat, pos) if with_pos else (feat,):
             assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (self.res[0] * self.res[1], 4)
         self._chk("rt_render_features_chain", self.lib.rt_render_features_chain(
-            self.h, index_begin, index_end, int(chain_depth), feat.ctypes.data_as(C.POINTER(capi.rt_feature)),
+            self.h, index_begin, index_end, chain_arg(chain_depth, chain_curved), feat.ctypes.data_as(C.POINTER(capi.rt_feature)),
             pos.ctypes.data_as(C.POINTER(capi.rt_position)) if with_pos else None))
         return (feat, pos) if with_pos else feat
 

@@ -330,7 +330,7 @@ typedef struct {
     float sigma_l, sigma_z; /* > 0, finite                                            */
     float lum_floor;        /* >= 0, finite; added to sigma_l*sqrt(var)               */
     float depth_floor;      /* >= 0, finite; times z_p, added to the depth denominator */
-    int chain_depth;        /* 0..RT_CHAIN_MAX: the sessions render their guides with rt_render_features_chain */
+    int chain_depth;        /* 0..RT_CHAIN_MAX [| RT_CHAIN_CURVED]: the sessions' guides, rt_render_features_chain */
 } rt_denoise_desc;          /* 32 B */
 /* Filter host arrays of any res_x x res_y (film, mom, feat, out: res_x*res_y each; variance_out: res_x*res_y floats
  * or NULL): out = (filtered mean * film.w, film.w), so both resolves apply.  The context supplies the device, the
@@ -363,8 +363,27 @@ int rt_render_features_pos(rt_ctx* ctx, int index_begin, int index_end, rt_featu
  *   pos += (o0 + D d0, 1): the virtual point on the camera ray, exact for planar mirrors.
  * chain_depth 0, or the reference integrator (no materials: every chain has length 0), gives rt_render_features_pos'
  * films bit for bit.  Batches, shards, sessions, rt_stats (continuation rays count as rays) and RT_E_STATE on
- * multi-device contexts as rt_render_features. */
+ * multi-device contexts as rt_render_features.
+ *
+ * chain_depth | RT_CHAIN_CURVED (here and in rt_denoise_desc.chain_depth and rt_temporal_desc.chain_depth; any other
+ * value outside 0..RT_CHAIN_MAX is RT_E_ARG; 0 | RT_CHAIN_CURVED behaves as 0): the curvature-aware virtual distance.
+ * Everything above is unchanged except the D of feat and pos.  Each continuation surface k = 0..K-1 records
+ * c_c = -(d.n), for a refraction c_f = -(wt.n) and mu = the far side's index over the camera side's (mu = 0 marks a
+ * reflection), and the signed curvature kappa: +-1 / (radius sigma) for a sphere whose object_to_render linear part
+ * is a rotation times a uniform scale sigma (decided in float64 at upload: G = L^T L, sigma^2 = tr G / 3,
+ * max |G - sigma^2 I| <= 1e-5 sigma^2; rounded to float), + hit from outside, - from inside; 0 for every other
+ * surface.  With t_k the length of the segment that reached surface k and t_K the last segment's, the chain's end
+ * goes backwards from k = K-1 to 0 with s_T = s_S = 0, per plane u = t_(k+1) + s:
+ *   reflection, kappa == 0:  s = u
+ *   reflection:   a_T = 1 / u_T + (2 kappa) / c_c                              a_S = 1 / u_S + (2 kappa) c_c
+ *   refraction:   a_T = (((mu c_f) c_f) / u_T + (c_c - mu c_f) kappa) / (c_c c_c)   a_S = mu / u_S + (c_c - mu c_f) kappa
+ *   s = 1 / a
+ * then D_T = t_0 + s_T, D_S = t_0 + s_S and D = ((2 D_T) D_S) / (D_T + D_S).  A sample keeps the plain sum D when
+ * every record is a reflection with kappa == 0 (bit for bit the films without the flag) or when some a is not > 0 (the
+ * image is real, at infinity, or NaN: inside a concave mirror).  The tangential and the sagittal plane are taken as
+ * aligned along the chain: exact for one sphere, an approximation across several objects. */
 #define RT_CHAIN_MAX 4
+#define RT_CHAIN_CURVED 0x100
 int rt_render_features_chain(rt_ctx* ctx, int index_begin, int index_end, int chain_depth, rt_feature* feat_inout,
                              rt_position* pos_inout);
 /* Reprojection of the previous frame's accumulated film and moments through the previous camera, rejection of taps
@@ -374,7 +393,7 @@ typedef struct {
     float plane_rel;        /* >= 0, finite: and |n_p.(P_q - P)| <= plane_rel * depth                        */
     float max_history;      /* >= 1: cap of the accumulated sample count n'                                  */
     int feature_samples;    /* k >= 1: indices accumulated in the feature and position films                 */
-    int chain_depth;        /* 0..RT_CHAIN_MAX: the frames render their guides with rt_render_features_chain */
+    int chain_depth;        /* 0..RT_CHAIN_MAX [| RT_CHAIN_CURVED]: the frames' guides, rt_render_features_chain */
     int reserved[3];
 } rt_temporal_desc;         /* 32 B */
 typedef struct {
