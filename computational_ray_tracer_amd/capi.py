@@ -29,6 +29,7 @@ ABI_VERSION = 10
 RT_MAX_DEVICES = 16
 RT_CHAIN_MAX = 4
 RT_CHAIN_CURVED = 0x100
+RT_TEX_CLAMP, RT_TEX_REPEAT = 0, 1
 QUEUE_SHARDS = 8  # RT_QUEUE_SHARDS
 
 F16 = C.c_float * 16
@@ -155,6 +156,17 @@ class rt_mesh(C.Structure):
                 ("texcoords", C.POINTER(C.c_float)), ("n_triangles", C.c_int), ("indices", C.POINTER(C.c_uint32))]
 
 
+class rt_texture(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("wrap", C.c_int), ("rgb", C.POINTER(C.c_uint8))]
+
+
+class rt_texture_desc(C.Structure):
+    _fields_ = [("n_textures", C.c_int), ("textures", C.POINTER(rt_texture)),
+                ("n_materials", C.c_int), ("material_texture", C.POINTER(C.c_int32)),
+                ("n_triangles", C.c_int), ("tri_texcoords", C.POINTER(C.c_float)),
+                ("reserved", C.c_int * 4)]
+
+
 class rt_octree_info(C.Structure):
     _fields_ = [("n_nodes", C.c_int), ("n_leaf_refs", C.c_int), ("max_queue_groups", C.c_int), ("depth", C.c_int),
                 ("bvh_nodes", C.c_int), ("bvh_depth", C.c_int)]
@@ -176,6 +188,7 @@ EXPORTS = [
     "rt_temporal_end",
     "rt_render_features_chain",
     "rt_temporal_frame_guided", "rt_temporal_block_error",
+    "rt_scene_set_textures", "rt_texel_index", "rt_debug_texture_bake", "rt_debug_texture_eval",
 ]
 
 _lib = None
@@ -273,6 +286,10 @@ def load_library(path=None):
                                      P(rt_feature), P(rt_position), P(C.c_float), P(C.c_float), P(C.c_int32)], C.c_int),
         "rt_temporal_reset": ([C.c_void_p], C.c_int),
         "rt_temporal_end": ([C.c_void_p], C.c_int),
+        "rt_scene_set_textures": ([C.c_void_p, P(rt_texture_desc)], C.c_int),
+        "rt_texel_index": ([C.c_int, C.c_int, C.c_int, C.c_float, C.c_float], C.c_int),
+        "rt_debug_texture_bake": ([C.c_void_p, C.c_int, P(C.c_uint8), P(C.c_float)], C.c_int),
+        "rt_debug_texture_eval": ([C.c_void_p, C.c_int, P(C.c_int32), P(C.c_float), P(C.c_int32), P(C.c_float)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

@@ -22,6 +22,7 @@
 
 #include "rt_guard.h"
 #include "rt_rgb2spec.h"
+#include "rt_texture.h"
 #include "../../include/rtmi355x.h"
 
 namespace {
@@ -70,36 +71,6 @@ const RgbTable* table() {
     return ok ? &t : nullptr;
 }
 
-inline float lerp(float x, float a, float b) { return (1 - x) * a + x * b; }  // helpers.h:154-157
-
-// color.cpp:26-72 RGBToSpectrumTable::operator() (non-uniform branch)
-void table_lookup(const RgbTable& T, const float* rgb, float* c) {
-    const int res = T.res;
-    const int maxc = (rgb[0] > rgb[1]) ? ((rgb[0] > rgb[2]) ? 0 : 2) : ((rgb[1] > rgb[2]) ? 1 : 2);
-    const float z = rgb[maxc];
-    const float x = rgb[(maxc + 1) % 3] * (res - 1) / z;
-    const float y = rgb[(maxc + 2) % 3] * (res - 1) / z;
-    const int xi = std::min((int)x, res - 2), yi = std::min((int)y, res - 2);
-    long size = (long)res - 2, first = 1;  // FindInterval(res, zNodes[i] < z)
-    while (size > 0) {
-        const long half = size >> 1, middle = first + half;
-        const bool r = T.z[middle] < z;
-        first = r ? middle + 1 : first;
-        size = r ? size - (half + 1) : half;
-    }
-    const int zi = (int)std::min(std::max(first - 1, 0L), (long)res - 2);
-    const float dx = x - xi, dy = y - yi, dz = (z - T.z[zi]) / (T.z[zi + 1] - T.z[zi]);
-    for (int i = 0; i < 3; ++i) {
-        auto co = [&](int ox, int oy, int oz) {
-            const size_t index = (size_t)maxc * 64 * 64 * 64 * 3 + (size_t)(zi + oz) * 64 * 64 * 3 +
-                                 (size_t)(yi + oy) * 64 * 3 + (size_t)(xi + ox) * 3 + i;
-            return T.coeffs[index];
-        };
-        c[i] = lerp(dz, lerp(dy, lerp(dx, co(0, 0, 0), co(1, 0, 0)), lerp(dx, co(0, 1, 0), co(1, 1, 0))),
-                    lerp(dy, lerp(dx, co(0, 0, 1), co(1, 0, 1)), lerp(dx, co(0, 1, 1), co(1, 1, 1))));
-    }
-}
-
 bool valid_rgb(const float* rgb) {
     for (int k = 0; k < 3; ++k)
         if (!(rgb[k] >= 0.f && rgb[k] <= 1.f)) return false;
@@ -108,19 +79,29 @@ bool valid_rgb(const float* rgb) {
 
 }  // namespace
 
+// the loaded table for the texture bake (rt_host.cpp uploads it once per context): 64 z-nodes, kRgbTableFloats coefficients
+namespace rtmi {
+bool rgb_table_host(const float** z, const float** coeffs) {
+    const RgbTable* T = table();
+    if (!T) return false;
+    *z = T->z.data();
+    *coeffs = T->coeffs.data();
+    return true;
+}
+}  // namespace rtmi
+
 extern "C" {
 
 static int impl_rt_rgb_to_sigmoid(const float* rgb, float* coeffs) {
     if (!rgb || !coeffs || !valid_rgb(rgb)) return RT_E_ARG;
-    if (rgb[0] == rgb[1] && rgb[1] == rgb[2]) {  // color.cpp:35-37, in float like the reference
-        float g = rgb[0];
-        coeffs[0] = 0; coeffs[1] = 0;
-        coeffs[2] = (g - .5f) / std::sqrt(g * (1 - g));  // +-inf at 0 and 1: s(+-inf) = 1, 0
+    // (the arithmetic is rt_texture.h's rgb_to_sigmoid, the text k_texture_bake compiles for the device)
+    if (rgb[0] == rgb[1] && rgb[1] == rgb[2]) {  // color.cpp:35-37, in float like the reference: no table needed
+        rtmi::rgb_to_sigmoid(nullptr, nullptr, rgb, coeffs);
         return RT_OK;
     }
     const RgbTable* T = table();
     if (!T) return RT_E_STATE;  // the coefficient table was not generated (python __graft_entry__.py build)
-    table_lookup(*T, rgb, coeffs);
+    rtmi::rgb_to_sigmoid(T->z.data(), T->coeffs.data(), rgb, coeffs);
     return RT_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include "rt_internal.h"
 #include "rt_mathf.h"
+#include "rt_texture.h"
 
 namespace rtmi {
 
@@ -404,6 +405,24 @@ RT_DEV float sigmoid_eval(float c0, float c1, float c2, float lambda) {  // colo
     return .5f + x / (2 * sqrtf(1 + (x * x)));
 }
 // pixelsensor.h:81-87 XYZ sensor ToSensorRGB (SafeDiv by pdf, Average, * imagingRatio)
+// The albedo of a hit on triangle `prim` of material `mid` at barycentrics (b0, b1, b2): when the
+// material has a texture, uv = (tc1 b0 + tc2 b1) + tc3 b2 per component (Shapes.h:1042), the nearest texel by
+// texel_index, and (c0, c1, c2) become that texel's baked coefficients.  Returns the texel's index within its texture
+// (gidx: within the scene's texel array) or -1 for an untextured material, which leaves c0, c1, c2 alone.
+RT_DEV int tex_fetch(const DevTex& tx, int prim, int mid, float b0, float b1, float b2, int& gidx, float& c0, float& c1,
+                     float& c2) {
+    const int t = tx.matTex[mid];
+    if (t < 0) return -1;
+    const int4 r = tx.tex[t];
+    const float2 t1 = tx.triUV[3 * prim], t2 = tx.triUV[3 * prim + 1], t3 = tx.triUV[3 * prim + 2];
+    const float u = (t1.x * b0 + t2.x * b1) + t3.x * b2, v = (t1.y * b0 + t2.y * b1) + t3.y * b2;
+    const int idx = texel_index(r.y, r.z, r.w, u, v);
+    gidx = r.x + idx;
+    const float4 c = tx.texels[gidx];
+    c0 = c.x; c1 = c.y; c2 = c.z;
+    return idx;
+}
+
 RT_DEV void to_sensor_rgb(const DevSpectra* sp, const float L_[8], const float lam[8], const float pdf[8], float ir,
                           float rgb[3]) {
     float L[8];

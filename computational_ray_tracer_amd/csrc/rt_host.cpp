@@ -27,6 +27,7 @@
 #include "rt_devbuf.h"
 #include "rt_guard.h"
 #include "rt_internal.h"
+#include "rt_texture.h"
 
 using namespace rtmi;
 
@@ -613,6 +614,20 @@ struct rt_ctx {
     DevScene dsc{};
     std::vector<DevBuf<unsigned char>> scene_allocs;  // the arrays dsc points to
     const float* d_kappa = nullptr;  // per analytic shape: the curvature the curved chain guides use (in scene_allocs)
+    // albedo textures of the uploaded scene (rt_scene_set_textures): live = the path kernels run their TEX
+    // instantiations on dev (the DevTex in device memory that points to the other arrays).  table: the RGB -> sigmoid
+    // coefficient table (kRgbRes z-nodes, then kRgbTableFloats coefficients), uploaded once per context on first use.
+    // mat_flags: per material of the scene, bit 0 = it emits, bit 1 = an analytic shape uses it (neither takes a texture).
+    struct Textures {
+        bool live = false;
+        DevBuf<float4> texels;
+        DevBuf<int4> recs;
+        DevBuf<int> matTex;
+        DevBuf<float2> triUV;
+        DevBuf<DevTex> dev;
+        DevBuf<float> table;
+        std::vector<unsigned char> mat_flags;
+    } tx;
     // spectra + resolve matrices
     HostSpectra hs;
     DevBuf<DevSpectra> d_spec;
@@ -722,7 +737,15 @@ int fail(rt_ctx* c, int code, const std::string& msg) {
                         std::string(#call) + ": " + hipGetErrorString(_e));                               \
     } while (0)
 
+// (the coefficient table stays: it belongs to the context, not to the scene)
+void free_textures(rt_ctx* c) {
+    c->tx.live = false;
+    c->tx.texels.reset(); c->tx.recs.reset(); c->tx.matTex.reset(); c->tx.triUV.reset(); c->tx.dev.reset();
+}
+
 void free_scene(rt_ctx* c) {
+    free_textures(c);
+    c->tx.mat_flags.clear();
     c->scene_allocs.clear();
     c->dsc = DevScene{};
     c->d_kappa = nullptr;
@@ -1178,7 +1201,7 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, 
     if (ie == ib || n_work == 0) return RT_OK;
     bool path = c->integ.kind == RT_INTEGRATOR_PATH || c->integ.kind == RT_INTEGRATOR_PATH_MIS;
     c->dsc.mis = c->integ.kind == RT_INTEGRATOR_PATH_MIS;
-    c->dsc.full = c->scene_full || c->dsc.mis;
+    c->dsc.full = c->scene_full || c->dsc.mis || c->tx.live;  // (textures are fetched by the general kernels alone)
     // samples per path batch: 16 Mi on a single-leaf octree (8 Mi: Cornell 1874 -> 1827; flat above 16 Mi, r06_ab7),
     // 32 Mi on multi-level ones, whose fewer, fuller launches keep more rays in every wave's reach (16 -> 32 Mi: CFG3
     // +2.5 %, CFG4 +3.5 %, flat above, r06_ab23/24)
@@ -1410,6 +1433,7 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, 
                     nio = NeeIO{b.neeRec.get(), ns.queue, qc_cur + kQShadowLen, qc_cur + kQShadowTicket, ns.fallback,
                                 qc_cur + kQNeeFallback, sort_nee ? ns.key : nullptr, c->sort_lo, c->sort_scale,
                                 kn.sort_nee_bits};
+                if (c->tx.live) nio.tex = c->tx.dev.get();
                 e0 = ev_start(c, s);
                 if (bins) {  // the hits binned by material, then one kernel per bin over its index list
                     HIPCHK(c, launch_bin_materials(s, grid, dsl, bio));
@@ -2310,7 +2334,11 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
     shading_arrays(s, sw, shade);
     LeafClusters clus;
     if (lim.qcap == 1) leaf_clusters(ob.nodes[0], flat, clus);
-    return upload_scene(c, s, flat, lim, shade, clus, bvh, wabs, oguard);
+    if ((rc = upload_scene(c, s, flat, lim, shade, clus, bvh, wabs, oguard))) return rc;
+    c->tx.mat_flags.assign(shade.mats.size(), 0);
+    for (size_t i = 0; i < shade.mats.size(); ++i) c->tx.mat_flags[i] = shade.mats[i].emit > 0 ? 1 : 0;
+    for (const DevShape& h : shade.shapes) c->tx.mat_flags[h.material] |= 2;
+    return RT_OK;
 }
 
 static int camera_set_one(rt_ctx* c, const rt_camera_desc* d) {
@@ -2680,7 +2708,7 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
     if (ie == ib || n_work == 0) return RT_OK;
     const bool path = c->integ.kind == RT_INTEGRATOR_PATH || c->integ.kind == RT_INTEGRATOR_PATH_MIS;
     c->dsc.mis = c->integ.kind == RT_INTEGRATOR_PATH_MIS;
-    c->dsc.full = c->scene_full || c->dsc.mis;
+    c->dsc.full = c->scene_full || c->dsc.mis || c->tx.live;  // (textures are fetched by the general kernels alone)
     const size_t target = c->knobs.batch_samples ? c->knobs.batch_samples : (size_t)(c->dsc.qcap == 1 ? 16 : 32) << 20;
     int B = (int)std::max<size_t>(1, target / (size_t)n_work);
     B = std::min(B, ie - ib);
@@ -3522,6 +3550,138 @@ static int impl_rt_debug_samples(rt_ctx* c, int n, const int32_t* pixel_ids, con
     });
 }
 
+// ---- albedo textures --------------------------------------------------------------------------
+// the coefficient table on the device, once per context
+static int ensure_rgb_table(rt_ctx* c) {
+    if (c->tx.table.get()) return RT_OK;
+    const float *z, *co;
+    if (!rgb_table_host(&z, &co))
+        return fail(c, RT_E_STATE, "the RGB -> sigmoid coefficient table is missing (python __graft_entry__.py build)");
+    DevBuf<float> t;
+    HIPCHK(c, t.reserve(kRgbRes + kRgbTableFloats));
+    HIPCHK(c, hipMemcpy(t.get(), z, sizeof(float) * kRgbRes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(t.get() + kRgbRes, co, sizeof(float) * kRgbTableFloats, hipMemcpyHostToDevice));
+    c->tx.table = std::move(t);
+    return RT_OK;
+}
+
+static int impl_rt_scene_set_textures(rt_ctx* c, const rt_texture_desc* d) {
+    if (!c) return RT_E_ARG;
+    if (!c->have_scene) return fail(c, RT_E_STATE, "rt_scene_set_textures needs an uploaded scene");
+    if (c->ad.live) return fail(c, RT_E_STATE, "rt_scene_set_textures during an adaptive session (rt_adaptive_end first)");
+    if (c->tp.live) return fail(c, RT_E_STATE, "rt_scene_set_textures during a temporal session (rt_temporal_end first)");
+    if (!c->peers.empty()) return fail(c, RT_E_STATE, "textures support one-device contexts only");
+    hipSetDevice(c->device);
+    if (!d || d->n_textures == 0) {  // clear: the untextured kernels again
+        HIPCHK(c, hipDeviceSynchronize());  // (passes on a caller's stream included)
+        free_textures(c);
+        return RT_OK;
+    }
+    if (d->n_textures < 0 || !d->textures || !d->material_texture || !d->tri_texcoords)
+        return fail(c, RT_E_ARG, "texture descriptor: NULL array or negative count");
+    if (d->n_materials != c->dsc.n_materials || d->n_triangles != c->n_tris)
+        return fail(c, RT_E_ARG, "texture descriptor: n_materials / n_triangles differ from the uploaded scene");
+    uint64_t total = 0;
+    for (int t = 0; t < d->n_textures; ++t) {
+        const rt_texture& x = d->textures[t];
+        if (x.width < 1 || x.height < 1) return fail(c, RT_E_ARG, "texture width and height must be >= 1");
+        if (x.wrap != RT_TEX_CLAMP && x.wrap != RT_TEX_REPEAT) return fail(c, RT_E_ARG, "unknown texture wrap mode");
+        if (!x.rgb) return fail(c, RT_E_ARG, "texture without pixels");
+        total += (uint64_t)x.width * (uint64_t)x.height;
+    }
+    for (int m = 0; m < d->n_materials; ++m) {
+        const int t = d->material_texture[m];
+        if (t < -1 || t >= d->n_textures) return fail(c, RT_E_ARG, "texture id out of range");
+        if (t >= 0 && (c->tx.mat_flags[m] & 1)) return fail(c, RT_E_ARG, "a texture cannot be bound to an emissive material");
+        if (t >= 0 && (c->tx.mat_flags[m] & 2))
+            return fail(c, RT_E_ARG, "a texture cannot be bound to a material an analytic shape uses");
+    }
+    // the NEE record's tag holds n_materials + texel index in 31 bits (rt_internal.h NeeIO)
+    if ((uint64_t)d->n_materials + total > 0x7fffffffull)
+        return fail(c, RT_E_LIMIT, "n_materials plus the textures' texel count exceeds 2^31 - 1");
+    int rc;
+    if ((rc = ensure_rgb_table(c))) return rc;
+    HIPCHK(c, hipDeviceSynchronize());
+    free_textures(c);
+    rt_ctx::Textures& T = c->tx;
+    std::vector<int4> recs(d->n_textures);
+    HIPCHK(c, T.texels.reserve((size_t)total));
+    {
+        DevBuf<unsigned char> bytes;  // one texture's RGB8 at a time
+        size_t base = 0;
+        for (int t = 0; t < d->n_textures; ++t) {
+            const rt_texture& x = d->textures[t];
+            const size_t n = (size_t)x.width * (size_t)x.height;
+            recs[t] = make_int4((int)base, x.width, x.height, x.wrap);
+            HIPCHK(c, bytes.reserve(3 * n));
+            HIPCHK(c, hipMemcpy(bytes.get(), x.rgb, 3 * n, hipMemcpyHostToDevice));
+            HIPCHK(c, launch_texture_bake(c->stream, T.table.get(), (int)n, bytes.get(), T.texels.get() + base));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            base += n;
+        }
+    }
+    HIPCHK(c, T.recs.reserve(recs.size()));
+    HIPCHK(c, hipMemcpy(T.recs.get(), recs.data(), sizeof(int4) * recs.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, T.matTex.reserve((size_t)d->n_materials));
+    HIPCHK(c, hipMemcpy(T.matTex.get(), d->material_texture, sizeof(int) * (size_t)d->n_materials, hipMemcpyHostToDevice));
+    HIPCHK(c, T.triUV.reserve(3 * (size_t)d->n_triangles));
+    HIPCHK(c, hipMemcpy(T.triUV.get(), d->tri_texcoords, sizeof(float2) * 3 * (size_t)d->n_triangles, hipMemcpyHostToDevice));
+    const DevTex dt{T.texels.get(), T.recs.get(), T.matTex.get(), T.triUV.get()};
+    HIPCHK(c, T.dev.reserve(1));
+    HIPCHK(c, hipMemcpy(T.dev.get(), &dt, sizeof(dt), hipMemcpyHostToDevice));
+    T.live = true;
+    return RT_OK;
+}
+
+static int impl_rt_debug_texture_bake(rt_ctx* c, int n, const uint8_t* rgb, float* coeffs) {
+    if (!c || n < 0 || (n && (!rgb || !coeffs))) return c ? fail(c, RT_E_ARG, "texture bake: invalid argument") : RT_E_ARG;
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    int rc;
+    if ((rc = ensure_rgb_table(c))) return rc;
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<unsigned char> bytes;
+        DevBuf<float4> out;
+        if (bytes.reserve(3 * (size_t)n) || out.reserve(n)) return fail(c, RT_E_OOM, "texture bake buffers");
+        std::vector<float4> h(n);
+        if (hipMemcpy(bytes.get(), rgb, 3 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_texture_bake(c->stream, c->tx.table.get(), n, bytes.get(), out.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(h.data(), out.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("texture bake: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) { coeffs[3 * i] = h[i].x; coeffs[3 * i + 1] = h[i].y; coeffs[3 * i + 2] = h[i].z; }
+        return RT_OK;
+    });
+}
+
+static int impl_rt_debug_texture_eval(rt_ctx* c, int n, const int32_t* prim, const float* b, int32_t* texel, float* coeffs) {
+    if (!c || n < 0 || (n && (!prim || !b || !texel || !coeffs)))
+        return c ? fail(c, RT_E_ARG, "texture eval: invalid argument") : RT_E_ARG;
+    if (!c->have_scene) return fail(c, RT_E_STATE, "no scene");
+    for (int i = 0; i < n; ++i)
+        if (prim[i] < 0 || prim[i] >= c->n_tris) return fail(c, RT_E_ARG, "texture eval: triangle id out of range");
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<int> dp, dt;
+        DevBuf<float> db;
+        DevBuf<float4> dc;
+        if (dp.reserve(n) || dt.reserve(n) || db.reserve(3 * (size_t)n) || dc.reserve(n))
+            return fail(c, RT_E_OOM, "texture eval buffers");
+        std::vector<float4> h(n);
+        if (hipMemcpy(dp.get(), prim, 4 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(db.get(), b, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_texture_eval(c->stream, c->dsc, c->tx.live ? c->tx.dev.get() : nullptr, n, dp.get(), db.get(), dt.get(),
+                                dc.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(texel, dt.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(h.data(), dc.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("texture eval: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) { coeffs[3 * i] = h[i].x; coeffs[3 * i + 1] = h[i].y; coeffs[3 * i + 2] = h[i].z; }
+        return RT_OK;
+    });
+}
+
 // ---- multi-device wrappers: configuration goes to every device of the context -------------------------------
 extern "C++" template <class F>
 static int on_all(rt_ctx* c, F f) {
@@ -3734,6 +3894,17 @@ int rt_debug_occluded(rt_ctx* c, int n, const float* ro, const float* rd, const 
 }
 int rt_debug_samples(rt_ctx* c, int n, const int32_t* pixel_ids, const int32_t* indices, rt_sample_record* out) {
     return entry(c, impl_rt_debug_samples, n, pixel_ids, indices, out);
+}
+int rt_scene_set_textures(rt_ctx* c, const rt_texture_desc* d) { return entry(c, impl_rt_scene_set_textures, d); }
+int rt_debug_texture_bake(rt_ctx* c, int n, const uint8_t* rgb, float* coeffs) {
+    return entry(c, impl_rt_debug_texture_bake, n, rgb, coeffs);
+}
+int rt_debug_texture_eval(rt_ctx* c, int n, const int32_t* prim, const float* b, int32_t* texel, float* coeffs) {
+    return entry(c, impl_rt_debug_texture_eval, n, prim, b, texel, coeffs);
+}
+int rt_texel_index(int width, int height, int wrap, float u, float v) {
+    if (width < 1 || height < 1 || (wrap != RT_TEX_CLAMP && wrap != RT_TEX_REPEAT)) return RT_E_ARG;
+    return rtmi::texel_index(width, height, wrap, u, v);
 }
 int rt_debug_sort(rt_ctx* c, int which, int S, const int32_t* shard_len, const uint32_t* keys, const int32_t* slots,
                   int bits_a, int bits_b, int32_t* out, int32_t* out_len) {

@@ -158,6 +158,14 @@ struct DevScene {
     const int* emit_shapes;
     int n_emit_shapes;
 };
+// Albedo textures of a scene (rt_scene_set_textures).  All textures share one texel array of baked
+// sigmoid coefficients (k_texture_bake: float4 (c0, c1, c2, 0) per texel, x fastest, row 0 is v = 0).
+struct DevTex {
+    const float4* texels;
+    const int4* tex;        // per texture: (first texel, width, height, wrap)
+    const int* matTex;      // per material: texture id or -1
+    const float2* triUV;    // 3 per triangle: the corners' (u, v)
+};
 static const int kMaxEmitTris = 64;  // emitter filter only with at most this many emissive triangles
 static const int kCoopFifo = 2048;   // entries of the wave-cooperative BFS's group FIFO (16-bit group ids, LDS)
 
@@ -407,7 +415,12 @@ struct NeeIO {
     int* fb_len;   // re-run by k_path_nee<Q, true> with the exact traversal (their count: zeroed with the region)
     unsigned* key; // NEE sort (nullptr: none): the Morton code of the shading point per NEE queue position
     float4 lo, scale; int key_bits;  // its quantisation (SortRaysIO lo / scale) and bits per axis
+    // albedo textures: the scene's DevTex in device memory, read by the TEX instantiations of
+    // k_path_shade_full and k_path_nee alone (nullptr: no textures, the launchers pick the untextured kernels).  It
+    // sits in the padding after key_bits, so the struct and every untextured kernel's arguments are unchanged.
+    const struct DevTex* tex = nullptr;
 };
+static_assert(sizeof(NeeIO) == 112, "NeeIO: the texture pointer lives in the tail padding");
 
 // 9 bits -> every third bit of 27
 __device__ __forceinline__ unsigned spread3_9(unsigned v) {
@@ -628,5 +641,16 @@ hipError_t launch_temporal_accumulate(hipStream_t st, const TemporalIO& io);
 // k_adaptive_error gives on k_temporal_accumulate's outputs.
 hipError_t launch_temporal_reproject(hipStream_t st, const TemporalIO& io, float4* rec);
 hipError_t launch_temporal_error(hipStream_t st, const AdaptiveIO& io, const float4* rec, float max_history);
+
+// Albedo textures (rt_texture.hip).  table: the RGB -> sigmoid coefficient table on the device, kRgbRes
+// z-nodes followed by kRgbTableFloats coefficients (rt_texture.h).
+// bake: texel i of n, rgb[3 i ..] bytes -> out[i] = (c0, c1, c2, 0) = rgb_to_sigmoid(byte / 255.f)
+hipError_t launch_texture_bake(hipStream_t st, const float* table, int n, const unsigned char* rgb, float4* out);
+// eval: the shade kernels' fetch (rt_device.h tex_fetch) on n explicit (prim, b0 b1 b2): texel[i] = the texel index
+// within its texture or -1, coeffs[i] = the (c0, c1, c2, 0) the shade would use.  tex == nullptr: no textures.
+hipError_t launch_texture_eval(hipStream_t st, const DevScene& sc, const DevTex* tex, int n, const int* prim,
+                               const float* b, int* texel, float4* coeffs);
+// the loaded coefficient table (rt_color.cpp), false when the file is missing
+bool rgb_table_host(const float** z, const float** coeffs);
 
 }  // namespace rtmi

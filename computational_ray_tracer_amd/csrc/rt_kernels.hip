@@ -2531,7 +2531,9 @@ __device__ __forceinline__ LightRay light_ray(const DevLight& Lt, V3 po, float u
 
 // MC (material class): 0 every material; 1 the Lambert-or-emitter bin, 2 the mirror-or-dielectric bin (items of
 // io.bin_idx: hits only: k_bin_materials appends no miss to any bin) — each bin kernel holds only its materials' code.
-template <int QCAP, int MC>
+// TEX (a scene with albedo textures): a textured triangle's (c0, c1, c2) come from its texel (tex_fetch)
+// and its NEE record's tag names the texel instead of the material; the untextured instantiations hold none of it.
+template <int QCAP, int MC, bool TEX = false>
 #ifndef RT_FULL_WAVES
 #define RT_FULL_WAVES RT_MULTI_WAVES  // the mixed-scene shade (variant builds)
 #endif
@@ -2544,6 +2546,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
     if constexpr (MC != 2) stage_spectra(sp);  // (the mirror / glass bin reads no spectrum table)
     const bool lds_mats = stage_materials(sc);
     const int nee_f4 = nee_stride(sc.n_lights);
+    DevTex tx{};
+    if constexpr (TEX) tx = *nee.tex;
     // lean depth 0: k_generate stored no β = 1 / L = 0, so they start in registers and every path's L is written
     const bool d0 = io.lean && io.depth == 0;
     // multi-level octrees: per-wave tickets and appends (per-ray cost varies by 100x); single leaf: per block
@@ -2608,7 +2612,13 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                     mid = s.material;
                     lidx = s.light;
                 }
-                const DevMaterial mt = mat_at(sc, lds_mats, mid);
+                DevMaterial mt = mat_at(sc, lds_mats, mid);
+                unsigned tagid = (unsigned)mid;  // the NEE record's albedo: a material, or n_materials + a texel
+                if constexpr (TEX) {
+                    int gidx;
+                    if (prim < sc.n_tris && tex_fetch(tx, prim, mid, hb.x, hb.y, hb.z, gidx, mt.c0, mt.c1, mt.c2) >= 0)
+                        tagid = (unsigned)(sc.n_materials + gidx);
+                }
                 // R_MISC (dimension, prevPdf, TerminateSecondary flag) read once and written back once, as a float4:
                 // the record is slot-indexed, so every narrow access of a wave is 64 scattered requests
                 float4 misc = *recf(io.rec, slot, R_MISC);
@@ -2754,7 +2764,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             }
                             if (wantNee)
                                 nr[N_PO] = make_float4(po.x, po.y, po.z,
-                                                       __uint_as_float((unsigned)mid | (bounced ? 0x80000000u : 0u)));
+                                                       __uint_as_float(tagid | (bounced ? 0x80000000u : 0u)));
                         }
                         save_sampler(io, slot, sm, io.dim >= 0);
                         if (io.dim < 0) misc.x = __int_as_float(sm.dim);
@@ -2835,7 +2845,8 @@ __global__ void __launch_bounds__(kBlock) k_occluded_path(DevScene sc, int n, co
 // accumulated but listed (nee.fb_slot); FB = true then re-runs the listed vertices with the exact traversal (the
 // reference BFS for the ambiguous rays), so this kernel never holds the BFS's registers (128 VGPRs + spill -> 108).
 // A vertex's lights are always accumulated together, in light order, by one of the two.
-template <int QCAP, bool FB>
+// TEX: the tag's low 31 bits are a material id below n_materials, else n_materials + a texel of the scene's texel array.
+template <int QCAP, bool FB, bool TEX = false>
 #ifndef RT_NEE_WAVES
 #define RT_NEE_WAVES 4  // (variant builds: Makefile `variants`)
 #endif
@@ -2849,6 +2860,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
     // the throughput of the continued path (NeeIO)
     const float InvPi = 0.31830988618379067154f;
     const int nuv4 = (nl + 1) / 2;
+    const float4* texels = nullptr;
+    if constexpr (TEX) texels = nee.tex->texels;
     // COOP (multi-level NEE queue): every lane of the wave calls vertex() in step (live = it has a vertex), so the
     // light loop reconverges after each light and the wave resolves the shadow rays the BVH could not decide with the
     // cooperative any-hit BFS (exact) instead of listing their vertices for k_path_nee<Q, true> (no fallback launch
@@ -2915,9 +2928,16 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             } else {
                 rload8(io.rec, slot, R_BETA, beta);
             }
-            const DevMaterial mt = sc.materials[tag & 0x7fffffffu];
+            float rc0, rc1, rc2;
+            if (TEX && (int)(tag & 0x7fffffffu) >= sc.n_materials) {
+                const float4 tc = texels[(tag & 0x7fffffffu) - (unsigned)sc.n_materials];
+                rc0 = tc.x; rc1 = tc.y; rc2 = tc.z;
+            } else {
+                const DevMaterial mt = sc.materials[tag & 0x7fffffffu];
+                rc0 = mt.c0; rc1 = mt.c1; rc2 = mt.c2;
+            }
 #pragma unroll
-            for (int i = 0; i < 8; ++i) R[i] = sigmoid_eval(mt.c0, mt.c1, mt.c2, lam[i]);
+            for (int i = 0; i < 8; ++i) R[i] = sigmoid_eval(rc0, rc1, rc2, lam[i]);
             if (vis) {
                 float L[8], x[8];
                 rload8(io.rec, slot, R_L, L);
@@ -3211,11 +3231,20 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
     if (!sc.full && qcap != 1 && !shq.shO) return hipErrorInvalidValue;       // so is the shadow queue
     if (sc.full) {  // (the material bins exist on multi-level scenes only: a single leaf shades every material)
         void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, NeeIO);
-        switch (qcap) {
-            case 0: k = matclass == 1 ? k_path_shade_full<0, 1> : matclass == 2 ? k_path_shade_full<0, 2> : k_path_shade_full<0, 0>; break;
-            case 1: k = k_path_shade_full<1, 0>; break;
-            case 16: k = matclass == 1 ? k_path_shade_full<16, 1> : matclass == 2 ? k_path_shade_full<16, 2> : k_path_shade_full<16, 0>; break;
-            default: return hipErrorInvalidValue;
+        if (nee.tex) {  // a textured scene: the TEX instantiations
+            switch (qcap) {
+                case 0: k = matclass == 1 ? k_path_shade_full<0, 1, true> : matclass == 2 ? k_path_shade_full<0, 2, true> : k_path_shade_full<0, 0, true>; break;
+                case 1: k = k_path_shade_full<1, 0, true>; break;
+                case 16: k = matclass == 1 ? k_path_shade_full<16, 1, true> : matclass == 2 ? k_path_shade_full<16, 2, true> : k_path_shade_full<16, 0, true>; break;
+                default: return hipErrorInvalidValue;
+            }
+        } else {
+            switch (qcap) {
+                case 0: k = matclass == 1 ? k_path_shade_full<0, 1> : matclass == 2 ? k_path_shade_full<0, 2> : k_path_shade_full<0, 0>; break;
+                case 1: k = k_path_shade_full<1, 0>; break;
+                case 16: k = matclass == 1 ? k_path_shade_full<16, 1> : matclass == 2 ? k_path_shade_full<16, 2> : k_path_shade_full<16, 0>; break;
+                default: return hipErrorInvalidValue;
+            }
         }
         return launch_resident(k, gb, grid, st, sc, sp, smp, film, ids, io, nee);
     }
@@ -3233,6 +3262,14 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
                            const PathIO& io, const NeeIO& nee, unsigned long long* ctr) {
     const int gb = ring_clamp(grid > 0 ? grid : 1, qcap, sc);
     if (qcap != 1 && (!nee.fb_slot || !nee.fb_len)) return hipErrorInvalidValue;  // the fallback list is required
+    if (nee.tex) {
+        switch (qcap) {
+            case 0: return launch_resident(k_path_nee<0, false, true>, gb, grid, st, sc, sp, io, nee, ctr);
+            case 1: return launch_resident(k_path_nee<1, false, true>, gb, grid, st, sc, sp, io, nee, ctr);
+            case 16: return launch_resident(k_path_nee<16, false, true>, gb, grid, st, sc, sp, io, nee, ctr);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (qcap) {
         case 0: return launch_resident(k_path_nee<0, false>, gb, grid, st, sc, sp, io, nee, ctr);
         case 1: return launch_resident(k_path_nee<1, false>, gb, grid, st, sc, sp, io, nee, ctr);
@@ -3245,6 +3282,13 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
 hipError_t launch_path_nee_fallback(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,
                                     const PathIO& io, const NeeIO& nee, unsigned long long* ctr) {
     const int gb = ring_clamp(std::min(grid > 0 ? grid : 1, kFallbackBlocks), qcap, sc);
+    if (nee.tex) {
+        switch (qcap) {
+            case 0: return launch_resident(k_path_nee<0, true, true>, gb, grid, st, sc, sp, io, nee, ctr);
+            case 16: return launch_resident(k_path_nee<16, true, true>, gb, grid, st, sc, sp, io, nee, ctr);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (qcap) {
         case 0: return launch_resident(k_path_nee<0, true>, gb, grid, st, sc, sp, io, nee, ctr);
         case 16: return launch_resident(k_path_nee<16, true>, gb, grid, st, sc, sp, io, nee, ctr);

@@ -61,11 +61,51 @@ class Renderer:
         self.cfg = cfg
         self._scene = cfg.model.desc()
         self._chk("rt_scene_upload", self.lib.rt_scene_upload(self.h, C.byref(self._scene)))
+        tex = cfg.model.texture_desc() if hasattr(cfg.model, "texture_desc") else None
+        if tex is not None:  # (the upload dropped any earlier textures)
+            self._chk("rt_scene_set_textures", self.lib.rt_scene_set_textures(self.h, C.byref(tex)))
         self._chk("rt_camera_set", self.lib.rt_camera_set(self.h, C.byref(cfg.camera.desc())))
         self._chk("rt_sampler_set", self.lib.rt_sampler_set(self.h, C.byref(cfg.sampler.desc())))
         self._chk("rt_film_set", self.lib.rt_film_set(self.h, C.byref(cfg.film.desc())))
         self._chk("rt_integrator_set", self.lib.rt_integrator_set(self.h, C.byref(cfg.integrator.desc())))
         self.res = cfg.film.res
+
+    # ---- albedo textures (rt_scene_set_textures) -----------------------------------------------
+    def set_textures(self, textures, material_texture=None, tri_texcoords=None):
+        """Bind scene.Texture images to the uploaded scene's materials: material_texture holds a texture id or -1 per
+        material, tri_texcoords (n_triangles, 3, 2) the corners' uv (default: the model's texcoords[indices]).
+        textures None or empty clears them.  The reference integrator ignores textures."""
+        if not textures:
+            self._chk("rt_scene_set_textures", self.lib.rt_scene_set_textures(self.h, None))
+            return
+        from . import scene
+        m = self.cfg.model
+        if tri_texcoords is None:
+            tri_texcoords = np.asarray(m.texcoords, np.float32)[np.asarray(m.indices, np.int64)]
+        d = scene.texture_desc(textures, material_texture, tri_texcoords, max(len(m.materials), 1))
+        self._chk("rt_scene_set_textures", self.lib.rt_scene_set_textures(self.h, C.byref(d)))
+
+    def texture_bake(self, rgb8):
+        """rt_debug_texture_bake: the bake kernel alone on (..., 3) uint8 texels -> (..., 3) float32 (c0, c1, c2)."""
+        a = np.ascontiguousarray(rgb8, np.uint8)
+        assert a.ndim >= 1 and a.shape[-1] == 3
+        out = np.zeros(a.shape, np.float32)
+        self._chk("rt_debug_texture_bake", self.lib.rt_debug_texture_bake(
+            self.h, a.size // 3, a.ctypes.data_as(C.POINTER(C.c_uint8)), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def texture_eval(self, prim, b):
+        """rt_debug_texture_eval: the shade kernels' texture fetch for triangle ids prim (n) and barycentrics b (n, 3):
+        (texel int32 (n): the index within the triangle's texture or -1 when it has none, coeffs float32 (n, 3): the
+        (c0, c1, c2) the shade would use)."""
+        prim = np.ascontiguousarray(prim, np.int32)
+        b = np.ascontiguousarray(b, np.float32)
+        assert b.shape == (len(prim), 3)
+        texel, co = np.zeros(len(prim), np.int32), np.zeros((len(prim), 3), np.float32)
+        self._chk("rt_debug_texture_eval", self.lib.rt_debug_texture_eval(
+            self.h, len(prim), prim.ctypes.data_as(C.POINTER(C.c_int32)), b.ctypes.data_as(C.POINTER(C.c_float)),
+            texel.ctypes.data_as(C.POINTER(C.c_int32)), co.ctypes.data_as(C.POINTER(C.c_float))))
+        return texel, co
 
     def set_shard(self, tile_size, n_shards, shard_id):
         self._chk("rt_set_shard", self.lib.rt_set_shard(self.h, tile_size, n_shards, shard_id))

@@ -379,6 +379,20 @@ class TriModel:
     lights: list = field(default_factory=list)      # dict(type=QUAD: p, e1, e2, n, material | DISK: shape,
                                                     #      material | POINT: p, scale | DISTANT: dir, scale)
     shapes: list = field(default_factory=list)      # Sphere / Disk / TriangleSimple, after the octree
+    # albedo textures: per-vertex uv, the images, and per material a texture id or -1
+    texcoords: np.ndarray = None                    # (nv, 2) float32
+    textures: list = field(default_factory=list)    # Texture
+    material_texture: list = None                   # one int per material (default: every material untextured)
+
+    def texture_desc(self):
+        """The rt_texture_desc of the model's textures (None without any); the returned object keeps its buffers
+        alive.  Texcoords go per triangle corner, texcoords[indices]: the context keeps no index buffer."""
+        if not self.textures:
+            return None
+        if self.texcoords is None:
+            raise ValueError("a textured TriModel needs texcoords")
+        return texture_desc(self.textures, self.material_texture, np.asarray(self.texcoords, np.float32)[
+            np.asarray(self.indices, np.int64)], max(len(self.materials), 1))
 
     def object_to_render(self):
         return np.asarray(self.rigid, float) @ PERM_YZ
@@ -434,6 +448,69 @@ class TriModel:
             d.shapes = C.cast(self._shapes, C.POINTER(capi.rt_shape))
         self._desc = d
         return d
+
+
+WRAP_MODES = {"clamp": capi.RT_TEX_CLAMP, "repeat": capi.RT_TEX_REPEAT}
+
+
+@dataclass
+class Texture:
+    """An RGB8 albedo image (rt_texture).  pixels: (H, W, 3) uint8; row 0 is v = 0 (RayTracerTestApp.h:231) unless
+    top_row_first, which is how image files store their rows.  wrap: "clamp" or "repeat"."""
+    pixels: np.ndarray
+    wrap: str = "clamp"
+    top_row_first: bool = False
+
+    def __post_init__(self):
+        p = np.asarray(self.pixels)
+        if p.dtype != np.uint8 or p.ndim != 3 or p.shape[2] != 3 or p.shape[0] < 1 or p.shape[1] < 1:
+            raise ValueError("Texture pixels: (H, W, 3) uint8")
+        if self.wrap not in WRAP_MODES:
+            raise ValueError(f"Texture wrap: one of {sorted(WRAP_MODES)}")
+
+    def rows(self):
+        """(H, W, 3) uint8, contiguous, row 0 at v = 0: the layout rt_texture.rgb takes."""
+        p = np.asarray(self.pixels)
+        return np.ascontiguousarray(p[::-1] if self.top_row_first else p)
+
+
+def texture_desc(textures, material_texture, tri_texcoords, n_materials):
+    """rt_texture_desc from Textures, per-material texture ids (None: all -1) and per-corner uv (nt, 3, 2)."""
+    d = capi.rt_texture_desc()
+    d._rows = [t.rows() for t in textures]
+    d._tex = (capi.rt_texture * max(len(textures), 1))()
+    for i, (t, r) in enumerate(zip(textures, d._rows)):
+        d._tex[i].height, d._tex[i].width = r.shape[0], r.shape[1]
+        d._tex[i].wrap = WRAP_MODES[t.wrap]
+        d._tex[i].rgb = r.ctypes.data_as(C.POINTER(C.c_uint8))
+    d.n_textures = len(textures)
+    d.textures = C.cast(d._tex, C.POINTER(capi.rt_texture))
+    mt = [-1] * n_materials if material_texture is None else material_texture
+    d._mt = np.ascontiguousarray(mt, np.int32)
+    d.n_materials = len(d._mt)
+    d.material_texture = d._mt.ctypes.data_as(C.POINTER(C.c_int32))
+    d._uv = np.ascontiguousarray(tri_texcoords, np.float32)
+    if d._uv.ndim != 3 or d._uv.shape[1:] != (3, 2):
+        raise ValueError("tri_texcoords: (n_triangles, 3, 2)")
+    d.n_triangles = len(d._uv)
+    d.tri_texcoords = d._uv.ctypes.data_as(C.POINTER(C.c_float))
+    return d
+
+
+def texel_index(width, height, wrap, u, v):
+    """rt_texel_index: the texel (y * width + x) a uv selects, the rule the shade kernels use.
+    wrap: "clamp" / "repeat" or the RT_TEX_* value.  u, v: scalars or arrays (int32 array back)."""
+    lib = capi.load_library()
+    w = WRAP_MODES.get(wrap, wrap)
+    uu, vv = np.broadcast_arrays(np.asarray(u, np.float32), np.asarray(v, np.float32))
+    out = np.empty(uu.shape, np.int32)
+    fo = out.reshape(-1)
+    for i, (a, b) in enumerate(zip(uu.reshape(-1), vv.reshape(-1))):
+        r = lib.rt_texel_index(int(width), int(height), int(w), C.c_float(a), C.c_float(b))
+        if r < 0:
+            raise capi.RTError("rt_texel_index", r, "width, height >= 1 and a wrap mode")
+        fo[i] = r
+    return out if out.ndim else int(out)
 
 
 def grey_sigmoid(g):
@@ -712,9 +789,10 @@ def cfg5_spectral(res=(3840, 2160), spp=(64, 32), max_depth=5, frequency=70):
 # ------------------------------------------------------------------ ingest / colour / image output
 
 
-def load_obj(path):
+def load_obj(path, texcoords=False):
     """rt_load_obj: Wavefront OBJ -> (positions, normals, indices) as the reference's assimp import leaves a
-    MeshCache::Mesh (AssetManager.cpp:67-190): triangulated, one vertex per corner, flat normals if absent."""
+    MeshCache::Mesh (AssetManager.cpp:67-190): triangulated, one vertex per corner, flat normals if absent.
+    texcoords=True: (positions, normals, indices, texcoords), the `vt` records per vertex (0 where absent)."""
     lib = capi.load_library()
     m = C.POINTER(capi.rt_mesh)()
     rc = lib.rt_load_obj(str(path).encode(), C.byref(m))
@@ -726,9 +804,10 @@ def load_obj(path):
         pos = np.ctypeslib.as_array(mm.positions, shape=(nv, 3)).copy()
         nrm = np.ctypeslib.as_array(mm.normals, shape=(nv, 3)).copy()
         idx = np.ctypeslib.as_array(mm.indices, shape=(mm.n_triangles, 3)).copy()
+        uv = np.ctypeslib.as_array(mm.texcoords, shape=(nv, 2)).copy() if texcoords else None
     finally:
         lib.rt_mesh_free(m)
-    return pos, nrm, idx
+    return (pos, nrm, idx, uv) if texcoords else (pos, nrm, idx)
 
 
 def rgb_albedo(rgb):

@@ -478,6 +478,53 @@ const char* rt_sensor_name(int sensor);
 /* The film's resolve matrices (column-major, glm layout): XYZFromSensorRGB of the current sensor, sRGB RGBFromXYZ. */
 int rt_film_matrices(rt_ctx* ctx, float* xyz_from_sensor9, float* rgb_from_xyz9);
 
+/* ---- albedo textures ----------------------------------------------------------------- */
+/* A diffuse or mirror material's reflectance R(lambda) read from an RGB8 image instead of the material's one sigmoid:
+ * the reference's texture lookup (the `if (false)` branch of Li, RayTracerTestApp.h:229-242) on the uv of
+ * Triangle::CalculateLocalSurface (Shapes.h:1036-1046).  float32, nothing fused:
+ *   uv of a hit, per component: (tc1 b0 + tc2 b1) + tc3 b2, the hit's barycentrics over the corners' texcoords;
+ *   texel: rt_texel_index (nearest; no filtering);
+ *   albedo: rgb = byte / 255.f per channel, then rt_rgb_to_sigmoid; its (c0, c1, c2) replace the material's wherever
+ *   the path integrators form R(lambda): the Lambert light terms, the Lambert bounce, the mirror scale.  Type, eta,
+ *   emission and light binding stay the material's.
+ * RT_INTEGRATOR_REFERENCE ignores textures (its Li has no materials); so do the feature, position and chain passes,
+ * which read geometry only. */
+enum { RT_TEX_CLAMP = 0, RT_TEX_REPEAT = 1 };
+typedef struct {
+    int width, height, wrap;         /* wrap: RT_TEX_CLAMP or RT_TEX_REPEAT                              */
+    const uint8_t* rgb;              /* 3 bytes per texel, x fastest, row 0 is v = 0 (RayTracerTestApp.h:231) */
+} rt_texture;
+typedef struct {
+    int n_textures;
+    const rt_texture* textures;
+    int n_materials;
+    const int32_t* material_texture; /* per material of the uploaded scene (one entry for a scene uploaded without
+                                        materials): texture id or -1                                        */
+    int n_triangles;
+    const float* tri_texcoords;      /* 6 per triangle: (u, v) of its three corners (the context keeps no index
+                                        buffer: the caller gathers texcoords[indices])                      */
+    int reserved[4];
+} rt_texture_desc;
+/* Bind textures to the uploaded scene (deep copy: the texels are baked to 16 B of coefficients each on the device, and
+ * the 9.4 MB coefficient table is uploaded once per context).  NULL or n_textures == 0 clears them; rt_scene_upload
+ * drops them.  A textured scene is shaded by the general path kernels (as a scene with MIS or several lights is).
+ * RT_E_STATE: no scene, an adaptive or temporal session is open, a multi-device context, or the coefficient table is
+ * missing.  RT_E_ARG: n_materials or n_triangles differ from the scene's, a texture id out of range, width or height
+ * < 1, a NULL array, a bad wrap value, a texture bound to an emissive material or to a material an analytic shape uses
+ * (shapes have no uv).  RT_E_LIMIT: n_materials plus the total texel count exceeds 2^31 - 1. */
+int rt_scene_set_textures(rt_ctx* ctx, const rt_texture_desc* desc);
+/* The texel a uv selects (host only, no context; RT_E_ARG for width or height < 1 or a bad wrap).  Per coordinate
+ * CLAMP: u' = min(max(u, 0), 1) (Shapes.h:1045-1046); REPEAT: u' = u - floorf(u), and 0 when that is not < 1; a NaN
+ * coordinate counts as 0 (build-defined).  x = (int)floorf(u' W) % W (u' = 1 wraps to column 0, as
+ * RayTracerTestApp.h:234 does), y = min((int)floorf(v' H), H - 1) (the reference reads past the image at v = 1; the
+ * clamp is build-defined); index = y W + x. */
+int rt_texel_index(int width, int height, int wrap, float u, float v);
+/* The bake kernel alone: n RGB8 texels (3n bytes) -> 3n floats (c0, c1, c2), bit for bit rt_rgb_to_sigmoid(byte / 255.f). */
+int rt_debug_texture_bake(rt_ctx* ctx, int n, const uint8_t* rgb, float* coeffs);
+/* The shade kernels' device function on n explicit (triangle id, b0 b1 b2): texel[i] = the texel index within its
+ * texture, or -1 for an untextured triangle, and coeffs[3i..] = the (c0, c1, c2) the shade would use. */
+int rt_debug_texture_eval(rt_ctx* ctx, int n, const int32_t* prim, const float* b, int32_t* texel, float* coeffs);
+
 /* ---- instrumentation ---------------------------------------------------------------------------- */
 int rt_get_stats(rt_ctx* ctx, rt_stats* out);
 int rt_reset_stats(rt_ctx* ctx);
