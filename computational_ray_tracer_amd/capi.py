@@ -167,6 +167,11 @@ class rt_texture_desc(C.Structure):
                 ("reserved", C.c_int * 4)]
 
 
+class rt_albedo(C.Structure):
+    """Albedo film entry: sums over the first hits of a feature pass."""
+    _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("hits", C.c_float)]
+
+
 class rt_octree_info(C.Structure):
     _fields_ = [("n_nodes", C.c_int), ("n_leaf_refs", C.c_int), ("max_queue_groups", C.c_int), ("depth", C.c_int),
                 ("bvh_nodes", C.c_int), ("bvh_depth", C.c_int)]
@@ -189,6 +194,7 @@ EXPORTS = [
     "rt_render_features_chain",
     "rt_temporal_frame_guided", "rt_temporal_block_error",
     "rt_scene_set_textures", "rt_texel_index", "rt_debug_texture_bake", "rt_debug_texture_eval",
+    "rt_render_features_albedo", "rt_denoise_albedo", "rt_adaptive_denoise_albedo", "rt_debug_albedo_bake",
 ]
 
 _lib = None
@@ -290,6 +296,12 @@ def load_library(path=None):
         "rt_texel_index": ([C.c_int, C.c_int, C.c_int, C.c_float, C.c_float], C.c_int),
         "rt_debug_texture_bake": ([C.c_void_p, C.c_int, P(C.c_uint8), P(C.c_float)], C.c_int),
         "rt_debug_texture_eval": ([C.c_void_p, C.c_int, P(C.c_int32), P(C.c_float), P(C.c_int32), P(C.c_float)], C.c_int),
+        "rt_render_features_albedo": ([C.c_void_p, C.c_int, C.c_int, C.c_int, P(rt_feature), P(rt_position),
+                                       P(rt_albedo)], C.c_int),
+        "rt_denoise_albedo": ([C.c_void_p, P(rt_denoise_desc), C.c_float, C.c_int, C.c_int, P(rt_pixel), P(rt_moment),
+                               P(rt_feature), P(rt_albedo), P(rt_pixel), P(C.c_float)], C.c_int),
+        "rt_adaptive_denoise_albedo": ([C.c_void_p, P(rt_denoise_desc), C.c_float, P(rt_pixel)], C.c_int),
+        "rt_debug_albedo_bake": ([C.c_void_p, C.c_int, P(C.c_float), P(C.c_float)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

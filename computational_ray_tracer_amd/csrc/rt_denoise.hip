@@ -8,6 +8,8 @@
 //   k_denoise_iter     one a-trous iteration with step s: the 3x3 blur of the variance, then the 25 taps in row-major
 //                      order; <LDS> stages the block's tile with its 2s halo in LDS (steps 1 and 2), otherwise every
 //                      tap is a plain load.  The last iteration also writes out = (c n, n) and the variance.
+//   k_denoise_prepare_albedo, k_denoise_finish_albedo   albedo demodulation: prepare that also divides
+//                      (c, var) by the pixel's floored albedo, and the multiplication back after the last iteration
 //
 // Everything is float32 in the order written (the build's -ffp-contract=off; / and sqrtf are correctly rounded) with
 // only + - * /, sqrtf, fmaxf and fabsf, so a numpy float32 restatement gives the same bits (tests/denoise_reference.py).
@@ -71,9 +73,10 @@ static_assert(kTX * kTY == kBlock, "one thread per pixel of the tile");
 
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
-__global__ void __launch_bounds__(kBlock) k_denoise_prepare(DenoiseIO io) {
-    const int x = (int)blockIdx.x * kTX + (int)(threadIdx.x % kTX), y = (int)blockIdx.y * kTY + (int)(threadIdx.x / kTX);
-    if (x >= io.res_x || y >= io.res_y) return;
+// One pixel of prepare.  ALB: the albedo variant, which divides c by the floored mean albedo a of the
+// pixel's albedo film entry, the variance by the square of a's mean sa, and keeps (a, sa) for the finish.
+template <bool ALB>
+__device__ __forceinline__ void prepare_pixel(const DenoiseIO& io, const DemodIO* dm, int x, int y) {
     const int W = io.res_x, p = y * W + x;
     const float4 f = io.film[p];
     const float n = f.w;
@@ -95,9 +98,48 @@ __global__ void __launch_bounds__(kBlock) k_denoise_prepare(DenoiseIO io) {
               yu = clampi(y + 1, io.res_y - 1);
     const float zl = io.feat[y * W + xl].w / kf, zr = io.feat[y * W + xr].w / kf;
     const float zd = io.feat[yd * W + x].w / kf, zu = io.feat[yu * W + x].w / kf;
+    if constexpr (ALB) {
+        const float4 al = dm->alb[p];
+        float4 a = make_float4(1.f, 1.f, 1.f, 1.f);
+        if (al.w > 0.f) {
+            a.x = fmaxf(al.x / al.w, dm->floor);
+            a.y = fmaxf(al.y / al.w, dm->floor);
+            a.z = fmaxf(al.z / al.w, dm->floor);
+        }
+        a.w = ((a.x + a.y) + a.z) / 3.f;
+        cv.x = cv.x / a.x;
+        cv.y = cv.y / a.y;
+        cv.z = cv.z / a.z;
+        cv.w = cv.w / (a.w * a.w);
+        dm->a[p] = a;
+    }
     io.cv_out[p] = cv;
     io.g[p] = make_float4(ft.x / kf, ft.y / kf, ft.z / kf, ft.w / kf);
     io.gz[p] = make_float2((zr - zl) * 0.5f, (zu - zd) * 0.5f);
+}
+
+__global__ void __launch_bounds__(kBlock) k_denoise_prepare(DenoiseIO io) {
+    const int x = (int)blockIdx.x * kTX + (int)(threadIdx.x % kTX), y = (int)blockIdx.y * kTY + (int)(threadIdx.x / kTX);
+    if (x >= io.res_x || y >= io.res_y) return;
+    prepare_pixel<false>(io, nullptr, x, y);
+}
+
+__global__ void __launch_bounds__(kBlock) k_denoise_prepare_albedo(DenoiseIO io, DemodIO dm) {
+    const int x = (int)blockIdx.x * kTX + (int)(threadIdx.x % kTX), y = (int)blockIdx.y * kTY + (int)(threadIdx.x / kTX);
+    if (x >= io.res_x || y >= io.res_y) return;
+    prepare_pixel<true>(io, &dm, x, y);
+}
+
+// The albedo variant's finish: the last iteration's (c', var') times the albedo kept by prepare.
+__global__ void __launch_bounds__(kBlock) k_denoise_finish_albedo(DenoiseIO io, DemodIO dm, const float4* __restrict__ cv,
+                                                                  float4* __restrict__ out, float* __restrict__ var_out) {
+    const int x = (int)blockIdx.x * kTX + (int)(threadIdx.x % kTX), y = (int)blockIdx.y * kTY + (int)(threadIdx.x / kTX);
+    if (x >= io.res_x || y >= io.res_y) return;
+    const int p = y * io.res_x + x;
+    const float4 r = cv[p], a = dm.a[p];
+    const float n = io.film[p].w;
+    out[p] = make_float4((r.x * a.x) * n, (r.y * a.y) * n, (r.z * a.z) * n, n);
+    if (var_out) var_out[p] = r.w * (a.w * a.w);
 }
 
 // the compact kernel e(x) = q^8, q = max(1 - x / 8, 0)
@@ -225,6 +267,17 @@ hipError_t launch_feature_film(hipStream_t st, const DevScene& sc, const Feature
 
 hipError_t launch_denoise_prepare(hipStream_t st, const DenoiseIO& io) {
     hipLaunchKernelGGL(k_denoise_prepare, tile_grid(io), dim3(kBlock), 0, st, io);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_prepare_albedo(hipStream_t st, const DenoiseIO& io, const DemodIO& dm) {
+    hipLaunchKernelGGL(k_denoise_prepare_albedo, tile_grid(io), dim3(kBlock), 0, st, io, dm);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_finish_albedo(hipStream_t st, const DenoiseIO& io, const DemodIO& dm, const float4* cv,
+                                        float4* out, float* var_out) {
+    hipLaunchKernelGGL(k_denoise_finish_albedo, tile_grid(io), dim3(kBlock), 0, st, io, dm, cv, out, var_out);
     return hipGetLastError();
 }
 

@@ -627,7 +627,14 @@ struct rt_ctx {
         DevBuf<DevTex> dev;
         DevBuf<float> table;
         std::vector<unsigned char> mat_flags;
+        size_t n_texels = 0;
     } tx;
+    // albedo demodulation: the sensor albedo of the scene's materials, then of its texels, 16 B per
+    // entry; built on first use and again after rt_scene_upload, rt_scene_set_textures or rt_film_set
+    struct Albedo {
+        DevBuf<float4> table;
+        bool valid = false;
+    } alb;
     // spectra + resolve matrices
     HostSpectra hs;
     DevBuf<DevSpectra> d_spec;
@@ -685,6 +692,9 @@ struct rt_ctx {
         DevBuf<float4> feat;         // rt_adaptive_denoise: the feature film of indices [0, feat_k), 0: not rendered,
         int feat_k = 0;              // through the chain pass of depth feat_chain
         int feat_chain = 0;
+        DevBuf<float4> alb;          // rt_adaptive_denoise_albedo: the albedo film of the same indices,
+        int alb_k = 0;               // rendered together with feat; 0: not rendered
+        int alb_chain = 0;
         // a guided temporal frame's session (rt_temporal_frame_guided): with `on` the steps estimate the
         // block errors with k_temporal_error, on the film blended with rec, the frame's reprojected history (the
         // temporal session's buffer; null: there is none)
@@ -698,6 +708,7 @@ struct rt_ctx {
     // the (c, var) ping-pong; grows on demand
     struct Denoise {
         DevBuf<float4> film, feat, g, cv[2], out;
+        DevBuf<float4> alb, a;       // the albedo variants: albedo film staging, the per-pixel (a, sa)
         DevBuf<float2> mom, gz;
         DevBuf<float> var;
     } dn;
@@ -741,6 +752,9 @@ int fail(rt_ctx* c, int code, const std::string& msg) {
 void free_textures(rt_ctx* c) {
     c->tx.live = false;
     c->tx.texels.reset(); c->tx.recs.reset(); c->tx.matTex.reset(); c->tx.triUV.reset(); c->tx.dev.reset();
+    c->tx.n_texels = 0;
+    c->alb.table.reset();  // (the albedo table covers the texels: released with them, rebuilt on first use)
+    c->alb.valid = false;
 }
 
 void free_scene(rt_ctx* c) {
@@ -1617,6 +1631,7 @@ void sensor_matrices(const HostSpectra& hs, int sensor, int illum_id, float* xyz
 }
 
 int setup_sensor(rt_ctx* c, const rt_film_desc& d) {
+    c->alb.valid = false;  // (the albedo table is baked under the sensor's curves)
     DenseS bars[3];
     sensor_matrices(c->hs, d.sensor, d.sensor_illum, c->resolveA, c->resolveB, bars);
     float both[18];
@@ -2684,6 +2699,18 @@ int chain_check_depth(rt_ctx* c, int chain_depth) {
     return RT_OK;
 }
 
+// The sensor albedo table of the scene's materials and texels, on first use after the scene, its textures or the
+// sensor changed.
+int ensure_albedo_table(rt_ctx* c, hipStream_t st) {
+    if (c->alb.valid) return RT_OK;
+    const size_t n = (size_t)c->dsc.n_materials + c->tx.n_texels;
+    HIPCHK(c, c->alb.table.reserve(n));
+    HIPCHK(c, launch_albedo_bake(st, c->d_spec.get(), c->dsc.n_materials, c->dsc.materials, (int)c->tx.n_texels,
+                                 c->tx.texels.get(), c->alb.table.get()));
+    c->alb.valid = true;
+    return RT_OK;
+}
+
 // Features of indices [ib, ie) of the full work list added to the device feature film: per batch the camera rays, the
 // closest hits as the current integrator's first trace finds them (reference: the culled tile set when the scene
 // culls; path: every triangle), then k_feature_film.  Batches as render_device_body's reference loop.
@@ -2692,8 +2719,11 @@ int chain_check_depth(rt_ctx* c, int chain_depth) {
 // level, k_chain_level over the level's queue and, for the rays it appends, the trace of a path bounce; then
 // k_chain_film.  The chain's per-slot state uses the reference workspace's wavelength and pdf arrays, which k_generate
 // fills and the feature pass never reads.
+// alb (may be null): the albedo film of the batch's FIRST hits, added right after the first trace, before
+// a chain's levels overwrite the hit records.
+
 int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, float4* pos = nullptr,
-                    int chain_arg = 0) {
+                    int chain_arg = 0, float4* alb = nullptr) {
     int rc;
     if ((rc = chain_check_depth(c, chain_arg))) return rc;
     const int chain_depth = chain_arg & ~RT_CHAIN_CURVED;
@@ -2719,6 +2749,7 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
     const DevFilm fd = dev_film(c);
     Work& w = c->ws[0];
     if ((rc = ensure_workspace(c, w, ncap, false))) return rc;
+    if (alb && (rc = ensure_albedo_table(c, st))) return rc;
     // (the reference integrator consults no material: every chain has length 0)
     const bool chain = path && chain_depth > 0;
     const bool dyn = c->dsc.qcap != 1;  // the bounce rays' trace: per-wave tickets on multi-level octrees
@@ -2743,6 +2774,11 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
         e0 = ev_start(c, st);
         HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()));
         ev_mark(c, st, ST_TRACE, e0);
+        if (alb) {
+            const AlbedoFilmIO aio{c->d_work.get(), n_work, nIdx, w.b.hitB.get(), w.b.hitPrim.get(), c->alb.table.get(),
+                                   c->tx.live ? c->tx.dev.get() : nullptr, path ? 0 : 1, alb};
+            HIPCHK(c, launch_albedo_film(st, c->dsc, aio));
+        }
         if (!chain) {
             const FeatureIO fio{c->d_work.get(), n_work, nIdx, w.b.rayD(), 1, w.b.hitB.get(), w.b.hitPrim.get(), feat,
                                 w.b.rayO(), pos};
@@ -2809,10 +2845,15 @@ int denoise_check_desc(rt_ctx* c, const rt_denoise_desc* d) {
 }
 
 // prepare and the iterations over device arrays of res_x * res_y; out = (c n, n), var (may be null) = the last variance
+// alb (may be null): the albedo film to demodulate by, floored at albedo_floor: the albedo prepare, every
+// iteration into the ping-pong, and the remodulating finish
 int denoise_device(rt_ctx* c, const rt_denoise_desc& d, int res_x, int res_y, const float4* film, const float2* mom,
-                   const float4* feat, float4* out, float* var, hipStream_t st) {
+                   const float4* feat, float4* out, float* var, hipStream_t st, const float4* alb = nullptr,
+                   float albedo_floor = 0.f) {
     rt_ctx::Denoise& w = c->dn;
     const size_t n = (size_t)res_x * res_y;
+    if (alb) HIPCHK(c, w.a.reserve(n));
+    const DemodIO dm{alb, w.a.get(), albedo_floor};
     HIPCHK(c, w.g.reserve(n)); HIPCHK(c, w.gz.reserve(n));
     HIPCHK(c, w.cv[0].reserve(n)); HIPCHK(c, w.cv[1].reserve(n));
     DenoiseIO io{};
@@ -2823,17 +2864,24 @@ int denoise_device(rt_ctx* c, const rt_denoise_desc& d, int res_x, int res_y, co
     io.normal_power_log2 = d.normal_power_log2;
     io.sigma_l = d.sigma_l; io.sigma_z = d.sigma_z; io.lum_floor = d.lum_floor; io.depth_floor = d.depth_floor;
     io.cv_out = w.cv[0].get();
-    HIPCHK(c, launch_denoise_prepare(st, io));
+    HIPCHK(c, alb ? launch_denoise_prepare_albedo(st, io, dm) : launch_denoise_prepare(st, io));
     for (int i = 0; i < d.iterations; ++i) {
         io.cv_in = w.cv[i & 1].get();
         io.cv_out = w.cv[(i & 1) ^ 1].get();
         io.step = 1 << i;
-        if (i == d.iterations - 1) {  // the finish is fused into the last iteration
+        if (i == d.iterations - 1 && !alb) {  // the finish is fused into the last iteration
             io.out = out;
             io.var_out = var;
         }
         HIPCHK(c, launch_denoise_iter(st, io, c->knobs.denoise_lds != 0));
     }
+    if (alb) HIPCHK(c, launch_denoise_finish_albedo(st, io, dm, io.cv_out, out, var));
+    return RT_OK;
+}
+
+int albedo_floor_check(rt_ctx* c, float albedo_floor) {
+    if (!std::isfinite(albedo_floor) || !(albedo_floor > 0.f) || albedo_floor > 1.f)
+        return fail(c, RT_E_ARG, "denoise: albedo_floor must be finite and in (0, 1]");
     return RT_OK;
 }
 
@@ -2862,43 +2910,56 @@ int overlap_kind(std::initializer_list<HostRange> outs, std::initializer_list<Ho
 }
 }  // namespace
 
-// rt_render_features (with_pos false: pos is not looked at), rt_render_features_pos and rt_render_features_chain
+// rt_render_features (with_pos false: pos is not looked at), rt_render_features_pos, rt_render_features_chain and, with
+// with_alb, rt_render_features_albedo
 static int impl_rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos, bool with_pos,
-                                   int chain_depth) {
-    if (!c || !feat || (with_pos && !pos)) return RT_E_ARG;
+                                   int chain_depth, rt_albedo* alb, bool with_alb) {
+    if (!c || !feat || (with_pos && !pos) || (with_alb && !alb)) return RT_E_ARG;
     int rc = chain_check_depth(c, chain_depth);
     if (rc) return rc;
     if ((rc = check_ready(c))) return rc;
     if (!c->peers.empty()) return fail(c, RT_E_STATE, "the feature pass supports one-device contexts only");
     hipSetDevice(c->device);
     const size_t n = (size_t)c->film.res_x * c->film.res_y;
-    if (overlap_kind({{feat, n * sizeof(rt_feature)}, {with_pos ? pos : nullptr, n * sizeof(rt_position)}}, {}))
-        return fail(c, RT_E_ARG, "the feature film and the position film overlap");
+    if (overlap_kind({{feat, n * sizeof(rt_feature)}, {with_pos ? pos : nullptr, n * sizeof(rt_position)},
+                      {with_alb ? alb : nullptr, n * sizeof(rt_albedo)}}, {}))
+        return fail(c, RT_E_ARG, with_alb ? "the feature, position and albedo films overlap"
+                                          : "the feature film and the position film overlap");
     DevBuf<float4>& d_feat = c->dn.feat;  // (rt_denoise's feature staging, and the temporal entries' position staging)
     DevBuf<float4>& d_pos = c->tp.s_pos;
+    DevBuf<float4>& d_alb = c->dn.alb;
     hipStream_t st = c->stream;
     rc = ordered(c, st, [&]() -> int {
         int rc;
-        if ((rc = stage_in(c, d_feat, feat, n, st)) || (with_pos && (rc = stage_in(c, d_pos, pos, n, st)))) return rc;
-        return features_device(c, ib, ie, d_feat.get(), st, with_pos ? d_pos.get() : nullptr, chain_depth);
+        if ((rc = stage_in(c, d_feat, feat, n, st)) || (with_pos && (rc = stage_in(c, d_pos, pos, n, st))) ||
+            (with_alb && (rc = stage_in(c, d_alb, alb, n, st))))
+            return rc;
+        return features_device(c, ib, ie, d_feat.get(), st, with_pos ? d_pos.get() : nullptr, chain_depth,
+                               with_alb ? d_alb.get() : nullptr);
     });
-    if (rc || (rc = stage_out(c, feat, d_feat, n, st)) || (with_pos && (rc = stage_out(c, pos, d_pos, n, st)))) return rc;
+    if (rc || (rc = stage_out(c, feat, d_feat, n, st)) || (with_pos && (rc = stage_out(c, pos, d_pos, n, st))) ||
+        (with_alb && (rc = stage_out(c, alb, d_alb, n, st))))
+        return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     return RT_OK;
 }
 
+// rt_denoise and, with with_alb, rt_denoise_albedo
 static int impl_rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int res_y, const rt_pixel* film,
-                           const rt_moment* mom, const rt_feature* feat, rt_pixel* out, float* variance_out) {
+                           const rt_moment* mom, const rt_feature* feat, rt_pixel* out, float* variance_out,
+                           const rt_albedo* alb, bool with_alb, float albedo_floor) {
     if (!c) return RT_E_ARG;
-    if (!d || !film || !mom || !feat || !out)
-        return fail(c, RT_E_ARG, "denoise: descriptor, film, moments, features and out are required");
+    if (!d || !film || !mom || !feat || !out || (with_alb && !alb))
+        return fail(c, RT_E_ARG, with_alb ? "denoise: descriptor, film, moments, features, albedo and out are required"
+                                          : "denoise: descriptor, film, moments, features and out are required");
     if (res_x <= 0 || res_y <= 0) return fail(c, RT_E_ARG, "denoise: the resolution must be positive");
     if ((int64_t)res_x * res_y > ((int64_t)1 << 28)) return fail(c, RT_E_LIMIT, "denoise: more than 2^28 pixels");
     int rc = denoise_check_desc(c, d);
-    if (rc) return rc;
+    if (rc || (with_alb && (rc = albedo_floor_check(c, albedo_floor)))) return rc;
     const size_t n = (size_t)res_x * res_y;
     if (const int k = overlap_kind({{out, n * sizeof(rt_pixel)}, {variance_out, n * sizeof(float)}},
-                                   {{film, n * sizeof(rt_pixel)}, {mom, n * sizeof(rt_moment)}, {feat, n * sizeof(rt_feature)}}))
+                                   {{film, n * sizeof(rt_pixel)}, {mom, n * sizeof(rt_moment)}, {feat, n * sizeof(rt_feature)},
+                                    {with_alb ? alb : nullptr, n * sizeof(rt_albedo)}}))
         return fail(c, RT_E_ARG, k == 1 ? "denoise: an output overlaps an input" : "denoise: variance_out overlaps out");
     hipSetDevice(c->device);
     rt_ctx::Denoise& w = c->dn;
@@ -2907,9 +2968,10 @@ static int impl_rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int r
     rc = ordered(c, st, [&]() -> int {
         int rc;
         if ((rc = stage_in(c, w.film, film, n, st)) || (rc = stage_in(c, w.mom, mom, n, st)) ||
-            (rc = stage_in(c, w.feat, feat, n, st)))
+            (rc = stage_in(c, w.feat, feat, n, st)) || (with_alb && (rc = stage_in(c, w.alb, alb, n, st))))
             return rc;
-        return denoise_device(c, *d, res_x, res_y, w.film.get(), w.mom.get(), w.feat.get(), w.out.get(), w.var.get(), st);
+        return denoise_device(c, *d, res_x, res_y, w.film.get(), w.mom.get(), w.feat.get(), w.out.get(), w.var.get(), st,
+                              with_alb ? w.alb.get() : nullptr, albedo_floor);
     });
     if (rc || (rc = stage_out(c, out, w.out, n, st)) || (variance_out && (rc = stage_out(c, variance_out, w.var, n, st))))
         return rc;
@@ -2917,33 +2979,50 @@ static int impl_rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int r
     return RT_OK;
 }
 
-static int impl_rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixel* film_out) {
+// rt_adaptive_denoise and, with with_alb, rt_adaptive_denoise_albedo
+static int impl_rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixel* film_out, bool with_alb,
+                                    float albedo_floor) {
     if (!c) return RT_E_ARG;
     if (!d || !film_out) return fail(c, RT_E_ARG, "adaptive denoise: descriptor and film_out are required");
     rt_ctx::Adaptive& a = c->ad;
     if (!a.live) return fail(c, RT_E_STATE, "no adaptive session is open (rt_adaptive_begin first)");
     int rc = check_ready(c);
     if (rc) return rc;
-    if ((rc = denoise_check_desc(c, d))) return rc;
+    if ((rc = denoise_check_desc(c, d)) || (with_alb && (rc = albedo_floor_check(c, albedo_floor)))) return rc;
     if (d->feature_samples > dev_sampler(c).spp)
         return fail(c, RT_E_ARG, "adaptive denoise: feature_samples exceeds the sampler's samples per pixel");
     hipSetDevice(c->device);
     const size_t n = (size_t)c->film.res_x * c->film.res_y;
     HIPCHK(c, a.feat.reserve(n));
+    if (with_alb) HIPCHK(c, a.alb.reserve(n));
     HIPCHK(c, c->dn.out.reserve(n));
     hipStream_t st = c->stream;
     rc = ordered(c, st, [&]() -> int {
-        // once per session (again only if the caller changes k or the chain depth)
-        if (a.feat_k != d->feature_samples || a.feat_chain != d->chain_depth) {
+        // once per session (again only if the caller changes k or the chain depth); the albedo film is rendered with the
+        // features, which come out as the feature pass alone leaves them
+        const bool feat_ok = a.feat_k == d->feature_samples && a.feat_chain == d->chain_depth;
+        const bool alb_ok = !with_alb || (a.alb_k == d->feature_samples && a.alb_chain == d->chain_depth);
+        if (!feat_ok || !alb_ok) {
             a.feat_k = 0;
             if (hipMemsetAsync(a.feat.get(), 0, n * sizeof(float4), st) != hipSuccess)
                 return fail(c, RT_E_HIP, "feature film memset");
-            if (int rc = features_device(c, 0, d->feature_samples, a.feat.get(), st, nullptr, d->chain_depth)) return rc;
+            if (with_alb) {
+                a.alb_k = 0;
+                if (hipMemsetAsync(a.alb.get(), 0, n * sizeof(float4), st) != hipSuccess)
+                    return fail(c, RT_E_HIP, "albedo film memset");
+            }
+            if (int rc = features_device(c, 0, d->feature_samples, a.feat.get(), st, nullptr, d->chain_depth,
+                                         with_alb ? a.alb.get() : nullptr))
+                return rc;
             a.feat_k = d->feature_samples;
             a.feat_chain = d->chain_depth;
+            if (with_alb) {
+                a.alb_k = d->feature_samples;
+                a.alb_chain = d->chain_depth;
+            }
         }
         return denoise_device(c, *d, c->film.res_x, c->film.res_y, a.film.get(), a.mom.get(), a.feat.get(),
-                              c->dn.out.get(), nullptr, st);
+                              c->dn.out.get(), nullptr, st, with_alb ? a.alb.get() : nullptr, albedo_floor);
     });
     if (rc || (rc = stage_out(c, film_out, c->dn.out, n, st))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
@@ -3606,6 +3685,7 @@ static int impl_rt_scene_set_textures(rt_ctx* c, const rt_texture_desc* d) {
     rt_ctx::Textures& T = c->tx;
     std::vector<int4> recs(d->n_textures);
     HIPCHK(c, T.texels.reserve((size_t)total));
+    T.n_texels = (size_t)total;
     {
         DevBuf<unsigned char> bytes;  // one texture's RGB8 at a time
         size_t base = 0;
@@ -3678,6 +3758,26 @@ static int impl_rt_debug_texture_eval(rt_ctx* c, int n, const int32_t* prim, con
             hipMemcpy(h.data(), dc.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(c, RT_E_HIP, std::string("texture eval: ") + hipGetErrorString(hipGetLastError()));
         for (int i = 0; i < n; ++i) { coeffs[3 * i] = h[i].x; coeffs[3 * i + 1] = h[i].y; coeffs[3 * i + 2] = h[i].z; }
+        return RT_OK;
+    });
+}
+
+// the albedo bake kernel alone, on explicit coefficients under the current sensor
+static int impl_rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
+    if (!c || n < 0 || (n && (!coeffs || !rgb))) return c ? fail(c, RT_E_ARG, "albedo bake: invalid argument") : RT_E_ARG;
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float4> in, out;
+        if (in.reserve(n) || out.reserve(n)) return fail(c, RT_E_OOM, "albedo bake buffers");
+        std::vector<float4> h(n);
+        for (int i = 0; i < n; ++i) h[i] = make_float4(coeffs[3 * i], coeffs[3 * i + 1], coeffs[3 * i + 2], 0.f);
+        if (hipMemcpy(in.get(), h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_albedo_bake(c->stream, c->d_spec.get(), 0, nullptr, n, in.get(), out.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(h.data(), out.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("albedo bake: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) { rgb[3 * i] = h[i].x; rgb[3 * i + 1] = h[i].y; rgb[3 * i + 2] = h[i].z; }
         return RT_OK;
     });
 }
@@ -3831,20 +3931,32 @@ int rt_debug_adaptive_select(rt_ctx* c, const rt_adaptive_desc* d, const rt_pixe
     return entry(c, impl_rt_debug_adaptive_select, d, film, mom, block_error, active, n_active);
 }
 int rt_render_features(rt_ctx* c, int ib, int ie, rt_feature* feat) {
-    return entry(c, impl_rt_render_features, ib, ie, feat, nullptr, false, 0);
+    return entry(c, impl_rt_render_features, ib, ie, feat, nullptr, false, 0, nullptr, false);
 }
 int rt_denoise(rt_ctx* c, const rt_denoise_desc* d, int res_x, int res_y, const rt_pixel* film, const rt_moment* mom,
                const rt_feature* feat, rt_pixel* out, float* variance_out) {
-    return entry(c, impl_rt_denoise, d, res_x, res_y, film, mom, feat, out, variance_out);
+    return entry(c, impl_rt_denoise, d, res_x, res_y, film, mom, feat, out, variance_out, nullptr, false, 0.f);
+}
+int rt_denoise_albedo(rt_ctx* c, const rt_denoise_desc* d, float albedo_floor, int res_x, int res_y, const rt_pixel* film,
+                      const rt_moment* mom, const rt_feature* feat, const rt_albedo* albedo, rt_pixel* out,
+                      float* variance_out) {
+    return entry(c, impl_rt_denoise, d, res_x, res_y, film, mom, feat, out, variance_out, albedo, true, albedo_floor);
 }
 int rt_adaptive_denoise(rt_ctx* c, const rt_denoise_desc* d, rt_pixel* film_out) {
-    return entry(c, impl_rt_adaptive_denoise, d, film_out);
+    return entry(c, impl_rt_adaptive_denoise, d, film_out, false, 0.f);
+}
+int rt_adaptive_denoise_albedo(rt_ctx* c, const rt_denoise_desc* d, float albedo_floor, rt_pixel* film_out) {
+    return entry(c, impl_rt_adaptive_denoise, d, film_out, true, albedo_floor);
 }
 int rt_render_features_chain(rt_ctx* c, int ib, int ie, int chain_depth, rt_feature* feat, rt_position* pos) {
-    return entry(c, impl_rt_render_features, ib, ie, feat, pos, pos != nullptr, chain_depth);
+    return entry(c, impl_rt_render_features, ib, ie, feat, pos, pos != nullptr, chain_depth, nullptr, false);
+}
+int rt_render_features_albedo(rt_ctx* c, int ib, int ie, int chain_depth, rt_feature* feat, rt_position* pos,
+                              rt_albedo* albedo) {
+    return entry(c, impl_rt_render_features, ib, ie, feat, pos, pos != nullptr, chain_depth, albedo, true);
 }
 int rt_render_features_pos(rt_ctx* c, int ib, int ie, rt_feature* feat, rt_position* pos) {
-    return entry(c, impl_rt_render_features, ib, ie, feat, pos, true, 0);
+    return entry(c, impl_rt_render_features, ib, ie, feat, pos, true, 0, nullptr, false);
 }
 int rt_temporal_accumulate(rt_ctx* c, const rt_temporal_desc* d, int res_x, int res_y, const rt_pixel* film,
                            const rt_moment* mom, const rt_feature* feat, const rt_position* pos, const rt_pixel* hist_film,
@@ -3901,6 +4013,9 @@ int rt_debug_texture_bake(rt_ctx* c, int n, const uint8_t* rgb, float* coeffs) {
 }
 int rt_debug_texture_eval(rt_ctx* c, int n, const int32_t* prim, const float* b, int32_t* texel, float* coeffs) {
     return entry(c, impl_rt_debug_texture_eval, n, prim, b, texel, coeffs);
+}
+int rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
+    return entry(c, impl_rt_debug_albedo_bake, n, coeffs, rgb);
 }
 int rt_texel_index(int width, int height, int wrap, float u, float v) {
     if (width < 1 || height < 1 || (wrap != RT_TEX_CLAMP && wrap != RT_TEX_REPEAT)) return RT_E_ARG;

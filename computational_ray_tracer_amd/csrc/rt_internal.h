@@ -650,6 +650,33 @@ hipError_t launch_texture_bake(hipStream_t st, const float* table, int n, const 
 // within its texture or -1, coeffs[i] = the (c0, c1, c2, 0) the shade would use.  tex == nullptr: no textures.
 hipError_t launch_texture_eval(hipStream_t st, const DevScene& sc, const DevTex* tex, int n, const int* prim,
                                const float* b, int* texel, float4* coeffs);
+
+// Albedo demodulation.  rt_albedo.hip: the sensor albedo table and the albedo film; rt_denoise.hip: the
+// demodulating prepare and the remodulating finish around the unchanged iterations.
+// bake: entry i < n_mat is materials[i]'s (c0, c1, c2), entry n_mat + j is coeffs[j]'s (a scene's texel array, or
+// explicit triples); out[i] = (A_r, A_g, A_b, 0) under sp's sensor curves.  n_mat + n_coeffs < 2^31.
+hipError_t launch_albedo_bake(hipStream_t st, const DevSpectra* sp, int n_mat, const DevMaterial* mats, int n_coeffs,
+                              const float4* coeffs, float4* out);
+// film: k_feature_film's loop over the batch's first hits, adding (A, 1) or (1, 1, 1, 1) per hit to alb (res_x * res_y)
+struct AlbedoFilmIO {
+    const int* work_pixels; int n_pixels; int n_index;
+    const float4* hitB; const int* hitPrim;
+    const float4* table;          // the baked table: n_materials material entries, then the scene's texels
+    const DevTex* tex;            // null: the scene has no textures
+    int reference;                // RT_INTEGRATOR_REFERENCE: every hit adds (1, 1, 1, 1)
+    float4* alb;
+};
+hipError_t launch_albedo_film(hipStream_t st, const DevScene& sc, const AlbedoFilmIO& io);
+// the filter's albedo variant: prepare also reads alb and writes a = (a.rgb, sa) and the demodulated (c, var); finish
+// turns the last iteration's cv = (c', var') into out = ((c' a) n, n) and var_out (may be null) = var' (sa sa)
+struct DemodIO {
+    const float4* alb;            // the albedo film
+    float4* a;                    // res_x * res_y workspace
+    float floor;
+};
+hipError_t launch_denoise_prepare_albedo(hipStream_t st, const DenoiseIO& io, const DemodIO& dm);
+hipError_t launch_denoise_finish_albedo(hipStream_t st, const DenoiseIO& io, const DemodIO& dm, const float4* cv,
+                                        float4* out, float* var_out);
 // the loaded coefficient table (rt_color.cpp), false when the file is missing
 bool rgb_table_host(const float** z, const float** coeffs);
 

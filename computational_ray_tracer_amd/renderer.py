@@ -23,6 +23,11 @@ CHAIN_DEFAULTS = dict(chain_depth=0)
 CHAIN_CURVED_DEFAULT = False
 
 
+# albedo_floor of the demodulating filter (rt_denoise_albedo): frozen on the oracle's textured floor at
+# 16 spp against the float64 closed form (tests/test_albedo_reference.py), among {1/256, 1/64, 1/16}
+ALBEDO_FLOOR_DEFAULT = 1.0 / 256
+
+
 def chain_arg(chain_depth, chain_curved=CHAIN_CURVED_DEFAULT):
     """The chain_depth value of the C ABI: the depth, with capi.RT_CHAIN_CURVED set when chain_curved."""
     return int(chain_depth) | (capi.RT_CHAIN_CURVED if chain_curved else 0)
@@ -222,10 +227,40 @@ class Renderer:
                                                                     feat.ctypes.data_as(C.POINTER(capi.rt_feature))))
         return feat
 
-    def denoise(self, film, mom, feat, res=None, variance=False, **desc):
+    def render_features_albedo(self, index_begin, index_end, chain_depth=0, feat=None, pos=None, albedo=None,
+                               with_pos=True, chain_curved=CHAIN_CURVED_DEFAULT):
+        """rt_render_features_albedo: render_features_chain that also accumulates the first-hit albedo film (sensor-RGB
+        albedo sums and hit count, float32 [W*H, 4]).  Returns (feat, pos, albedo); with_pos=False:
+        (feat, albedo)."""
+        feat = self.new_film() if feat is None else feat
+        albedo = self.new_film() if albedo is None else albedo
+        if with_pos:
+            pos = self.new_film() if pos is None else pos
+        for a in (feat, pos, albedo) if with_pos else (feat, albedo):
+            assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (self.res[0] * self.res[1], 4)
+        self._chk("rt_render_features_albedo", self.lib.rt_render_features_albedo(
+            self.h, index_begin, index_end, chain_arg(chain_depth, chain_curved),
+            feat.ctypes.data_as(C.POINTER(capi.rt_feature)),
+            pos.ctypes.data_as(C.POINTER(capi.rt_position)) if with_pos else None,
+            albedo.ctypes.data_as(C.POINTER(capi.rt_albedo))))
+        return (feat, pos, albedo) if with_pos else (feat, albedo)
+
+    def albedo_bake(self, coeffs):
+        """rt_debug_albedo_bake: the albedo bake kernel alone on (..., 3) float32 sigmoid coefficients -> (..., 3)
+        float32 sensor-RGB albedo under the current film's sensor."""
+        a = np.ascontiguousarray(coeffs, np.float32)
+        assert a.ndim >= 1 and a.shape[-1] == 3
+        out = np.zeros(a.shape, np.float32)
+        self._chk("rt_debug_albedo_bake", self.lib.rt_debug_albedo_bake(
+            self.h, a.size // 3, a.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def denoise(self, film, mom, feat, res=None, variance=False, albedo=None, albedo_floor=ALBEDO_FLOOR_DEFAULT,
+                **desc):
         """rt_denoise on host arrays of `res` (default: the film's): film [N, 4], moments [N, 2], features [N, 4] of
         desc feature_samples indices -> the filtered film [N, 4] (and the filtered variance [N] with variance=True).
-        Descriptor fields default to DENOISE_DEFAULTS."""
+        albedo [N, 4] (render_features_albedo): rt_denoise_albedo, which filters the film divided by the albedo, floored
+        at albedo_floor, and multiplies it back.  Descriptor fields default to DENOISE_DEFAULTS."""
         W, H = res or self.res
         film = np.ascontiguousarray(film, np.float32)
         mom = np.ascontiguousarray(mom, np.float32)
@@ -234,30 +269,44 @@ class Renderer:
         d = self._denoise_desc(**desc)
         out = np.zeros((W * H, 4), np.float32)
         var = np.zeros(W * H, np.float32) if variance else None
-        self._chk("rt_denoise", self.lib.rt_denoise(
-            self.h, C.byref(d), W, H, film.ctypes.data_as(C.POINTER(capi.rt_pixel)),
-            mom.ctypes.data_as(C.POINTER(capi.rt_moment)), feat.ctypes.data_as(C.POINTER(capi.rt_feature)),
-            out.ctypes.data_as(C.POINTER(capi.rt_pixel)),
-            None if var is None else var.ctypes.data_as(C.POINTER(C.c_float))))
+        tail = (out.ctypes.data_as(C.POINTER(capi.rt_pixel)),
+                None if var is None else var.ctypes.data_as(C.POINTER(C.c_float)))
+        head = (film.ctypes.data_as(C.POINTER(capi.rt_pixel)), mom.ctypes.data_as(C.POINTER(capi.rt_moment)),
+                feat.ctypes.data_as(C.POINTER(capi.rt_feature)))
+        if albedo is None:
+            self._chk("rt_denoise", self.lib.rt_denoise(self.h, C.byref(d), W, H, *head, *tail))
+        else:
+            albedo = np.ascontiguousarray(albedo, np.float32)
+            assert albedo.shape == (W * H, 4)
+            self._chk("rt_denoise_albedo", self.lib.rt_denoise_albedo(
+                self.h, C.byref(d), float(albedo_floor), W, H, *head, albedo.ctypes.data_as(C.POINTER(capi.rt_albedo)),
+                *tail))
         return (out, var) if variance else out
 
-    def adaptive_denoise(self, **desc):
+    def adaptive_denoise(self, demodulate=False, albedo_floor=ALBEDO_FLOOR_DEFAULT, **desc):
         """rt_adaptive_denoise: the open session's film filtered on the device (features rendered once per session);
-        the session is left as it was."""
+        the session is left as it was.  demodulate=True: rt_adaptive_denoise_albedo, with a session-owned albedo film
+        rendered with the features."""
         d = self._denoise_desc(**desc)
         out = self.new_film()
-        self._chk("rt_adaptive_denoise", self.lib.rt_adaptive_denoise(self.h, C.byref(d),
-                                                                      out.ctypes.data_as(C.POINTER(capi.rt_pixel))))
+        if demodulate:
+            self._chk("rt_adaptive_denoise_albedo", self.lib.rt_adaptive_denoise_albedo(
+                self.h, C.byref(d), float(albedo_floor), out.ctypes.data_as(C.POINTER(capi.rt_pixel))))
+        else:
+            self._chk("rt_adaptive_denoise", self.lib.rt_adaptive_denoise(self.h, C.byref(d),
+                                                                          out.ctypes.data_as(C.POINTER(capi.rt_pixel))))
         return out
 
-    def render_denoised(self, min_samples, step_samples, max_samples, rel_error, abs_floor=1e-3, **desc):
-        """Adaptive session -> denoise -> end: (filtered film, info dict of the session)."""
+    def render_denoised(self, min_samples, step_samples, max_samples, rel_error, abs_floor=1e-3, demodulate=False,
+                        albedo_floor=ALBEDO_FLOOR_DEFAULT, **desc):
+        """Adaptive session -> denoise -> end: (filtered film, info dict of the session).  demodulate=True filters the
+        film divided by its first-hit albedo, which keeps the detail of an albedo texture."""
         self.adaptive_begin(min_samples, step_samples, max_samples, rel_error, abs_floor)
         try:
             info = self.adaptive_step()
             while info["active_pixels"] > 0 and info["index_done"] < max_samples:
                 info = self.adaptive_step()
-            return self.adaptive_denoise(**desc), info
+            return self.adaptive_denoise(demodulate=demodulate, albedo_floor=albedo_floor, **desc), info
         finally:
             self.adaptive_end()
 

@@ -525,6 +525,48 @@ int rt_debug_texture_bake(rt_ctx* ctx, int n, const uint8_t* rgb, float* coeffs)
  * texture, or -1 for an untextured triangle, and coeffs[3i..] = the (c0, c1, c2) the shade would use. */
 int rt_debug_texture_eval(rt_ctx* ctx, int n, const int32_t* prim, const float* b, int32_t* texel, float* coeffs);
 
+/* ---- albedo demodulation for the denoiser (additive) ------------------------------
+ * The filter divides the film by a noise-free first-hit albedo, filters the demodulated irradiance (smooth across the
+ * edges of an albedo texture) and multiplies the albedo back.  All arithmetic is float32 in the order written, unfused,
+ * with only + - * /, sqrtf and fmaxf, as rt_denoise's (build-defined; tests/albedo_reference.py restates it).
+ *
+ * The albedo lives in the film's channel space, sensor RGB.  Every emitter is a multiple of D65, so a Lambert surface
+ * of reflectance R scales channel c of directly lit radiance by
+ *   A_c = sum_k (bar_c[k] D65[k]) R(360 + k) / sum_k bar_c[k] D65[k],   k = 0..470 ascending, both sums from 0,
+ * bar_c the current film's sensor curves, R(l) = 0.5f + x / (2 sqrtf(1 + x x)), x = (l c0 + c1) l + c2 (1 or 0 by
+ * the sign of an infinite x).  The context keeps A of every material and every texel of the scene in a lazily built
+ * table (16 B per entry; rebuilt on first use after rt_scene_upload, rt_scene_set_textures or rt_film_set; a context
+ * that never asks for albedo bakes nothing). */
+typedef struct { float r, g, b, hits; } rt_albedo;        /* 16 B, sums over the pass's hits */
+/* rt_render_features_chain that also accumulates (+=) the albedo film albedo_inout (res_x*res_y, host memory);
+ * feat_inout and pos_inout (may be NULL) come out exactly as rt_render_features_chain leaves them.  The albedo is
+ * always the FIRST hit's, at any chain_depth.  Per sample, in increasing index order: a miss adds nothing; under
+ * RT_INTEGRATOR_REFERENCE (no material is consulted) a hit adds (1, 1, 1, 1); otherwise the hit's material is the
+ * triangle's, or the analytic shape's (no texture lookup), and an emitter, a mirror or a dielectric adds (1, 1, 1, 1)
+ * (emitters and specular surfaces are not demodulated); any other hit adds (A.r, A.g, A.b, 1) with A of the texel that
+ * the hit's barycentrics select when the material has a texture, else of the material.
+ * Work list, shards, rt_stats, error codes and multi-device contexts as rt_render_features. */
+int rt_render_features_albedo(rt_ctx* ctx, int index_begin, int index_end, int chain_depth, rt_feature* feat_inout,
+                              rt_position* pos_inout, rt_albedo* albedo_inout);
+/* rt_denoise with demodulation by the albedo film `albedo` (res_x*res_y, host memory).  Per pixel, h = albedo.hits:
+ *   a_c = h > 0 ? fmaxf(albedo_c / h, albedo_floor) : 1;   c = (film.rgb / n) / a;   sa = ((a.r + a.g) + a.b) / 3.f;
+ *   var = var / (sa sa)   (var as rt_denoise computes it);  guides and depth gradient as rt_denoise;
+ * rt_denoise's iterations, untouched, on (c, var); then
+ *   out = ((c'.r a.r) n, (c'.g a.g) n, (c'.b a.b) n, n),   variance_out = var' (sa sa).
+ * An albedo film of all (k, k, k, k) gives rt_denoise's bits.  albedo_floor must be finite and in (0, 1] (RT_E_ARG
+ * otherwise); NULL and overlap rules as rt_denoise, with albedo an input. */
+int rt_denoise_albedo(rt_ctx* ctx, const rt_denoise_desc* desc, float albedo_floor, int res_x, int res_y,
+                      const rt_pixel* film, const rt_moment* mom, const rt_feature* feat, const rt_albedo* albedo,
+                      rt_pixel* out, float* variance_out);
+/* rt_adaptive_denoise with a session-owned device albedo film of indices [0, feature_samples), rendered with the
+ * features once per session (again when feature_samples or chain_depth change).  The session's film, moments and
+ * active list are untouched.  rt_adaptive_denoise itself neither renders nor allocates an albedo film.
+ * Multi-device contexts: RT_E_STATE, as the feature pass. */
+int rt_adaptive_denoise_albedo(rt_ctx* ctx, const rt_denoise_desc* desc, float albedo_floor, rt_pixel* film_out);
+/* The bake kernel alone: n coefficient triples (3n floats) -> 3n floats (A_r, A_g, A_b) under the current film's
+ * sensor (the XYZ sensor until rt_film_set). */
+int rt_debug_albedo_bake(rt_ctx* ctx, int n, const float* coeffs, float* rgb);
+
 /* ---- instrumentation ---------------------------------------------------------------------------- */
 int rt_get_stats(rt_ctx* ctx, rt_stats* out);
 int rt_reset_stats(rt_ctx* ctx);
