@@ -16,7 +16,7 @@ STATUS_NAMES = {0: "RT_OK", -1: "RT_E_ARG", -2: "RT_E_HIP", -3: "RT_E_RCCL", -4:
                 -6: "RT_E_NODEVICE", -7: "RT_E_LIMIT"}
 RT_MAT_DIFFUSE, RT_MAT_MIRROR, RT_MAT_DIELECTRIC = 0, 1, 2
 RT_SHAPE_SPHERE, RT_SHAPE_DISK, RT_SHAPE_TRIANGLE = 0, 1, 2
-RT_LIGHT_QUAD, RT_LIGHT_DISK, RT_LIGHT_POINT, RT_LIGHT_DISTANT = 0, 1, 2, 3
+RT_LIGHT_QUAD, RT_LIGHT_DISK, RT_LIGHT_POINT, RT_LIGHT_DISTANT, RT_LIGHT_MESH = 0, 1, 2, 3, 4
 RT_CAMERA_PERSPECTIVE, RT_CAMERA_ORTHOGRAPHIC, RT_CAMERA_PINHOLE, RT_CAMERA_THINLENS = 0, 1, 2, 3
 RT_SAMPLER_INDEPENDENT, RT_SAMPLER_STRATIFIED, RT_SAMPLER_SOBOL = 0, 1, 2
 RT_SOBOL_NONE, RT_SOBOL_PERMUTE_DIGITS, RT_SOBOL_FAST_OWEN, RT_SOBOL_OWEN = 0, 1, 2, 3
@@ -195,6 +195,7 @@ EXPORTS = [
     "rt_temporal_frame_guided", "rt_temporal_block_error",
     "rt_scene_set_textures", "rt_texel_index", "rt_debug_texture_bake", "rt_debug_texture_eval",
     "rt_render_features_albedo", "rt_denoise_albedo", "rt_adaptive_denoise_albedo", "rt_debug_albedo_bake",
+    "rt_debug_meshlight_table", "rt_debug_light_sample",
 ]
 
 _lib = None
@@ -302,6 +303,9 @@ def load_library(path=None):
                                P(rt_feature), P(rt_albedo), P(rt_pixel), P(C.c_float)], C.c_int),
         "rt_adaptive_denoise_albedo": ([C.c_void_p, P(rt_denoise_desc), C.c_float, P(rt_pixel)], C.c_int),
         "rt_debug_albedo_bake": ([C.c_void_p, C.c_int, P(C.c_float), P(C.c_float)], C.c_int),
+        "rt_debug_meshlight_table": ([C.c_void_p, C.c_int, P(C.c_int), P(C.c_int32), P(C.c_float), P(C.c_float)], C.c_int),
+        "rt_debug_light_sample": ([C.c_void_p, C.c_int, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                   P(C.c_float), P(C.c_float), P(C.c_int32)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

@@ -741,6 +741,75 @@ RT_DEV float fr_dielectric(float cosi, float eta) {
     float r_perp = (cosi - eta * cost) / (cosi + eta * cost);
     return (r_parl * r_parl + r_perp * r_perp) / 2;
 }
+// The shadow ray toward one light sample (Lights.h semantics): area lights (quad: p + u0 e1 + u1 e2;
+// disk: the concentric mapping of the Disk shape) and point lights aim at the point, tMax = 0.999 dist; a distant
+// light's direction is fixed (tMax = FLT_MAX; u0, u1 are drawn and unused).  k_path_shade_full evaluates it for the
+// light weights and k_path_nee again for the ray: the same code on the same inputs, so the same bits.
+// ML (the mesh-light instantiations): an RT_LIGHT_MESH picks the triangle i with the smallest
+// cdf_i > u0 (binary search of the light's table), remaps u0 to the triangle's cdf step, and takes a uniform point of
+// the triangle (pbrt-v4 SampleUniformTriangle); ms returns the triangle's geometric normal and its id.  Without ML
+// the function holds none of it and ms is left alone.
+struct LightRay {
+    V3 wi;
+    float tmax, dist2;
+};
+struct MeshSample {
+    V3 nl;
+    int tri;
+};
+template <bool ML = false>
+RT_DEV LightRay light_ray(const DevLight& Lt, V3 po, float u0, float u1, const float4* triWorld, MeshSample& ms) {
+    LightRay r;
+    if (Lt.type == 3) {
+        r.wi = v3(Lt.dir[0], Lt.dir[1], Lt.dir[2]);
+        r.tmax = 3.402823466e+38f;
+        r.dist2 = 1.0f;
+        return r;
+    }
+    V3 pl;
+    if (Lt.type == 0) {
+        pl = vadd(vadd(v3(Lt.p[0], Lt.p[1], Lt.p[2]), vmul(v3(Lt.e1[0], Lt.e1[1], Lt.e1[2]), u0)),
+                  vmul(v3(Lt.e2[0], Lt.e2[1], Lt.e2[2]), u1));
+    } else if (Lt.type == 1) {
+        float dx, dy;
+        disk_concentric(u0, u1, dx, dy);
+        pl = m4_point(Lt.o2r, v3(Lt.ro * dx, Lt.ro * dy, Lt.h));
+    } else if (ML && Lt.type == 4) {
+        const MeshLightTab T = meshlight_tab(Lt);
+        int lo = 0, hi = T.n - 1;  // (u0 < 1 = cdf[n - 1]; a u0 of exactly 1 stays inside the table as well)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (u0 < T.cdf[mid]) hi = mid;
+            else lo = mid + 1;
+        }
+        const float c0 = lo > 0 ? T.cdf[lo - 1] : 0.f, c1 = T.cdf[lo];
+        const float up = fminf((u0 - c0) / (c1 - c0), 0x1.fffffep-1f);
+        const int t = T.tri[lo];
+        const float4 P0 = triWorld[3 * t], P1 = triWorld[3 * t + 1], P2 = triWorld[3 * t + 2];
+        const V3 p0 = v3(P0.x, P0.y, P0.z), p1 = v3(P1.x, P1.y, P1.z), p2 = v3(P2.x, P2.y, P2.z);
+        float b0, b1;
+        if (up < u1) {
+            b0 = up / 2;
+            b1 = u1 - b0;
+        } else {
+            b1 = u1 / 2;
+            b0 = up - b1;
+        }
+        const float b2 = (1 - b0) - b1;
+        pl = vadd(vadd(vmul(p0, b0), vmul(p1, b1)), vmul(p2, b2));
+        ms.nl = vnorm(vcross(vsub(p0, p2), vsub(p1, p2)));
+        ms.tri = t;
+    } else {
+        pl = v3(Lt.p[0], Lt.p[1], Lt.p[2]);
+    }
+    const V3 wv = vsub(pl, po);
+    r.dist2 = vdot(wv, wv);
+    const float dist = sqrtf(r.dist2);
+    r.wi = vmul(wv, 1.0f / dist);
+    r.tmax = dist * 0.999f;
+    return r;
+}
+
 RT_DEV bool refract_dir(V3 wi, V3 n, float eta, float& etap, V3& wt) {
     float cosi = vdot(n, wi);
     if (cosi < 0) { eta = 1 / eta; cosi = -cosi; n = v3(-n.x, -n.y, -n.z); }

@@ -614,6 +614,16 @@ struct rt_ctx {
     DevScene dsc{};
     std::vector<DevBuf<unsigned char>> scene_allocs;  // the arrays dsc points to
     const float* d_kappa = nullptr;  // per analytic shape: the curvature the curved chain guides use (in scene_allocs)
+    // mesh lights of the uploaded scene: per light its slice (first, n) of the shared id and cdf arrays
+    // (n = 0: not a mesh light) and its total area; the arrays themselves are in scene_allocs.  any = the path kernels
+    // run their ML instantiations.
+    struct MeshLights {
+        bool any = false;
+        std::vector<int> first, n;
+        std::vector<float> area;
+        const int* tri = nullptr;
+        const float* cdf = nullptr;
+    } ml;
     // albedo textures of the uploaded scene (rt_scene_set_textures): live = the path kernels run their TEX
     // instantiations on dev (the DevTex in device memory that points to the other arrays).  table: the RGB -> sigmoid
     // coefficient table (kRgbRes z-nodes, then kRgbTableFloats coefficients), uploaded once per context on first use.
@@ -763,6 +773,7 @@ void free_scene(rt_ctx* c) {
     c->scene_allocs.clear();
     c->dsc = DevScene{};
     c->d_kappa = nullptr;
+    c->ml = rt_ctx::MeshLights{};
     c->have_scene = false;
 }
 
@@ -1448,6 +1459,7 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, 
                                 qc_cur + kQNeeFallback, sort_nee ? ns.key : nullptr, c->sort_lo, c->sort_scale,
                                 kn.sort_nee_bits};
                 if (c->tx.live) nio.tex = c->tx.dev.get();
+                nio.ml = c->ml.any ? 1 : 0;
                 e0 = ev_start(c, s);
                 if (bins) {  // the hits binned by material, then one kernel per bin over its index list
                     HIPCHK(c, launch_bin_materials(s, grid, dsl, bio));
@@ -1918,6 +1930,20 @@ static std::string validate_scene(const rt_scene_desc* s, bool geometry_only = f
                 return "disk light needs an emissive full DISK shape with inner radius 0";
         } else if (L.type == RT_LIGHT_DISTANT) {
             if (L.dir[0] == 0 && L.dir[1] == 0 && L.dir[2] == 0) return "distant light direction";
+        } else if (L.type == RT_LIGHT_MESH) {
+            // (that a non-degenerate triangle uses the material is checked once the world triangles exist:
+            // scene_upload_one)
+            if (!mat_ok(L.material) || !(s->materials && s->materials[L.material].emission_scale > 0))
+                return "mesh light needs an emissive material";
+            for (int h = 0; h < s->n_shapes; ++h)
+                if (s->shapes[h].material == L.material)
+                    return "mesh light material is used by an analytic shape (mesh lights are triangles only)";
+            // DevMaterial.light names one light: no other light of any type may stand behind this material
+            for (int j = 0; j < s->n_lights; ++j) {
+                const rt_light& O = s->lights[j];
+                if (j != i && (O.type == RT_LIGHT_QUAD || O.type == RT_LIGHT_MESH) && O.material == L.material)
+                    return "mesh light material is named by another light";
+            }
         } else if (L.type != RT_LIGHT_POINT) {
             return "unknown light type";
         }
@@ -2086,6 +2112,9 @@ struct ShadingArrays {
     // the emissive surfaces, for the last depth's emitter filter (EmitIO): non-degenerate triangles and shapes whose
     // material emits
     std::vector<int> etris, eshapes;
+    // mesh lights: per light its slice (first, n) of ml_tri, the non-degenerate triangles of the
+    // light's material in ascending id (n = 0: not a mesh light)
+    std::vector<int> ml_first, ml_n, ml_tri;
     bool full = false;              // the scene needs the general path-shade kernel
 };
 // The curvature magnitude the curved chain guides give a shape: 1 / (radius sigma) for a sphere whose
@@ -2170,8 +2199,21 @@ static void shading_arrays(const rt_scene_desc* s, const SceneWorld& sw, Shading
         } else if (q.type == RT_LIGHT_DISTANT) {
             F3 d = f3norm(F3{q.dir[0], q.dir[1], q.dir[2]});
             L.dir[0] = d.x; L.dir[1] = d.y; L.dir[2] = d.z;
+        } else if (q.type == RT_LIGHT_MESH) {
+            // (p, e1, e2 and area are set from the device table: upload_scene, mesh_light_tables)
+            for (int k = 0; k < 3; ++k) L.p[k] = L.e1[k] = L.e2[k] = L.n[k] = 0.f;
+            mats[q.material].light = i;  // (validate_scene: no other light names this material)
         }
         if (q.type != RT_LIGHT_QUAD) full = true;
+    }
+    a.ml_first.assign(s->n_lights, 0);
+    a.ml_n.assign(s->n_lights, 0);
+    for (int i = 0; i < s->n_lights; ++i) {
+        if (s->lights[i].type != RT_LIGHT_MESH) continue;
+        a.ml_first[i] = (int)a.ml_tri.size();
+        for (int t = 0; t < nt; ++t)
+            if (!sw.degen[t] && a.tm[t] == s->lights[i].material) a.ml_tri.push_back(t);
+        a.ml_n[i] = (int)a.ml_tri.size() - a.ml_first[i];
     }
     a.full = full;
     for (int t = 0; t < nt; ++t)
@@ -2233,6 +2275,43 @@ static int upload_array(rt_ctx* c, const std::vector<T>& v, const T*& dst) {
     return RT_OK;
 }
 
+// The device tables of the scene's mesh lights, built by k_meshlight_table from the resident world
+// triangles, and each mesh light's DevLight words: its slice of the shared id and cdf arrays and its total area.
+static int mesh_light_tables(rt_ctx* c, const ShadingArrays& a, const float4* triWorld, std::vector<DevLight>& lights) {
+    rt_ctx::MeshLights& M = c->ml;
+    M.first = a.ml_first;
+    M.n = a.ml_n;
+    M.area.assign(lights.size(), 0.f);
+    std::vector<int> jobs, job_light;
+    for (size_t i = 0; i < lights.size(); ++i)
+        if (a.ml_n[i] > 0) { jobs.push_back(a.ml_first[i]); jobs.push_back(a.ml_n[i]); job_light.push_back((int)i); }
+    if (job_light.empty()) return RT_OK;
+    const int nj = (int)job_light.size();
+    std::vector<float> zeros(a.ml_tri.size(), 0.f), zarea(nj, 0.f);
+    const int* d_jobs = nullptr;
+    const float *d_sums = nullptr, *d_area = nullptr;
+    int rc;
+    if ((rc = upload_array(c, a.ml_tri, M.tri)) || (rc = upload_array(c, zeros, M.cdf)) ||
+        (rc = upload_array(c, zeros, d_sums)) || (rc = upload_array(c, jobs, d_jobs)) ||
+        (rc = upload_array(c, zarea, d_area)))
+        return rc;
+    std::vector<float> area(nj);
+    HIPCHK(c, launch_meshlight_table(c->stream, triWorld, nj, d_jobs, M.tri, const_cast<float*>(d_sums),
+                                     const_cast<float*>(M.cdf), const_cast<float*>(d_area)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(area.data(), d_area, sizeof(float) * (size_t)nj, hipMemcpyDeviceToHost));
+    for (int j = 0; j < nj; ++j) {
+        const int i = job_light[j];
+        if (!(area[j] > 0.f) || !std::isfinite(area[j]))
+            return fail(c, RT_E_ARG, "mesh light " + std::to_string(i) + ": the total area of its triangles is not a positive finite float");
+        M.area[i] = area[j];
+        lights[i].area = area[j];
+        meshlight_pack(lights[i], MeshLightTab{M.tri + a.ml_first[i], M.cdf + a.ml_first[i], a.ml_n[i]});
+    }
+    M.any = true;
+    return RT_OK;
+}
+
 // Everything on the device and the DevScene that points to it.
 static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, const OctLimits& lim,
                         const ShadingArrays& a, const LeafClusters& cl, BvhData bvh[3], float wabs, float oguard) {
@@ -2244,9 +2323,10 @@ static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, 
         (rc = upload_array(c, f.tiles[0], d.tiles[0])) || (rc = upload_array(c, f.tiles[1], d.tiles[1])) ||
         (rc = upload_array(c, a.tw, d.triWorld)) || (rc = upload_array(c, a.tn, d.triNormal)) ||
         (rc = upload_array(c, a.tm, d.triMaterial)) || (rc = upload_array(c, a.mats, d.materials)) ||
-        (rc = upload_array(c, a.shapes, d.shapes)) || (rc = upload_array(c, a.lights, d.lights)) ||
-        (rc = upload_array(c, a.kappa, c->d_kappa)))
+        (rc = upload_array(c, a.shapes, d.shapes)) || (rc = upload_array(c, a.kappa, c->d_kappa)))
         return rc;
+    std::vector<DevLight> lights = a.lights;  // (mesh lights: completed from the device tables)
+    if ((rc = mesh_light_tables(c, a, d.triWorld, lights)) || (rc = upload_array(c, lights, d.lights))) return rc;
     if (qcap == 1) {
         d.cl_guard = cl.guard;
         for (int st = 0; st < 2; ++st) {
@@ -2299,7 +2379,7 @@ static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, 
         d.ring_mask = rs - 1;
     }
     d.n_lights = s->n_lights;
-    if (s->n_lights >= 1) d.light0 = a.lights[0];
+    if (s->n_lights >= 1) d.light0 = lights[0];
     // more than kMaxEmitTris emissive triangles turn the emitter filter off
     if ((rc = upload_array(c, a.etris, d.emit_tris)) || (rc = upload_array(c, a.eshapes, d.emit_shapes))) return rc;
     d.n_emit_tris = (int)a.etris.size() <= kMaxEmitTris ? (int)a.etris.size() : -1;
@@ -2312,11 +2392,18 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
     if (!c || !s) return RT_E_ARG;
     const std::string bad = validate_scene(s);
     if (!bad.empty()) return fail(c, RT_E_ARG, bad);
+    SceneWorld sw;
+    scene_world(s, sw);
+    for (int i = 0; i < s->n_lights; ++i) {  // (before the old scene is released: a rejected upload changes nothing)
+        if (s->lights[i].type != RT_LIGHT_MESH) continue;
+        bool used = false;
+        for (int t = 0; t < s->n_triangles && !used; ++t)
+            used = !sw.degen[t] && (s->tri_material ? s->tri_material[t] : 0) == s->lights[i].material;
+        if (!used) return fail(c, RT_E_ARG, "mesh light " + std::to_string(i) + ": no non-degenerate triangle uses its material");
+    }
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     free_scene(c);
-    SceneWorld sw;
-    scene_world(s, sw);
     c->cull = s->cull_backfaces != 0;
     // octree build (all triangles, culled and degenerate included — the reference inserts every triangle)
     OctBuild ob;
@@ -3762,6 +3849,57 @@ static int impl_rt_debug_texture_eval(rt_ctx* c, int n, const int32_t* prim, con
     });
 }
 
+// the device table of one mesh light
+static int impl_rt_debug_meshlight_table(rt_ctx* c, int light, int* n, int32_t* tri, float* cdf, float* area) {
+    if (!c || !n || !area) return c ? fail(c, RT_E_ARG, "mesh light table: n and area must not be NULL") : RT_E_ARG;
+    if (!c->have_scene) return fail(c, RT_E_STATE, "no scene");
+    const rt_ctx::MeshLights& M = c->ml;
+    if (light < 0 || light >= (int)M.n.size() || M.n[light] <= 0)
+        return fail(c, RT_E_ARG, "mesh light table: light " + std::to_string(light) + " is not a mesh light");
+    *n = M.n[light];
+    *area = M.area[light];
+    hipSetDevice(c->device);
+    const size_t bytes = 4 * (size_t)M.n[light];
+    if ((tri && hipMemcpy(tri, M.tri + M.first[light], bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (cdf && hipMemcpy(cdf, M.cdf + M.first[light], bytes, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(c, RT_E_HIP, std::string("mesh light table: ") + hipGetErrorString(hipGetLastError()));
+    return RT_OK;
+}
+
+// the path kernels' light_ray on explicit shading points and sample points
+static int impl_rt_debug_light_sample(rt_ctx* c, int light, int n, const float* po, const float* u, float* wi, float* tmax,
+                                      float* dist2, float* nl, int32_t* tri) {
+    if (!c || n < 0 || (n && (!po || !u || !wi || !tmax || !dist2 || !nl || !tri)))
+        return c ? fail(c, RT_E_ARG, "light sample: invalid argument") : RT_E_ARG;
+    if (!c->have_scene) return fail(c, RT_E_STATE, "no scene");
+    if (light < 0 || light >= c->dsc.n_lights) return fail(c, RT_E_ARG, "light sample: light index out of range");
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float> dp, du;
+        DevBuf<float4> da, db;
+        DevBuf<int> dt;
+        if (dp.reserve(3 * (size_t)n) || du.reserve(2 * (size_t)n) || da.reserve(n) || db.reserve(n) || dt.reserve(n))
+            return fail(c, RT_E_OOM, "light sample buffers");
+        std::vector<float4> ha(n), hb(n);
+        if (hipMemcpy(dp.get(), po, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(du.get(), u, 8 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_light_sample(c->stream, c->dsc, light, n, dp.get(), du.get(), da.get(), db.get(), dt.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(ha.data(), da.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hb.data(), db.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(tri, dt.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("light sample: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) {
+            wi[3 * i] = ha[i].x; wi[3 * i + 1] = ha[i].y; wi[3 * i + 2] = ha[i].z;
+            tmax[i] = ha[i].w;
+            dist2[i] = hb[i].x;
+            nl[3 * i] = hb[i].y; nl[3 * i + 1] = hb[i].z; nl[3 * i + 2] = hb[i].w;
+        }
+        return RT_OK;
+    });
+}
+
 // the albedo bake kernel alone, on explicit coefficients under the current sensor
 static int impl_rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
     if (!c || n < 0 || (n && (!coeffs || !rgb))) return c ? fail(c, RT_E_ARG, "albedo bake: invalid argument") : RT_E_ARG;
@@ -4013,6 +4151,13 @@ int rt_debug_texture_bake(rt_ctx* c, int n, const uint8_t* rgb, float* coeffs) {
 }
 int rt_debug_texture_eval(rt_ctx* c, int n, const int32_t* prim, const float* b, int32_t* texel, float* coeffs) {
     return entry(c, impl_rt_debug_texture_eval, n, prim, b, texel, coeffs);
+}
+int rt_debug_meshlight_table(rt_ctx* c, int light, int* n, int32_t* tri, float* cdf, float* area) {
+    return entry(c, impl_rt_debug_meshlight_table, light, n, tri, cdf, area);
+}
+int rt_debug_light_sample(rt_ctx* c, int light, int n, const float* po, const float* u, float* wi, float* tmax,
+                          float* dist2, float* nl, int32_t* tri) {
+    return entry(c, impl_rt_debug_light_sample, light, n, po, u, wi, tmax, dist2, nl, tri);
 }
 int rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
     return entry(c, impl_rt_debug_albedo_bake, n, coeffs, rgb);

@@ -90,6 +90,27 @@ struct DevLight {                   // rt_light (build-defined)
     float ro, h;                    // disk: outer radius and height of shapes[shape]
     float o2r[16];                  // disk: ObjectToRender of shapes[shape]
 };
+// RT_LIGHT_MESH: the light's slice of the scene's mesh-light table — tri[i] the i-th triangle id
+// (ascending), cdf[i] = S_i / A with S the inclusive float32 prefix sums of the triangle areas (k_meshlight_table) —
+// travels in the words of p, e1 and e2, which a mesh light does not use, so DevLight, DevScene and with them every
+// kernel's arguments keep their size.  area = A = S_{n-1}; n[] is unused (each triangle has its own normal).
+struct MeshLightTab {
+    const int* tri;
+    const float* cdf;
+    int n;
+};
+inline __host__ __device__ void meshlight_pack(DevLight& L, const MeshLightTab& t) {
+    __builtin_memcpy(&L.p[0], &t.tri, 8);
+    __builtin_memcpy(&L.e1[0], &t.cdf, 8);
+    __builtin_memcpy(&L.e2[0], &t.n, 4);
+}
+inline __host__ __device__ MeshLightTab meshlight_tab(const DevLight& L) {
+    MeshLightTab t;
+    __builtin_memcpy(&t.tri, &L.p[0], 8);
+    __builtin_memcpy(&t.cdf, &L.e1[0], 8);
+    __builtin_memcpy(&t.n, &L.e2[0], 4);
+    return t;
+}
 
 struct DevMaterial {                // rt_material + the area light it feeds (MIS)
     float c0, c1, c2, emit;
@@ -415,6 +436,9 @@ struct NeeIO {
     int* fb_len;   // re-run by k_path_nee<Q, true> with the exact traversal (their count: zeroed with the region)
     unsigned* key; // NEE sort (nullptr: none): the Morton code of the shading point per NEE queue position
     float4 lo, scale; int key_bits;  // its quantisation (SortRaysIO lo / scale) and bits per axis
+    // mesh lights: 1 = the scene has an RT_LIGHT_MESH, the launchers pick the ML instantiations of
+    // k_path_shade_full and k_path_nee (no kernel reads it).  Like tex below it sits in what was padding.
+    int ml = 0;
     // albedo textures: the scene's DevTex in device memory, read by the TEX instantiations of
     // k_path_shade_full and k_path_nee alone (nullptr: no textures, the launchers pick the untextured kernels).  It
     // sits in the padding after key_bits, so the struct and every untextured kernel's arguments are unchanged.
@@ -641,6 +665,15 @@ hipError_t launch_temporal_accumulate(hipStream_t st, const TemporalIO& io);
 // k_adaptive_error gives on k_temporal_accumulate's outputs.
 hipError_t launch_temporal_reproject(hipStream_t st, const TemporalIO& io, float4* rec);
 hipError_t launch_temporal_error(hipStream_t st, const AdaptiveIO& io, const float4* rec, float max_history);
+
+// Mesh area lights (rt_meshlight.hip).  jobs2: (first, n) per mesh light, its slice of tri (triangle
+// ids), sums (scratch) and cdf; area[j] = the light's total area S_{n-1}.  One wave per light, serial over 64-entry
+// chunks.
+hipError_t launch_meshlight_table(hipStream_t st, const float4* triWorld, int n_jobs, const int* jobs2, const int* tri,
+                                  float* sums, float* cdf, float* area);
+// the path kernels' light_ray on explicit (po, u): a[i] = (wi, tmax), b[i] = (dist2, nl), tri[i]
+hipError_t launch_light_sample(hipStream_t st, const DevScene& sc, int light, int n, const float* po, const float* u,
+                               float4* a, float4* b, int* tri);
 
 // Albedo textures (rt_texture.hip).  table: the RGB -> sigmoid coefficient table on the device, kRgbRes
 // z-nodes followed by kRgbTableFloats coefficients (rt_texture.h).

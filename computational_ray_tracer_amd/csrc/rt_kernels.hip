@@ -2494,46 +2494,14 @@ __global__ void __launch_bounds__(kBlock) k_occluded(DevScene sc, int n, const f
     count_add(ctr, C_SFALLBACK, nfb);
 }
 
-// The shadow ray toward one light sample (Lights.h semantics): area lights (quad: p + u0 e1 + u1 e2;
-// disk: the concentric mapping of the Disk shape) and point lights aim at the point, tMax = 0.999 dist; a distant
-// light's direction is fixed (tMax = FLT_MAX; u0, u1 are drawn and unused).  k_path_shade_full evaluates it for the
-// light weights and k_path_nee again for the ray: the same code on the same inputs, so the same bits.
-struct LightRay {
-    V3 wi;
-    float tmax, dist2;
-};
-__device__ __forceinline__ LightRay light_ray(const DevLight& Lt, V3 po, float u0, float u1) {
-    LightRay r;
-    if (Lt.type == 3) {
-        r.wi = v3(Lt.dir[0], Lt.dir[1], Lt.dir[2]);
-        r.tmax = 3.402823466e+38f;
-        r.dist2 = 1.0f;
-        return r;
-    }
-    V3 pl;
-    if (Lt.type == 0) {
-        pl = vadd(vadd(v3(Lt.p[0], Lt.p[1], Lt.p[2]), vmul(v3(Lt.e1[0], Lt.e1[1], Lt.e1[2]), u0)),
-                  vmul(v3(Lt.e2[0], Lt.e2[1], Lt.e2[2]), u1));
-    } else if (Lt.type == 1) {
-        float dx, dy;
-        disk_concentric(u0, u1, dx, dy);
-        pl = m4_point(Lt.o2r, v3(Lt.ro * dx, Lt.ro * dy, Lt.h));
-    } else {
-        pl = v3(Lt.p[0], Lt.p[1], Lt.p[2]);
-    }
-    const V3 wv = vsub(pl, po);
-    r.dist2 = vdot(wv, wv);
-    const float dist = sqrtf(r.dist2);
-    r.wi = vmul(wv, 1.0f / dist);
-    r.tmax = dist * 0.999f;
-    return r;
-}
-
 // MC (material class): 0 every material; 1 the Lambert-or-emitter bin, 2 the mirror-or-dielectric bin (items of
 // io.bin_idx: hits only: k_bin_materials appends no miss to any bin) — each bin kernel holds only its materials' code.
 // TEX (a scene with albedo textures): a textured triangle's (c0, c1, c2) come from its texel (tex_fetch)
 // and its NEE record's tag names the texel instead of the material; the untextured instantiations hold none of it.
-template <int QCAP, int MC, bool TEX = false>
+// ML (a scene with an RT_LIGHT_MESH): light_ray's table search and triangle sample, the sampled
+// triangle's normal in the light weight and the hit triangle's in the emitter-hit pdf; the other instantiations hold
+// none of it.
+template <int QCAP, int MC, bool TEX = false, bool ML = false>
 #ifndef RT_FULL_WAVES
 #define RT_FULL_WAVES RT_MULTI_WAVES  // the mixed-scene shade (variant builds)
 #endif
@@ -2634,7 +2602,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             const DevLight& Lt = sc.lights[lidx];
                             V3 dv = vsub(p, ro);
                             float dist2 = vdot(dv, dv);
-                            float cl = -vdot(v3(Lt.n[0], Lt.n[1], Lt.n[2]), rayd);
+                            V3 ln = v3(Lt.n[0], Lt.n[1], Lt.n[2]);
+                            if (ML && Lt.type == 4) ln = nout;  // (a mesh light's triangles: the hit one's ng)
+                            float cl = -vdot(ln, rayd);
                             if (cl > 0) {
                                 float wb = power_heuristic(prevPdf, dist2 / (cl * Lt.area));
 #pragma unroll
@@ -2717,12 +2687,15 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                                 const DevLight Lt = ldconst(sc.lights, li);
                                 float u0, u1;
                                 sm.get2d(smp, u0, u1);
-                                const LightRay lr = light_ray(Lt, po, u0, u1);
+                                MeshSample ms;
+                                const LightRay lr = light_ray<ML>(Lt, po, u0, u1, sc.triWorld, ms);
                                 const float cs = vdot(nrm, lr.wi);
                                 bool ok;
                                 float wgt;
-                                if (Lt.type <= 1) {
-                                    float cl = -vdot(v3(Lt.n[0], Lt.n[1], Lt.n[2]), lr.wi);
+                                if (Lt.type <= 1 || (ML && Lt.type == 4)) {
+                                    V3 ln = v3(Lt.n[0], Lt.n[1], Lt.n[2]);
+                                    if (ML && Lt.type == 4) ln = ms.nl;
+                                    float cl = -vdot(ln, lr.wi);
                                     ok = cs > 0 && cl > 0;
                                     float G = (cs * cl) / lr.dist2;
                                     wgt = G * Lt.area;
@@ -2846,7 +2819,8 @@ __global__ void __launch_bounds__(kBlock) k_occluded_path(DevScene sc, int n, co
 // reference BFS for the ambiguous rays), so this kernel never holds the BFS's registers (128 VGPRs + spill -> 108).
 // A vertex's lights are always accumulated together, in light order, by one of the two.
 // TEX: the tag's low 31 bits are a material id below n_materials, else n_materials + a texel of the scene's texel array.
-template <int QCAP, bool FB, bool TEX = false>
+// ML: light_ray with the mesh-light search (the record holds (u0, u1) alone: the triangle is found again).
+template <int QCAP, bool FB, bool TEX = false, bool ML = false>
 #ifndef RT_NEE_WAVES
 #define RT_NEE_WAVES 4  // (variant builds: Makefile `variants`)
 #endif
@@ -2891,7 +2865,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             LightRay lr{};
             if (act) {
                 ++nv;
-                lr = light_ray(ldconst(sc.lights, li), po, uv[2 * li], uv[2 * li + 1]);
+                MeshSample ms;
+                lr = light_ray<ML>(ldconst(sc.lights, li), po, uv[2 * li], uv[2 * li + 1], sc.triWorld, ms);
                 if constexpr (COOP) occ = scene_occluded_bvh(sc, po, lr.wi, lr.tmax, snn, snt, amb);
                 else occ = scene_occluded<QCAP>(sc, po, lr.wi, lr.tmax, snn, snt, sfb);
             }
@@ -2948,7 +2923,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                 for (int li = 0; li < nl; ++li) {
                     if (!((vis >> li) & 1)) continue;
                     const DevLight Lt = ldconst(sc.lights, li);
-                    const float sc_le = Lt.type <= 1 ? sc.materials[Lt.material].emit : Lt.scale;
+                    const float sc_le = Lt.type <= 1 || (ML && Lt.type == 4) ? sc.materials[Lt.material].emit : Lt.scale;
                     if ((li >> 2) != wq) {
                         wq = li >> 2;
                         w4 = reinterpret_cast<const float4*>(wg)[wq];
@@ -3231,21 +3206,18 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
     if (!sc.full && qcap != 1 && !shq.shO) return hipErrorInvalidValue;       // so is the shadow queue
     if (sc.full) {  // (the material bins exist on multi-level scenes only: a single leaf shades every material)
         void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, NeeIO);
-        if (nee.tex) {  // a textured scene: the TEX instantiations
-            switch (qcap) {
-                case 0: k = matclass == 1 ? k_path_shade_full<0, 1, true> : matclass == 2 ? k_path_shade_full<0, 2, true> : k_path_shade_full<0, 0, true>; break;
-                case 1: k = k_path_shade_full<1, 0, true>; break;
-                case 16: k = matclass == 1 ? k_path_shade_full<16, 1, true> : matclass == 2 ? k_path_shade_full<16, 2, true> : k_path_shade_full<16, 0, true>; break;
-                default: return hipErrorInvalidValue;
-            }
-        } else {
-            switch (qcap) {
-                case 0: k = matclass == 1 ? k_path_shade_full<0, 1> : matclass == 2 ? k_path_shade_full<0, 2> : k_path_shade_full<0, 0>; break;
-                case 1: k = k_path_shade_full<1, 0>; break;
-                case 16: k = matclass == 1 ? k_path_shade_full<16, 1> : matclass == 2 ? k_path_shade_full<16, 2> : k_path_shade_full<16, 0>; break;
-                default: return hipErrorInvalidValue;
-            }
+        // a textured scene: the TEX instantiations; a scene with a mesh light: the ML ones
+        const int v = (nee.tex ? 1 : 0) | (nee.ml ? 2 : 0);
+#define RT_SHADE_FULL(Q, M) \
+    (v == 0 ? k_path_shade_full<Q, M> : v == 1 ? k_path_shade_full<Q, M, true> : v == 2 ? k_path_shade_full<Q, M, false, true> \
+                                                                                       : k_path_shade_full<Q, M, true, true>)
+        switch (qcap) {
+            case 0: k = matclass == 1 ? RT_SHADE_FULL(0, 1) : matclass == 2 ? RT_SHADE_FULL(0, 2) : RT_SHADE_FULL(0, 0); break;
+            case 1: k = RT_SHADE_FULL(1, 0); break;
+            case 16: k = matclass == 1 ? RT_SHADE_FULL(16, 1) : matclass == 2 ? RT_SHADE_FULL(16, 2) : RT_SHADE_FULL(16, 0); break;
+            default: return hipErrorInvalidValue;
         }
+#undef RT_SHADE_FULL
         return launch_resident(k, gb, grid, st, sc, sp, smp, film, ids, io, nee);
     }
     void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, unsigned long long*, ShadowQueueIO);
@@ -3262,38 +3234,37 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
                            const PathIO& io, const NeeIO& nee, unsigned long long* ctr) {
     const int gb = ring_clamp(grid > 0 ? grid : 1, qcap, sc);
     if (qcap != 1 && (!nee.fb_slot || !nee.fb_len)) return hipErrorInvalidValue;  // the fallback list is required
-    if (nee.tex) {
-        switch (qcap) {
-            case 0: return launch_resident(k_path_nee<0, false, true>, gb, grid, st, sc, sp, io, nee, ctr);
-            case 1: return launch_resident(k_path_nee<1, false, true>, gb, grid, st, sc, sp, io, nee, ctr);
-            case 16: return launch_resident(k_path_nee<16, false, true>, gb, grid, st, sc, sp, io, nee, ctr);
-            default: return hipErrorInvalidValue;
-        }
-    }
+    void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
+    const int v = (nee.tex ? 1 : 0) | (nee.ml ? 2 : 0);  // (as launch_path_shade)
+#define RT_NEE(Q) \
+    (v == 0 ? k_path_nee<Q, false> : v == 1 ? k_path_nee<Q, false, true> : v == 2 ? k_path_nee<Q, false, false, true> \
+                                                                              : k_path_nee<Q, false, true, true>)
     switch (qcap) {
-        case 0: return launch_resident(k_path_nee<0, false>, gb, grid, st, sc, sp, io, nee, ctr);
-        case 1: return launch_resident(k_path_nee<1, false>, gb, grid, st, sc, sp, io, nee, ctr);
-        case 16: return launch_resident(k_path_nee<16, false>, gb, grid, st, sc, sp, io, nee, ctr);
+        case 0: k = RT_NEE(0); break;
+        case 1: k = RT_NEE(1); break;
+        case 16: k = RT_NEE(16); break;
         default: return hipErrorInvalidValue;
     }
+#undef RT_NEE
+    return launch_resident(k, gb, grid, st, sc, sp, io, nee, ctr);
 }
 
 // the vertices k_path_nee listed (multi-level octrees only; a resident grid, the list's length read on the device)
 hipError_t launch_path_nee_fallback(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,
                                     const PathIO& io, const NeeIO& nee, unsigned long long* ctr) {
     const int gb = ring_clamp(std::min(grid > 0 ? grid : 1, kFallbackBlocks), qcap, sc);
-    if (nee.tex) {
-        switch (qcap) {
-            case 0: return launch_resident(k_path_nee<0, true, true>, gb, grid, st, sc, sp, io, nee, ctr);
-            case 16: return launch_resident(k_path_nee<16, true, true>, gb, grid, st, sc, sp, io, nee, ctr);
-            default: return hipErrorInvalidValue;
-        }
-    }
+    void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
+    const int v = (nee.tex ? 1 : 0) | (nee.ml ? 2 : 0);
+#define RT_NEE_FB(Q) \
+    (v == 0 ? k_path_nee<Q, true> : v == 1 ? k_path_nee<Q, true, true> : v == 2 ? k_path_nee<Q, true, false, true> \
+                                                                            : k_path_nee<Q, true, true, true>)
     switch (qcap) {
-        case 0: return launch_resident(k_path_nee<0, true>, gb, grid, st, sc, sp, io, nee, ctr);
-        case 16: return launch_resident(k_path_nee<16, true>, gb, grid, st, sc, sp, io, nee, ctr);
+        case 0: k = RT_NEE_FB(0); break;
+        case 16: k = RT_NEE_FB(16); break;
         default: return hipErrorInvalidValue;
     }
+#undef RT_NEE_FB
+    return launch_resident(k, gb, grid, st, sc, sp, io, nee, ctr);
 }
 
 hipError_t launch_occluded(hipStream_t st, int qcap, const DevScene& sc, int n, const float4* o, const float4* d,

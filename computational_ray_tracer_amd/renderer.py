@@ -112,6 +112,36 @@ class Renderer:
             texel.ctypes.data_as(C.POINTER(C.c_int32)), co.ctypes.data_as(C.POINTER(C.c_float))))
         return texel, co
 
+    # ---- mesh area lights (capi.RT_LIGHT_MESH) -------------------------------------------------
+    def meshlight_table(self, light):
+        """rt_debug_meshlight_table: the device table of mesh light `light` -> (tri int32 (n): the light's triangle
+        ids, cdf float32 (n), area float32: the total area S_{n-1})."""
+        n, area = C.c_int(0), C.c_float(0)
+        self._chk("rt_debug_meshlight_table", self.lib.rt_debug_meshlight_table(
+            self.h, int(light), C.byref(n), None, None, C.byref(area)))
+        tri, cdf = np.zeros(n.value, np.int32), np.zeros(n.value, np.float32)
+        self._chk("rt_debug_meshlight_table", self.lib.rt_debug_meshlight_table(
+            self.h, int(light), C.byref(n), tri.ctypes.data_as(C.POINTER(C.c_int32)),
+            cdf.ctypes.data_as(C.POINTER(C.c_float)), C.byref(area)))
+        return tri, cdf, np.float32(area.value)
+
+    def light_sample(self, light, po, u):
+        """rt_debug_light_sample: the path kernels' light sampling for shading points po (n, 3) and sample points
+        u (n, 2) -> dict(wi (n, 3), tmax (n), dist2 (n), nl (n, 3), tri int32 (n)); tri is -1 unless `light` is a
+        mesh light."""
+        po = np.ascontiguousarray(po, np.float32)
+        u = np.ascontiguousarray(u, np.float32)
+        n = len(po)
+        assert po.shape == (n, 3) and u.shape == (n, 2)
+        wi, nl = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        tmax, dist2, tri = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_light_sample", self.lib.rt_debug_light_sample(
+            self.h, int(light), n, po.ctypes.data_as(F), u.ctypes.data_as(F), wi.ctypes.data_as(F),
+            tmax.ctypes.data_as(F), dist2.ctypes.data_as(F), nl.ctypes.data_as(F),
+            tri.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(wi=wi, tmax=tmax, dist2=dist2, nl=nl, tri=tri)
+
     def set_shard(self, tile_size, n_shards, shard_id):
         self._chk("rt_set_shard", self.lib.rt_set_shard(self.h, tile_size, n_shards, shard_id))
 

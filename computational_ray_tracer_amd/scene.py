@@ -377,7 +377,8 @@ class TriModel:
     tri_material: np.ndarray = None
     materials: list = field(default_factory=list)   # (sigmoid c0,c1,c2, emission_scale[, type, eta])
     lights: list = field(default_factory=list)      # dict(type=QUAD: p, e1, e2, n, material | DISK: shape,
-                                                    #      material | POINT: p, scale | DISTANT: dir, scale)
+                                                    #      material | POINT: p, scale | DISTANT: dir, scale |
+                                                    #      MESH: material — every triangle of it)
     shapes: list = field(default_factory=list)      # Sphere / Disk / TriangleSimple, after the octree
     # albedo textures: per-vertex uv, the images, and per material a texture id or -1
     texcoords: np.ndarray = None                    # (nv, 2) float32

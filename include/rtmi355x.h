@@ -89,12 +89,19 @@ typedef struct {
     int material;
 } rt_shape;
 
-enum { RT_LIGHT_QUAD = 0, RT_LIGHT_DISK = 1, RT_LIGHT_POINT = 2, RT_LIGHT_DISTANT = 3 };
+enum { RT_LIGHT_QUAD = 0, RT_LIGHT_DISK = 1, RT_LIGHT_POINT = 2, RT_LIGHT_DISTANT = 3, RT_LIGHT_MESH = 4 };
 /* Build-defined lights (Lights.h:1-10 is a comment stub naming area, point and sun lights).
  * QUAD: x = p + u·e1 + v·e2, emitting normal n, Le from `material` (the quad is also geometry: two
  *   emissive triangles of the mesh);  DISK: uniform area sampling of shapes[shape] (an emissive DISK
  *   shape with inner_radius 0), Le from its material;  POINT: at p, intensity scale · D65;
- *   DISTANT: unit direction `dir` towards the light, irradiance scale · D65. */
+ *   DISTANT: unit direction `dir` towards the light, irradiance scale · D65.
+ * MESH (reads `material` only): the light is every non-degenerate mesh triangle whose tri_material is
+ *   `material`, in ascending triangle id, sampled uniformly by area (one sample and one shadow ray per
+ *   path vertex whatever the triangle count).  Each triangle emits from the side of its geometric normal
+ *   normalize(cross(p0 - p2, p1 - p2)) of its world vertices; Le from the material.  rt_scene_upload
+ *   returns RT_E_ARG when the material is out of range or not emissive, when no non-degenerate triangle
+ *   uses it, when an analytic shape uses it, or when another light names the same material.
+ *   RT_INTEGRATOR_REFERENCE ignores it, like every light. */
 typedef struct {
     int type;
     float p[3], e1[3], e2[3], n[3];
@@ -524,6 +531,25 @@ int rt_debug_texture_bake(rt_ctx* ctx, int n, const uint8_t* rgb, float* coeffs)
 /* The shade kernels' device function on n explicit (triangle id, b0 b1 b2): texel[i] = the texel index within its
  * texture, or -1 for an untextured triangle, and coeffs[3i..] = the (c0, c1, c2) the shade would use. */
 int rt_debug_texture_eval(rt_ctx* ctx, int n, const int32_t* prim, const float* b, int32_t* texel, float* coeffs);
+
+/* ---- mesh area lights (additive): RT_LIGHT_MESH above -------------------------------
+ * The device table of mesh light `light` of the uploaded scene, built in float32 with nothing fused: with
+ * cr = cross(p0 - p2, p1 - p2) (each component a*b - c*d as written there, the dot (x x + y y) + z z),
+ * area_i = 0.5f sqrtf(dot(cr, cr)); S = the inclusive prefix sums of the areas taken 64 entries at a time (inside a
+ * chunk v += shift_up(v, o) for o = 1, 2, 4, 8, 16, 32, entries below o keep theirs; S_i = carry + v, carry = the S of
+ * the previous chunk's last entry, 0 for the first chunk); cdf_i = S_i / S_{n-1}.
+ * *n = the triangle count and *area = S_{n-1} are always written; tri (n triangle ids), cdf (n) when non-NULL.
+ * RT_E_ARG if `light` is not a mesh light of the scene. */
+int rt_debug_meshlight_table(rt_ctx* ctx, int light, int* n, int32_t* tri, float* cdf, float* area);
+/* The path kernels' own light-sampling device function for light `light` on n explicit shading points po (3n) and
+ * sample points u (2n): wi (3n) the unit direction of the shadow ray, tmax, dist2 (n), nl (3n) the light's normal at
+ * the sample and tri (n) the sampled triangle id (-1 and the light's n for the other light types).
+ * A mesh light, float32 in the order written: i = the smallest index with u0 < cdf_i; lo = i > 0 ? cdf_{i-1} : 0;
+ * u' = fminf((u0 - lo) / (cdf_i - lo), 0x1.fffffep-1f); if u' < u1: b0 = u' / 2, b1 = u1 - b0, else b1 = u1 / 2,
+ * b0 = u' - b1; b2 = (1 - b0) - b1; pl = (p0 b0 + p1 b1) + p2 b2; nl = normalize(cross(p0 - p2, p1 - p2));
+ * wv = pl - po, dist2 = dot(wv, wv), wi = wv (1 / sqrtf(dist2)), tmax = sqrtf(dist2) 0.999f. */
+int rt_debug_light_sample(rt_ctx* ctx, int light, int n, const float* po, const float* u, float* wi, float* tmax,
+                          float* dist2, float* nl, int32_t* tri);
 
 /* ---- albedo demodulation for the denoiser (additive) ------------------------------
  * The filter divides the film by a noise-free first-hit albedo, filters the demodulated irradiance (smooth across the
