@@ -546,6 +546,10 @@ struct Knobs {
     // single-leaf simple path, depths >= 1: the trace appends its hits to a dense hit queue and the shade runs only
     // those (TraceIO hq_d; Cornell +4.2 %, r07_ab4).  RTMI_HIT_COMPACT=0: every queue position is shaded (A/B)
     int hit_compact = 1;
+    // the hit queue's records packed into one float4, (b0, b1, b2, slot | prim << 24 | facing << 30), the trace forming
+    // the facing bit, face normals staged in LDS, and depth 0's hit word in hitB.w (rt_internal.h hit_pack, hit_pack0):
+    // scenes of <= kHitPackTris triangles, batches of <= kHitPackSlots samples.  RTMI_HIT_PACK=0: unpacked (A/B, fallback)
+    int hit_pack = 1;
     size_t batch_samples = 0;  // samples in flight per batch (0: 16 Mi single leaf, 32 Mi multi-level; RTMI_BATCH_SAMPLES)
     // denoiser iterations of step 1 and 2 stage their tile and halo in LDS (same bits; RTMI_DENOISE_LDS=0: every tap a
     // plain load, A/B in DESIGN.md §3c)
@@ -587,6 +591,7 @@ static Knobs read_knobs() {
     if (const char* e = std::getenv("RTMI_SORT_NEE")) std::sscanf(e, "%d/%d", &k.sort_nee, &k.sort_nee_bits);
     k.sort_nee_bits = std::max(1, std::min(9, k.sort_nee_bits));
     if (const char* e = std::getenv("RTMI_HIT_COMPACT")) k.hit_compact = std::atoi(e) != 0;
+    if (const char* e = std::getenv("RTMI_HIT_PACK")) k.hit_pack = std::atoi(e) != 0;
     if (const char* e = std::getenv("RTMI_BATCH_SAMPLES")) k.batch_samples = (size_t)std::max(0L, std::atol(e));
     if (const char* e = std::getenv("RTMI_DENOISE_LDS")) k.denoise_lds = std::atoi(e) != 0;
     return k;
@@ -817,7 +822,14 @@ DevScene lane_scene(const rt_ctx* c, const Work& w) {
     return d;
 }
 
-int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path) {
+// the single-leaf simple path packs its hit records (Knobs hit_pack) for batches of at most nmax samples
+bool hit_pack_active(const rt_ctx* c, size_t nmax) {
+    return c->knobs.hit_pack && c->knobs.hit_compact && c->dsc.qcap == 1 && !c->dsc.full &&
+           c->dsc.n_tris <= kHitPackTris && nmax <= (size_t)kHitPackSlots;
+}
+
+// hit_pack: the path pass packs its hit records (hit_pack_active), so the batch needs no hitD
+int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path, bool hit_pack = false) {
     int rc;
     HIPCHK(c, w.qcount.reserve(2 * kQRegion));
     if (&w != &c->ws[0] && !w.stream) HIPCHK(c, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
@@ -826,9 +838,10 @@ int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path) {
     Batch& b = w.b;
     // the compacted hit records' (direction, prim) stream, sized like hitB (RTMI_HIT_COMPACT: the single-leaf
     // simple path; the scene may have changed since the batch buffers were allocated)
-    const bool hit_d = path && c->knobs.hit_compact && c->dsc.qcap == 1 && !c->dsc.full;
+    const bool hit_d = path && c->knobs.hit_compact && c->dsc.qcap == 1 && !c->dsc.full && !hit_pack;
     if (b.capacity(path) >= n) {
         if (hit_d) HIPCHK(c, b.hitD.reserve(n));
+        else if (path) b.hitD.reset();  // (packed records, or another scene: not kept beside the batch)
         return RT_OK;
     }
     b = Batch{};  // every batch buffer of the lane, the sort, shadow and NEE groups included
@@ -1274,8 +1287,10 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, 
     // multi-level octrees: coherence-sort each bounce's rays (rt_sort.hip); on the single-leaf Cornell box the sort
     // costs more than it saves (1110 -> 720 Msamples/s)
     const bool sort_rays = c->dsc.qcap != 1 && kn.sort_rays;
+    // single-leaf simple path: packed hit records while every slot of a batch fits the record's 24-bit field
+    const bool hpack = hit_pack_active(c, nmax);
     for (int l = 0; l < lanes; ++l) {
-        if ((rc = ensure_workspace(c, c->ws[l], ncap, true))) return rc;
+        if ((rc = ensure_workspace(c, c->ws[l], ncap, true, hpack))) return rc;
         if (sort_rays && (rc = ensure_sort_workspace(c, c->ws[l].b, ncap))) return rc;
         // the trace-fallback list (multi-level octrees): one entry per queue position at most
         if (c->dsc.qcap != 1) HIPCHK(c, c->ws[l].tfb.reserve(ncap));
@@ -1383,13 +1398,17 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, 
                 }
                 TraceIO tio{cO, cD, qv, 0, b.hitB.get(), b.hitPrim.get(), dyn ? qc_cur + kQTraceTicket : nullptr, 1};
                 if (depth > 0 && !efilter) tio.zero = qc_nxt;
+                // packed hit records, depth 0: the hit word (prim, flip, front) in hitB's w lane, so the shade reads
+                // hitB alone (no hitPrim, no ray).  Nothing else reads this depth's hits on the simple path.
+                if (hpack && depth == 0) tio.hq_pack = 1;
                 // single-leaf simple path, bounce depths: the trace appends its hits to a dense hit queue and the shade
                 // runs only those.  The length word is this queue's shadow-queue length, which single-leaf scenes
                 // never use (zero before the launch like the rest of the region).  Depth 0 keeps its dense queue:
                 // slot = position, and the lean path writes L = 0 for the camera misses there.
                 const bool hitc = kn.hit_compact && c->dsc.qcap == 1 && !c->dsc.full && depth > 0;
                 if (hitc) {
-                    tio.hq_d = b.hitD.get();
+                    if (hpack) tio.hq_pack = 1;  // one float4 per record: hitD is neither allocated nor touched
+                    else tio.hq_d = b.hitD.get();
                     tio.hq_len = qc_cur + kQShadowLen;
                 }
                 if (c->dsc.qcap != 1) {  // ambiguous rays listed for k_trace_fallback (the trace holds no BFS)
@@ -1473,7 +1492,7 @@ int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, 
                     }
                 } else {
                     HIPCHK(c, launch_path_shade(s, grid, c->dsc.qcap, dsl, d_spec, smp, fd, ids, pio, d_ctr, sqio,
-                                                nio));
+                                                nio, 0, hpack));
                 }
                 ev_mark(c, s, ST_SHADE, e0);
                 if (sort_nee) {  // NEE vertices in Morton order of their shading points (no host round trip)

@@ -310,6 +310,52 @@ struct QueueView {
 static const int kBlockThreads = 256;  // threads per block of every kernel
 static const int kClusterTris = 2;     // leaf tiles per culling cluster (single-leaf scenes; 4 or 6: -2 %)
 
+// Packed hit record of the single-leaf simple path (RTMI_HIT_PACK; TraceIO hq_pack): the w lane of hitB[h]
+// holds slot | prim << 24 | facing << 30 with bit 31 clear, facing = the ray looks at the back of the triangle
+// (dot(face normal, normalised direction) > 0: the shade flips the normal).  The host packs only while every slot of
+// the batch is below kHitPackSlots and the scene has at most kHitPackTris triangles.
+static const int kHitPackSlots = 1 << 24;
+static const int kHitPackTris = 64;
+inline __host__ __device__ constexpr unsigned hit_pack(int slot, int prim, bool facing) {
+    return (unsigned)slot | (unsigned)prim << 24 | (facing ? 1u << 30 : 0u);
+}
+struct HitWord {
+    int slot, prim;
+    bool facing;
+};
+inline __host__ __device__ constexpr HitWord hit_unpack(unsigned w) {
+    return HitWord{(int)(w & (unsigned)(kHitPackSlots - 1)), (int)(w >> 24 & (unsigned)(kHitPackTris - 1)),
+                   (w >> 30 & 1u) != 0};
+}
+// Depth 0 of the same path (the dense camera queue, slot = position): hitB[k].w = prim | front << 29 | flip << 30, or
+// -1 for a miss; flip as facing above, front = dot < 0 (the one-sided emitter's lit side; dot == 0 sets neither).
+inline __host__ __device__ constexpr unsigned hit_pack0(int prim, bool flip, bool front) {
+    return (unsigned)prim | (front ? 1u << 29 : 0u) | (flip ? 1u << 30 : 0u);
+}
+struct HitWord0 {
+    int prim;  // -1: a miss
+    bool flip, front;
+};
+inline __host__ __device__ constexpr HitWord0 hit_unpack0(unsigned w) {
+    return HitWord0{(int)w < 0 ? -1 : (int)(w & (unsigned)(kHitPackTris - 1)), (w >> 30 & 1u) != 0, (w >> 29 & 1u) != 0};
+}
+static_assert(hit_unpack0(hit_pack0(kHitPackTris - 1, true, false)).prim == kHitPackTris - 1 &&
+                  hit_unpack0(hit_pack0(kHitPackTris - 1, true, false)).flip &&
+                  !hit_unpack0(hit_pack0(kHitPackTris - 1, true, false)).front &&
+                  hit_unpack0(hit_pack0(0, false, true)).front && !hit_unpack0(hit_pack0(0, false, true)).flip &&
+                  hit_unpack0(0xffffffffu).prim == -1 && (hit_pack0(kHitPackTris - 1, true, true) >> 31) == 0,
+              "packed depth-0 hit word: round trip, a negative word is a miss");
+static_assert(hit_unpack(hit_pack(kHitPackSlots - 1, kHitPackTris - 1, true)).slot == kHitPackSlots - 1 &&
+                  hit_unpack(hit_pack(kHitPackSlots - 1, kHitPackTris - 1, true)).prim == kHitPackTris - 1 &&
+                  hit_unpack(hit_pack(kHitPackSlots - 1, kHitPackTris - 1, true)).facing,
+              "packed hit word: round trip at the field limits, facing set");
+static_assert(hit_unpack(hit_pack(kHitPackSlots - 1, kHitPackTris - 1, false)).slot == kHitPackSlots - 1 &&
+                  hit_unpack(hit_pack(kHitPackSlots - 1, kHitPackTris - 1, false)).prim == kHitPackTris - 1 &&
+                  !hit_unpack(hit_pack(kHitPackSlots - 1, kHitPackTris - 1, false)).facing,
+              "packed hit word: round trip at the field limits, facing clear");
+static_assert((hit_pack(kHitPackSlots - 1, kHitPackTris - 1, true) >> 31) == 0 && hit_unpack(hit_pack(0, 0, false)).slot == 0,
+              "packed hit word: bit 31 stays clear (a negative word marks a miss)");
+
 struct TraceIO {
     const float4* rayO; const float4* rayD;
     QueueView q;              // the queue's shards
@@ -318,6 +364,11 @@ struct TraceIO {
     int* hitPrim;
     int* ticket = nullptr;    // per-shard chunk tickets (zeroed before the launch) or nullptr: static chunks
     int rsh = 0;              // ray k at rayO[k << rsh] (1: the workspace's interleaved (o, d) pairs; 0: caller arrays)
+    // RTMI_HIT_PACK (single-leaf simple path; scenes of <= kHitPackTris triangles, slots < kHitPackSlots).  With the
+    // hit queue (hq_len): its records are hitB[h] = (b0, b1, b2, bits(hit_pack(slot, prim, facing))) alone, hq_d is
+    // neither written nor read.  Without (depth 0, the dense camera queue): hitB[k] = (b0, b1, b2, bits(hit_pack0(prim,
+    // flip, front)) or -1 for a miss) and hitPrim is not written — only the path pass's own shade reads this form.
+    int hq_pack = 0;
     // sorted bounce (multi-level scenes, tickets only): position p traces the queue's ray perm[p] (rt_sort.hip) and
     // stores it to so[2p], so[2p + 1] — the sorted side queue the shade kernel reads; nullptr: no sort
     const int* perm = nullptr;
@@ -398,6 +449,8 @@ struct PathIO {
     const int* bin_idx = nullptr;  // material-binned shade: item i of q is queue position bin_idx[i] (BinIO)
     // compacted hits (TraceIO hq_d; k_path_shade<1, true>): q is the hit queue, item h's record is hitB[h] = (b0, b1,
     // b2, bits(slot)) and hq_d[h] = (the ray's direction, bits(prim >= 0)); rayO, rayD and hitPrim are not read
+    // packed hit records (TraceIO hq_pack, launch_path_shade's hit_pack; k_path_shade<1, true, true>): q is the hit
+    // queue and item h's record is hitB[h] alone, its w lane the packed (slot, prim, facing) word; hq_d stays nullptr
     const float4* hq_d = nullptr;
 };
 
@@ -540,7 +593,7 @@ hipError_t launch_path_shadow(hipStream_t st, int grid, int qcap, bool dfs, cons
 hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,
                              const DevSampler& smp, const DevFilm& film, const SampleIds& ids, const PathIO& io,
                              unsigned long long* ctr, const ShadowQueueIO& shq = ShadowQueueIO{},
-                             const NeeIO& nee = NeeIO{}, int matclass = 0);
+                             const NeeIO& nee = NeeIO{}, int matclass = 0, bool hit_pack = false);
 hipError_t launch_path_film(hipStream_t st, int grid, const DevSpectra* sp, const DevFilm& film, const PathFilmIO& io,
                             unsigned long long* ctr);
 hipError_t launch_path_nee_fallback(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,

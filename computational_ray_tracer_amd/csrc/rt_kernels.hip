@@ -104,18 +104,42 @@ __device__ __forceinline__ BvhNode8 load_node8(const float4* __restrict__ nodes,
 // the simple path's per-triangle shading inputs on single-leaf scenes (<= 64 triangles): world vertices and the
 // material's (c0, c1, c2, emission), staged in LDS by k_path_shade<1>
 __shared__ float4 g_tri1[4 * 64];
+// a triangle's face normal as the simple path shades it (Shapes.h:1073)
+__device__ __forceinline__ V3 tri_face_normal(V3 p0, V3 p1, V3 p2) { return vnorm(vcross(vsub(p0, p2), vsub(p1, p2))); }
+// NG (packed hit records, RTMI_HIT_PACK): triangle i's face normal in the w lanes of its three vertices, so the
+// shade forms no cross product or normalisation per hit
+template <bool NG = false>
 __device__ __forceinline__ bool stage_tris1(const DevScene& sc) {
     const bool ok = sc.n_tris <= 64;
     if (ok)
         for (int i = threadIdx.x; i < sc.n_tris; i += blockDim.x) {
-            g_tri1[4 * i] = sc.triWorld[3 * i];
-            g_tri1[4 * i + 1] = sc.triWorld[3 * i + 1];
-            g_tri1[4 * i + 2] = sc.triWorld[3 * i + 2];
+            if constexpr (NG) {
+                float4 P0 = sc.triWorld[3 * i], P1 = sc.triWorld[3 * i + 1], P2 = sc.triWorld[3 * i + 2];
+                const V3 ng = tri_face_normal(v3(P0.x, P0.y, P0.z), v3(P1.x, P1.y, P1.z), v3(P2.x, P2.y, P2.z));
+                P0.w = ng.x; P1.w = ng.y; P2.w = ng.z;
+                g_tri1[4 * i] = P0;
+                g_tri1[4 * i + 1] = P1;
+                g_tri1[4 * i + 2] = P2;
+            } else {
+                g_tri1[4 * i] = sc.triWorld[3 * i];
+                g_tri1[4 * i + 1] = sc.triWorld[3 * i + 1];
+                g_tri1[4 * i + 2] = sc.triWorld[3 * i + 2];
+            }
             const DevMaterial dm = sc.materials[sc.triMaterial[i]];
             g_tri1[4 * i + 3] = make_float4(dm.c0, dm.c1, dm.c2, dm.emit);
         }
     __syncthreads();
     return ok;
+}
+// the same face normals alone, for the trace kernel that packs the facing bit into its hit records (1 KB)
+__shared__ float4 g_ng1[kHitPackTris];
+__device__ __forceinline__ void stage_ng1(const DevScene& sc) {
+    for (int i = threadIdx.x; i < sc.n_tris && i < kHitPackTris; i += blockDim.x) {
+        const float4 P0 = sc.triWorld[3 * i], P1 = sc.triWorld[3 * i + 1], P2 = sc.triWorld[3 * i + 2];
+        const V3 ng = tri_face_normal(v3(P0.x, P0.y, P0.z), v3(P1.x, P1.y, P1.z), v3(P2.x, P2.y, P2.z));
+        g_ng1[i] = make_float4(ng.x, ng.y, ng.z, 0.f);
+    }
+    __syncthreads();
 }
 // Mixed-scene material table in LDS (<= kLdsMats entries, 32 B each): the shade and binning kernels look up the
 // material of every hit (prim -> triMaterial -> material), so staging the table removes the chain's last global
@@ -1681,9 +1705,14 @@ __device__ __forceinline__ int finish_closest(const DevScene& sc, const TraceIO&
 // FBL (multi-level scenes, path mode: io.fb_pos): the BVH walk alone, the ambiguous rays listed for k_trace_fallback;
 // otherwise the reference BFS runs inline for them.
 // HQ (single leaf, TraceIO hq_d): the hits are appended to the dense hit queue.
-template <int QCAP, bool FBL, bool HQ = false>
+// PK (single leaf, TraceIO hq_pack): with HQ one float4 per record, its w lane the packed (slot, prim, facing) word;
+// without (the dense camera queue, one shard): hitB[p].w is the packed (prim, flip, front) word or -1 for a miss
+// instead of t, and hitPrim is not written.
+template <int QCAP, bool FBL, bool HQ = false, bool PK = false>
 __global__ void __launch_bounds__(kBlock) RT_WAVES_ATTR(QCAP) k_trace_closest(DevScene sc, TraceIO io, unsigned long long* ctr) {
+    static_assert(!PK || (QCAP == 1 && !FBL), "packed records exist on the single-leaf simple path only");
     stage_scene<QCAP, false>(sc, io.set);
+    if constexpr (PK) stage_ng1(sc);
     if (io.zero && blockIdx.x == 0)
         for (int i = threadIdx.x; i < kQRegion; i += blockDim.x) io.zero[i] = 0;
     ctr_t nn = 0, nt = 0, nh = 0, nr = 0, nfb = 0, novf = 0;
@@ -1704,7 +1733,20 @@ __global__ void __launch_bounds__(kBlock) RT_WAVES_ATTR(QCAP) k_trace_closest(De
             prim = traverse_any<QCAP, false>(sc, io.set, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 3.402823466e+38f,
                                              b0, b1, b2, t, nn, nt, nfb);
         }
-        prim = finish_closest<QCAP != 1>(sc, io, p, o4, d4, prim, b0, b1, b2, t);
+        if constexpr (PK) {
+            // the shade's two sign tests of dot(face normal, normalised direction), on the same floats: > 0 flips
+            // the normal, < 0 is the depth-0 emitter's front side (== 0 or NaN: neither)
+            closest_shapes<false>(sc, o4, d4, prim, b0, b1, b2, t);
+            int w = -1;
+            if (prim >= 0) {
+                const float4 n4 = g_ng1[prim];
+                const float dn = vdot(v3(n4.x, n4.y, n4.z), vnorm(v3(d4.x, d4.y, d4.z)));
+                w = (int)hit_pack0(prim, dn > 0, dn < 0);
+            }
+            io.hitB[p] = make_float4(b0, b1, b2, __int_as_float(w));
+        } else {
+            prim = finish_closest<QCAP != 1>(sc, io, p, o4, d4, prim, b0, b1, b2, t);
+        }
         nh += prim >= 0;
         nr += 1;
     };
@@ -1740,21 +1782,39 @@ __global__ void __launch_bounds__(kBlock) RT_WAVES_ATTR(QCAP) k_trace_closest(De
                     nh += prim >= 0;
                     nr += 1;
                 }
-                const float4 rb = make_float4(b0, b1, b2, o4.w), rd = make_float4(d4.x, d4.y, d4.z, __int_as_float(prim));
+                float4 rb = make_float4(b0, b1, b2, o4.w);
+                const float4 rd = make_float4(d4.x, d4.y, d4.z, __int_as_float(prim));
+                if constexpr (PK) {
+                    // the shade's only use of the direction is the sign of dot(face normal, normalised direction):
+                    // the same expression on the same floats here, with the traversal's registers dead (a miss: -1)
+                    int w = -1;
+                    if (prim >= 0) {
+                        const float4 n4 = g_ng1[prim];
+                        const bool facing = vdot(v3(n4.x, n4.y, n4.z), vnorm(v3(d4.x, d4.y, d4.z))) > 0;
+                        w = (int)hit_pack(__float_as_int(o4.w), prim, facing);
+                    }
+                    rb.w = __int_as_float(w);
+                }
                 if (r == 0) {
                     rb0 = rb;
                     rd0 = rd;
                 } else {
-                    const bool h0 = __float_as_int(rd0.w) >= 0;
+                    const bool h0 = __float_as_int(PK ? rb0.w : rd0.w) >= 0;
                     int p0, p1;
                     block_append2(io.hq_len, h0, prim >= 0, hq_lds, p0, p1);
-                    if (h0) { io.hitB[p0] = rb0; io.hq_d[p0] = rd0; }
-                    if (prim >= 0) { io.hitB[p1] = rb; io.hq_d[p1] = rd; }
+                    if (h0) {
+                        io.hitB[p0] = rb0;
+                        if constexpr (!PK) io.hq_d[p0] = rd0;
+                    }
+                    if (prim >= 0) {
+                        io.hitB[p1] = rb;
+                        if constexpr (!PK) io.hq_d[p1] = rd;
+                    }
                 }
                 k = kn; o4 = on; d4 = dn;
             }
         }
-    } else if (!io.ticket && io.q.ns == 1) {
+    } else if (PK || (!io.ticket && io.q.ns == 1)) {  // (PK: the host launches this form alone)
         const int n = q_len(io.q, 0);
         auto item = [&](int i) {
             return (blockIdx.x + (i / kStaticItems) * gridDim.x) * kChunk + (i % kStaticItems) * kBlock +
@@ -2161,7 +2221,10 @@ __device__ __forceinline__ void push_bounce(const PathIO& io, int pos, float4 nO
 }
 
 // HQ (single leaf, PathIO hq_d): the items are the trace kernel's compacted hit records instead of queue positions.
-template <int QCAP, bool HQ = false>
+// PK (launch_path_shade's hit_pack): with HQ (depths >= 1) one float4 per record, its w lane the packed (slot, prim,
+// facing) word; without (depth 0) item k reads hitB[k] alone, its w lane the packed (prim, flip, front) word, and
+// neither hitPrim nor the ray.  The face normal comes from LDS and is flipped on the record's bit.
+template <int QCAP, bool HQ = false, bool PK = false>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCAP == 1 ? RT_SHADE1_WAVES : RT_SHADE_WAVES))) k_path_shade(DevScene sc, const DevSpectra* sp, DevSampler smp,
                                                                          DevFilm film, SampleIds ids, PathIO io,
                                                                          unsigned long long* ctr, ShadowQueueIO shq) {
@@ -2169,7 +2232,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
     bool lds_tris = false;
     stage_spectra(sp);
     stage_scene<QCAP>(sc, 0);
-    if constexpr (QCAP == 1) lds_tris = stage_tris1(sc);
+    static_assert(!PK || QCAP == 1, "packed records exist on the single-leaf simple path only");
+    if constexpr (QCAP == 1) lds_tris = stage_tris1<PK>(sc);
     __shared__ int lds[2 * (kBlock / 64) + 1];
     // single leaf: the first item of a static chunk parks its bounce ray here; the second item appends both (one
     // atomic and one round of barriers per chunk: Cornell +3.5 %, r03)
@@ -2199,7 +2263,21 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             // streams, so the ray queue is not read at all
             int prim;
             float4 hq = make_float4(0, 0, 0, 0), hd = hq;
-            if constexpr (HQ) {
+            bool facing = false, front = false;
+            if constexpr (PK && !HQ) {  // depth 0: the dense camera queue, slot = position; a negative word: a miss
+                hq = io.hitB[k];
+                const HitWord0 hw = hit_unpack0(__float_as_uint(hq.w));
+                slot = k;
+                prim = hw.prim;
+                facing = hw.flip;
+                front = hw.front;
+            } else if constexpr (PK) {
+                hq = io.hitB[k];
+                const HitWord hw = hit_unpack(__float_as_uint(hq.w));
+                slot = hw.slot;
+                prim = hw.prim;
+                facing = hw.facing;
+            } else if constexpr (HQ) {
                 hq = io.hitB[k];
                 hd = io.hq_d[k];
                 slot = __float_as_int(hq.w);
@@ -2218,7 +2296,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                     rload8(io.rec, slot, R_BETA, beta);
                 }
                 float4 P0, P1, P2, mt;
-                if (QCAP == 1 && lds_tris) {
+                if (QCAP == 1 && (PK || lds_tris)) {  // (PK: the host packs only scenes the table holds)
                     P0 = g_tri1[4 * prim]; P1 = g_tri1[4 * prim + 1]; P2 = g_tri1[4 * prim + 2]; mt = g_tri1[4 * prim + 3];
                 } else {
                     P0 = sc.triWorld[3 * prim]; P1 = sc.triWorld[3 * prim + 1]; P2 = sc.triWorld[3 * prim + 2];
@@ -2227,11 +2305,17 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                     mt = make_float4(dm.c0, dm.c1, dm.c2, dm.emit);
                 }
                 V3 p0 = v3(P0.x, P0.y, P0.z), p1 = v3(P1.x, P1.y, P1.z), p2 = v3(P2.x, P2.y, P2.z);
-                V3 ng = vnorm(vcross(vsub(p0, p2), vsub(p1, p2)));  // Shapes.h:1073
-                const float4 d4 = HQ ? hd : io.rayD[2 * k];
-                V3 rayd = vnorm(v3(d4.x, d4.y, d4.z));
+                V3 ng, rayd = v3(0, 0, 0);
+                if constexpr (PK) {
+                    ng = v3(P0.w, P1.w, P2.w);  // (stage_tris1<true>)
+                } else {
+                    ng = tri_face_normal(p0, p1, p2);
+                    const float4 d4 = HQ ? hd : io.rayD[2 * k];
+                    rayd = vnorm(v3(d4.x, d4.y, d4.z));
+                }
                 if (mt.w > 0) {
-                    if (io.depth == 0 && vdot(ng, rayd) < 0) {
+                    // (the packed hit queue: depths >= 1 only, where an emitter hit adds nothing)
+                    if (!(PK && HQ) && io.depth == 0 && (PK ? front : vdot(ng, rayd) < 0)) {
                         float L[8];
                         rload8_or_zero(io.rec, slot, R_L, L, d0);
 #pragma unroll
@@ -2241,8 +2325,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                     }
                 } else if (io.depth < io.max_depth) {
                     V3 nrm = ng;
-                    if (vdot(nrm, rayd) > 0) nrm = v3(-nrm.x, -nrm.y, -nrm.z);
-                    const float4 hb = HQ ? hq : io.hitB[k];
+                    if (PK ? facing : vdot(nrm, rayd) > 0) nrm = v3(-nrm.x, -nrm.y, -nrm.z);
+                    const float4 hb = HQ || PK ? hq : io.hitB[k];
                     V3 p = vadd(vadd(vmul(p0, hb.x), vmul(p1, hb.y)), vmul(p2, hb.z));
                     float off = 1e-4f * (1.0f + max3f(fabsf(p.x), fabsf(p.y), fabsf(p.z)));
                     V3 po = vadd(p, vmul(nrm, off));
@@ -3144,8 +3228,12 @@ hipError_t launch_trace_closest(hipStream_t st, int grid, int qcap, const DevSce
         case 0: k = fbl ? k_trace_closest<0, true> : k_trace_closest<0, false>; break;
         case 1:
             if (io.hq_len) {  // compacted hits: static chunks of a one-shard queue only
-                if (io.ticket || io.q.ns != 1 || !io.hq_d) return hipErrorInvalidValue;
-                k = k_trace_closest<1, false, true>;
+                if (io.ticket || io.q.ns != 1) return hipErrorInvalidValue;
+                if (io.hq_pack ? sc.n_tris > kHitPackTris : !io.hq_d) return hipErrorInvalidValue;
+                k = io.hq_pack ? k_trace_closest<1, false, true, true> : k_trace_closest<1, false, true>;
+            } else if (io.hq_pack) {  // the dense camera queue with packed hit words
+                if (io.ticket || io.q.ns != 1 || io.q.len || sc.n_tris > kHitPackTris) return hipErrorInvalidValue;
+                k = k_trace_closest<1, false, false, true>;
             } else {
                 k = k_trace_closest<1, false>;
             }
@@ -3200,8 +3288,13 @@ hipError_t launch_path_shadow(hipStream_t st, int grid, int qcap, bool dfs, cons
 
 hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,
                              const DevSampler& smp, const DevFilm& film, const SampleIds& ids, const PathIO& io,
-                             unsigned long long* ctr, const ShadowQueueIO& shq, const NeeIO& nee, int matclass) {
+                             unsigned long long* ctr, const ShadowQueueIO& shq, const NeeIO& nee, int matclass,
+                             bool hit_pack) {
     const int gb = ring_clamp(grid > 0 ? grid : 1, qcap, sc);
+    // packed hit records: the single-leaf simple path, a scene the LDS triangle table holds; depth 0 reads the dense
+    // camera queue's hit words, the bounce depths the hit queue's records
+    if (hit_pack && (qcap != 1 || sc.full || io.ticket || sc.n_tris > kHitPackTris || (io.depth == 0 && io.q.len)))
+        return hipErrorInvalidValue;
     if (sc.full && sc.n_lights > 0 && !nee.rec) return hipErrorInvalidValue;  // NEE records are required
     if (!sc.full && qcap != 1 && !shq.shO) return hipErrorInvalidValue;       // so is the shadow queue
     if (sc.full) {  // (the material bins exist on multi-level scenes only: a single leaf shades every material)
@@ -3223,7 +3316,10 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
     void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, unsigned long long*, ShadowQueueIO);
     switch (qcap) {
         case 0: k = k_path_shade<0>; break;
-        case 1: k = io.hq_d ? k_path_shade<1, true> : k_path_shade<1>; break;
+        case 1:
+            k = hit_pack ? (io.depth == 0 ? k_path_shade<1, false, true> : k_path_shade<1, true, true>)
+                         : io.hq_d ? k_path_shade<1, true> : k_path_shade<1>;
+            break;
         case 16: k = k_path_shade<16>; break;
         default: return hipErrorInvalidValue;
     }
