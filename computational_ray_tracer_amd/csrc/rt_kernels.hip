@@ -3057,8 +3057,11 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
 }
 
 // sensor + film for path mode (pixel-owned, index order)
+#ifndef RT_FILM_WAVES
+#define RT_FILM_WAVES 1  // unbudgeted: 84 / 88 VGPRs, 5 waves per SIMD (variant builds: 6 = an 80-VGPR budget)
+#endif
 template <bool MOM>  // (as k_ref_shade_film)
-__global__ void __launch_bounds__(kBlock) k_path_film(const DevSpectra* sp, DevFilm film, PathFilmIO io,
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RT_FILM_WAVES))) k_path_film(const DevSpectra* sp, DevFilm film, PathFilmIO io,
                                                       unsigned long long* ctr) {
     stage_spectra(sp);
     if (io.lean) stage_warp_tables();  // (block-uniform)

@@ -3,7 +3,7 @@
 loads / stores.
 
   hipcc --offload-arch=gfx950 --cuda-device-only -S -O3 -std=c++17 -ffp-contract=off -fno-fast-math \
-        computational_ray_tracer_amd/csrc/rt_kernels.hip -o /tmp/rtk.s && python3 tools/isa_stats.py /tmp/rtk.s
+        -fno-slp-vectorize computational_ray_tracer_amd/csrc/rt_kernels.hip -o /tmp/rtk.s && python3 tools/isa_stats.py /tmp/rtk.s
 """
 import collections
 import re

@@ -3,7 +3,7 @@
 VGPRs (SGPR-spill lanes — v_writelane / v_readlane — excluded), with a few lines of context each.
 
   hipcc --offload-arch=gfx950 --cuda-device-only -S -O3 -std=c++17 -ffp-contract=off -fno-fast-math \\
-        -munsafe-fp-atomics computational_ray_tracer_amd/csrc/rt_kernels.hip -o /tmp/rtk.s
+        -munsafe-fp-atomics -fno-slp-vectorize computational_ray_tracer_amd/csrc/rt_kernels.hip -o /tmp/rtk.s
   python3 tools/vgpr_peak.py /tmp/rtk.s k_path_shadeILi1 [top=3] [context=12]
 """
 import re
