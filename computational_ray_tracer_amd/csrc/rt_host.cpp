@@ -27,6 +27,7 @@
 #include "rt_devbuf.h"
 #include "rt_guard.h"
 #include "rt_internal.h"
+#include "rt_pass_plan.h"
 #include "rt_texture.h"
 
 using namespace rtmi;
@@ -35,8 +36,6 @@ namespace {
 
 constexpr int kRingMax = 1 << 16;  // largest BFS group FIFO (HBM ring per resident thread, 4 B per entry)
 constexpr int kMaxLights = 64;
-constexpr int kDefaultLanes = 2;   // path-mode batches in flight on separate streams (RTMI_LANES overrides; 1 lane:
-                                   // Cornell 1217, 2 lanes 1500, 3-4 lanes with 4 Mi-sample batches ~1150 Msamples/s)
 constexpr float kClusterPadRel = 1e-5f;  // cluster-box inflation per unit of scene extent (see scene upload)
 
 // ------------------------------------------------------------------------------ host float math
@@ -496,7 +495,6 @@ struct Batch {
 // One lane: its batch buffers and the state that lives as long as the context.  Path mode keeps kLanes lanes so that
 // consecutive batches run concurrently on separate streams: one batch's VALU-bound traversal overlaps the other's
 // HBM-bound path-state traffic.
-static const int kLanes = 4;
 struct Work {
     Batch b;
     DevBuf<int> qcount;  // queue q's counters at [q * kQRegion + kQLen / kQTraceTicket / ...] (rt_internal.h)
@@ -512,90 +510,6 @@ struct Work {
     hipStream_t stream = nullptr;  // lanes >= 1: own stream (lane 0 runs on the caller's stream)
     hipEvent_t film_done = nullptr;
 };
-
-// The tuning and test knobs of the environment, with their defaults (INTEGRATION.md lists them): read once per
-// context, and by rt_debug_bvh_build, so the exported and the uploaded BVHs come from the same parameters.
-struct Knobs {
-    bool stage_events = true;   // per-stage HIP events (rt_stats ms_*); RTMI_NO_STAGE_EVENTS=1 turns them off
-    int lanes = kDefaultLanes;  // batches in flight in path mode (RTMI_LANES)
-    // multi-level simple path scenes: NEE rays traced by k_path_shadow (RTMI_SHADOW_QUEUE=1; measured slower than
-    // the inline any-hit, kept as a parity-tested option), depth first (RTMI_SHADOW_DFS, exact any-hit, §6)
-    int shadow_queue = 0;
-    int shadow_dfs = 1;
-    int sort_rays = 1;         // RTMI_SORT=0: no coherence sort (A/B)
-    float bvh_node_cost = 2.5f;  // SAH node cost relative to a triangle test (RTMI_BVH_CI; r04 with 64 bins: 2.5 vs 3 CFG3 +1.6 %, CFG4 +1.2 %)
-    int bvh_max_leaf = kBvhMaxLeaf;  // triangles per BVH leaf at most (RTMI_BVH_LEAF)
-    // the any-hit walks' BVH: its own (SAH node cost 2, leaves <= 4), or with RTMI_BVH_ANY="0/4" the closest-hit BVH
-    // of set 0 itself (one working set for both queries).  r04 A/B: the shared BVH made CFG4's NEE stage 7.7 % slower
-    // (30.0 vs 27.9 ms per step): the shadow rays' better tree outweighs the smaller working set
-    float bvh_any_cost = 2.f;
-    int bvh_any_leaf = 4;
-    int force_amb = -1;        // RTMI_FORCE_AMB=k (test knob, DevScene amb_force / amb_mask): -1 off
-    int coop = 1;              // RTMI_COOP=0 (test knob): undecided rays to the fallback kernels (DevScene coop_ok 0)
-    int mat_bins = 1;          // RTMI_MAT_BINS=0: mixed multi-level scenes shade every material in one kernel (A/B)
-    int emit_filter = 1;       // RTMI_EMIT_FILTER=0: the last depth of a mixed scene traces every ray (A/B)
-    int debug_path = 0;        // RTMI_DEBUG_PATH_KERNELS=1 (tests): rt_debug_trace / _occluded run path mode's kernels
-    int sort_dir_bits = 3, sort_org_bits = 3;  // sort key widths (RTMI_SORT_BITS="dir/org[/major]"; r03 A/B: 3/3 vs 3/4 CFG3 +1 %, 2/3 -4 %)
-    // origin Morton code in the key's high bits (1) or the direction (0); -1: origin-major on the simple path, whose
-    // shade kernel traces the NEE shadow rays inline (CFG3 588 -> 600), direction-major in mixed scenes, whose NEE
-    // queue has a sort of its own (CFG4 372 vs 367)
-    int sort_org_major = -1;
-    // Morton sort of the NEE queue (mixed multi-level scenes; RTMI_SORT_NEE="on[/bits]"): CFG4 337 -> 364 at 9 bits
-    // per axis (6 / 7 bits: 353 / 356; CFG5 334 -> 355 at 7)
-    int sort_nee = 1, sort_nee_bits = 8;  // (r03, device radix sort: 8 bits = 3 passes, CFG4 +1.5 % over 9 bits = 4 passes)
-    // single-leaf simple path, depths >= 1: the trace appends its hits to a dense hit queue and the shade runs only
-    // those (TraceIO hq_d; Cornell +4.2 %, r07_ab4).  RTMI_HIT_COMPACT=0: every queue position is shaded (A/B)
-    int hit_compact = 1;
-    // the hit queue's records packed into one float4, (b0, b1, b2, slot | prim << 24 | facing << 30), the trace forming
-    // the facing bit, face normals staged in LDS, and depth 0's hit word in hitB.w (rt_internal.h hit_pack, hit_pack0):
-    // scenes of <= kHitPackTris triangles, batches of <= kHitPackSlots samples.  RTMI_HIT_PACK=0: unpacked (A/B, fallback)
-    int hit_pack = 1;
-    size_t batch_samples = 0;  // samples in flight per batch (0: 16 Mi single leaf, 32 Mi multi-level; RTMI_BATCH_SAMPLES)
-    // denoiser iterations of step 1 and 2 stage their tile and halo in LDS (same bits; RTMI_DENOISE_LDS=0: every tap a
-    // plain load, A/B in DESIGN.md §3c)
-    int denoise_lds = 1;
-};
-
-static Knobs read_knobs() {
-    Knobs k;
-    if (std::getenv("RTMI_NO_STAGE_EVENTS")) k.stage_events = false;
-    if (const char* e = std::getenv("RTMI_LANES")) k.lanes = std::max(1, std::min(kLanes, std::atoi(e)));
-    if (const char* e = std::getenv("RTMI_SHADOW_QUEUE")) k.shadow_queue = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_SHADOW_DFS")) k.shadow_dfs = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_SORT")) k.sort_rays = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_BVH_CI")) k.bvh_node_cost = (float)std::atof(e);
-    if (const char* e = std::getenv("RTMI_BVH_LEAF")) k.bvh_max_leaf = std::max(1, std::min(15, std::atoi(e)));
-    if (const char* e = std::getenv("RTMI_BVH_ANY")) {  // "cost/leaf": both fields, or the defaults stay
-        float ac;
-        int al;
-        if (std::sscanf(e, "%f/%d", &ac, &al) == 2) {
-            k.bvh_any_cost = ac;
-            k.bvh_any_leaf = std::max(1, std::min(15, al));
-        }
-    }
-    if (const char* e = std::getenv("RTMI_FORCE_AMB")) k.force_amb = std::max(-1, std::min(30, std::atoi(e)));
-    if (const char* e = std::getenv("RTMI_COOP")) k.coop = std::atoi(e) != 0;
-    if (const char* e = std::getenv("RTMI_MAT_BINS")) k.mat_bins = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_EMIT_FILTER")) k.emit_filter = std::atoi(e);
-    if (const char* e = std::getenv("RTMI_DEBUG_PATH_KERNELS")) k.debug_path = std::atoi(e) != 0;
-    if (const char* e = std::getenv("RTMI_SORT_BITS")) {
-        int db = 3, ob = 4, om = -1;
-        const int got = std::sscanf(e, "%d/%d/%d", &db, &ob, &om);
-        // the key is 3 octant bits + 2 x db direction bits + 3 x ob origin bits in one u32, ob <= 9 (spread3_9)
-        if (got >= 2 && db >= 0 && db <= 9 && ob >= 0 && ob <= 9 && 3 + 2 * db + 3 * ob <= 32) {
-            k.sort_dir_bits = db;
-            k.sort_org_bits = ob;
-            if (got == 3) k.sort_org_major = om < 0 ? -1 : (om ? 1 : 0);
-        }
-    }
-    if (const char* e = std::getenv("RTMI_SORT_NEE")) std::sscanf(e, "%d/%d", &k.sort_nee, &k.sort_nee_bits);
-    k.sort_nee_bits = std::max(1, std::min(9, k.sort_nee_bits));
-    if (const char* e = std::getenv("RTMI_HIT_COMPACT")) k.hit_compact = std::atoi(e) != 0;
-    if (const char* e = std::getenv("RTMI_HIT_PACK")) k.hit_pack = std::atoi(e) != 0;
-    if (const char* e = std::getenv("RTMI_BATCH_SAMPLES")) k.batch_samples = (size_t)std::max(0L, std::atol(e));
-    if (const char* e = std::getenv("RTMI_DENOISE_LDS")) k.denoise_lds = std::atoi(e) != 0;
-    return k;
-}
 
 struct rt_ctx {
     // coherence sort of path queues (multi-level octrees): scene quantisation of the sort key
@@ -815,21 +729,23 @@ int ensure_ring(rt_ctx* c, Work& w) {
     HIPCHK(c, w.ring.reserve((size_t)c->dsc.ring_threads * (size_t)(c->dsc.ring_mask + 1)));
     return RT_OK;
 }
-// the scene as a lane's kernels see it: its own overflow ring
-DevScene lane_scene(const rt_ctx* c, const Work& w) {
+// the scene as a pass's kernels see it: the integrator's flags are the pass's, not the context's (c->dsc keeps 0 / 0:
+// the debug entries run the simple kernels)
+DevScene pass_scene(const rt_ctx* c, const BatchPlan& bp) {
     DevScene d = c->dsc;
+    d.mis = bp.mis;
+    d.full = bp.full;
+    return d;
+}
+// ... and as a lane's kernels see it: its own overflow ring
+DevScene lane_scene(const DevScene& sc, const Work& w) {
+    DevScene d = sc;
     d.ring = w.ring.get();
     return d;
 }
 
-// the single-leaf simple path packs its hit records (Knobs hit_pack) for batches of at most nmax samples
-bool hit_pack_active(const rt_ctx* c, size_t nmax) {
-    return c->knobs.hit_pack && c->knobs.hit_compact && c->dsc.qcap == 1 && !c->dsc.full &&
-           c->dsc.n_tris <= kHitPackTris && nmax <= (size_t)kHitPackSlots;
-}
-
-// hit_pack: the path pass packs its hit records (hit_pack_active), so the batch needs no hitD
-int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path, bool hit_pack = false) {
+// hit_d: the path pass compacts its hits without packing them (PathPlan hit_d), so the batch needs hitD
+int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path, bool hit_d = false) {
     int rc;
     HIPCHK(c, w.qcount.reserve(2 * kQRegion));
     if (&w != &c->ws[0] && !w.stream) HIPCHK(c, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
@@ -838,7 +754,6 @@ int ensure_workspace(rt_ctx* c, Work& w, size_t n, bool path, bool hit_pack = fa
     Batch& b = w.b;
     // the compacted hit records' (direction, prim) stream, sized like hitB (RTMI_HIT_COMPACT: the single-leaf
     // simple path; the scene may have changed since the batch buffers were allocated)
-    const bool hit_d = path && c->knobs.hit_compact && c->dsc.qcap == 1 && !c->dsc.full && !hit_pack;
     if (b.capacity(path) >= n) {
         if (hit_d) HIPCHK(c, b.hitD.reserve(n));
         else if (path) b.hitD.reset();  // (packed records, or another scene: not kept beside the batch)
@@ -1227,318 +1142,380 @@ int render_device(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st) {
     });
 }
 
-int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, const PassTarget& pass) {
-    int rc;
+// The refusals of a pass over indices [ib, ie) that need the context (render pass and feature pass): the range, the
+// Sobol tables of the current film, the unjittered stratified sampler's index limit.
+int pass_checks(rt_ctx* c, int ib, int ie) {
     if (ib < 0 || ie < ib) return fail(c, RT_E_ARG, "invalid index range");
-    if ((rc = ensure_sobol(c))) return rc;
-    DevSampler smp = dev_sampler(c);
-    if (c->smp.kind == RT_SAMPLER_STRATIFIED && !c->smp.jitter && ie > smp.spp)
+    if (int rc = ensure_sobol(c)) return rc;
+    if (c->smp.kind == RT_SAMPLER_STRATIFIED && !c->smp.jitter && ie > dev_sampler(c).spp)
         return fail(c, RT_E_ARG, "StratifiedSampler without jitter supports indices < SamplesPerPixel (samplers.h:83-87)");
-    const int* const work = pass.work;
-    const int n_work = pass.n;
-    if (ie == ib || n_work == 0) return RT_OK;
-    bool path = c->integ.kind == RT_INTEGRATOR_PATH || c->integ.kind == RT_INTEGRATOR_PATH_MIS;
-    c->dsc.mis = c->integ.kind == RT_INTEGRATOR_PATH_MIS;
-    c->dsc.full = c->scene_full || c->dsc.mis || c->tx.live;  // (textures are fetched by the general kernels alone)
-    // samples per path batch: 16 Mi on a single-leaf octree (8 Mi: Cornell 1874 -> 1827; flat above 16 Mi, r06_ab7),
-    // 32 Mi on multi-level ones, whose fewer, fuller launches keep more rays in every wave's reach (16 -> 32 Mi: CFG3
-    // +2.5 %, CFG4 +3.5 %, flat above, r06_ab23/24)
-    const Knobs& kn = c->knobs;
-    const size_t target = kn.batch_samples ? kn.batch_samples : (size_t)(c->dsc.qcap == 1 ? 16 : 32) << 20;
-    int B = (int)std::max<size_t>(1, target / (size_t)n_work);
-    B = std::min(B, ie - ib);
-    size_t nmax = (size_t)B * n_work;
-    // queue / hit capacity: the shards of the largest batch (>= nmax); single-leaf scenes use one shard
-    const int nsh = c->dsc.qcap == 1 ? 1 : kShards;
-    const size_t ncap = (size_t)nsh * (size_t)shard_stride((int)nmax, nsh);
-    DevCamera cam = dev_camera(c->cam);
-    DevFilm fd = dev_film(c);
-    const DevSpectra* const d_spec = c->d_spec.get();
-    unsigned long long* const d_ctr = c->d_ctr.get();
-    if (!path) {
-        Work& w = c->ws[0];
-        if ((rc = ensure_workspace(c, w, ncap, false))) return rc;
-        for (int b0 = ib; b0 < ie; b0 += B) {
-            int nIdx = std::min(B, ie - b0);
-            int nS = nIdx * n_work;
-            SampleIds ids = sample_ids(work, n_work, b0);
-            RefIO r = ref_io(c, w.b, nS, nsh);
-            hipEvent_t e0 = ev_start(c, st);
-            HIPCHK(c, launch_generate(st, c->grid, nS, ids, cam, smp, fd, r.go));
-            ev_mark(c, st, ST_GEN, e0);
-            e0 = ev_start(c, st);
-            HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), r.tio, d_ctr));
-            ev_mark(c, st, ST_TRACE, e0);
-            r.sio.work_pixels = work; r.sio.n_pixels = n_work; r.sio.n_index = nIdx;
-            r.sio.film = film;
-            r.sio.mom = pass.mom;
-            e0 = ev_start(c, st);
-            HIPCHK(c, launch_ref_shade_film(st, 0, c->dsc, d_spec, fd, r.sio, d_ctr));
-            ev_mark(c, st, ST_FILM, e0);
-        }
-        return RT_OK;
-    }
+    return RT_OK;
+}
+// what a pass over [ib, ie) of n_work pixels is planned from (rt_pass_plan.h)
+PassFacts pass_facts(const rt_ctx* c, int n_work, int ib, int ie) {
+    PassFacts f;
+    f.qcap = c->dsc.qcap; f.n_tris = c->dsc.n_tris; f.n_lights = c->dsc.n_lights;
+    f.n_emit_tris = c->dsc.n_emit_tris; f.coop_ok = c->dsc.coop_ok;
+    f.scene_full = c->scene_full; f.textures = c->tx.live; f.mesh_light = c->ml.any;
+    f.integ = c->integ.kind == RT_INTEGRATOR_PATH_MIS ? kIntegPathMis
+              : c->integ.kind == RT_INTEGRATOR_PATH   ? kIntegPath : kIntegReference;
+    f.max_depth = c->integ.max_depth;
+    f.n_work = n_work; f.ib = ib; f.ie = ie;
+    return f;
+}
 
-    // ---- path mode: up to c->lanes batches in flight, batch k on lane k mod lanes (lane 0 = the caller's stream).
-    // Within a lane everything is stream-ordered; across lanes only the film kernels are chained (batch k's film
-    // after batch k-1's), so every pixel still adds its sample indices in increasing order.
-    const int nbatch = (ie - ib + B - 1) / B;
-    const int lanes = std::max(1, std::min(std::min(kn.lanes, kLanes), nbatch));
-    // multi-level octrees: coherence-sort each bounce's rays (rt_sort.hip); on the single-leaf Cornell box the sort
-    // costs more than it saves (1110 -> 720 Msamples/s)
-    const bool sort_rays = c->dsc.qcap != 1 && kn.sort_rays;
-    // single-leaf simple path: packed hit records while every slot of a batch fits the record's 24-bit field
-    const bool hpack = hit_pack_active(c, nmax);
-    for (int l = 0; l < lanes; ++l) {
-        if ((rc = ensure_workspace(c, c->ws[l], ncap, true, hpack))) return rc;
-        if (sort_rays && (rc = ensure_sort_workspace(c, c->ws[l].b, ncap))) return rc;
-        // the trace-fallback list (multi-level octrees): one entry per queue position at most
-        if (c->dsc.qcap != 1) HIPCHK(c, c->ws[l].tfb.reserve(ncap));
+// One trace launch of path mode, and the exact BFS for the rays it listed when the plan says one may be (BatchPlan
+// trace_fallback), as one ST_TRACE stage: the path pass's bounces and the chain pass's levels.
+int trace_with_fallback(rt_ctx* c, hipStream_t s, const DevScene& sc, const TraceIO& tio, bool fallback) {
+    hipEvent_t e0 = ev_start(c, s);
+    HIPCHK(c, launch_trace_closest(s, c->grid, sc.qcap, sc, tio, c->d_ctr.get()));
+    if (fallback) HIPCHK(c, launch_trace_fallback(s, c->grid, sc.qcap, sc, tio, c->d_ctr.get()));
+    ev_mark(c, s, ST_TRACE, e0);
+    return RT_OK;
+}
+
+// ---- the reference integrator's pass: one batch at a time on the caller's stream
+int render_reference(rt_ctx* c, const BatchPlan& bp, int ib, int ie, float4* film, hipStream_t st,
+                     const PassTarget& pass) {
+    const DevCamera cam = dev_camera(c->cam);
+    const DevSampler smp = dev_sampler(c);
+    const DevFilm fd = dev_film(c);
+    const DevScene sc = pass_scene(c, bp);
+    Work& w = c->ws[0];
+    if (int rc = ensure_workspace(c, w, bp.ncap, false)) return rc;
+    for (int b0 = ib; b0 < ie; b0 += bp.B) {
+        int nIdx = std::min(bp.B, ie - b0);
+        int nS = nIdx * pass.n;
+        SampleIds ids = sample_ids(pass.work, pass.n, b0);
+        RefIO r = ref_io(c, w.b, nS, bp.nsh);
+        hipEvent_t e0 = ev_start(c, st);
+        HIPCHK(c, launch_generate(st, c->grid, nS, ids, cam, smp, fd, r.go));
+        ev_mark(c, st, ST_GEN, e0);
+        e0 = ev_start(c, st);
+        HIPCHK(c, launch_trace_closest(st, 0, sc.qcap, lane_scene(sc, w), r.tio, c->d_ctr.get()));
+        ev_mark(c, st, ST_TRACE, e0);
+        r.sio.work_pixels = pass.work; r.sio.n_pixels = pass.n; r.sio.n_index = nIdx;
+        r.sio.film = film;
+        r.sio.mom = pass.mom;
+        e0 = ev_start(c, st);
+        HIPCHK(c, launch_ref_shade_film(st, 0, sc, c->d_spec.get(), fd, r.sio, c->d_ctr.get()));
+        ev_mark(c, st, ST_FILM, e0);
     }
-    // Cornell-like single-leaf scenes cost the same per ray: static chunks on a resident grid beat tickets there
-    // (A/B 1229 vs 1106-1158 Msamples/s); multi-level octrees vary per ray by 100x: tickets (CFG3 71 -> 96)
-    const bool dyn = c->dsc.qcap != 1;
-    // k_generate stores no β = 1 / L = 0 / pdf streams: depth 0 starts from them in registers and the film recomputes
-    // the pdf (simple path: +4.5 %).  1: the simple path (the host derives each depth's sampler dimension); 2: mixed
-    // scenes, whose slots keep their dimension, prevPdf and TerminateSecondary flag in R_MISC (CFG4: k_generate
-    // writes 96 instead of 192 B per sample)
-    const int lean = c->dsc.full ? 2 : 1;
-    // multi-level simple scenes: the NEE shadow rays the BVH alone cannot decide (or, with RTMI_SHADOW_QUEUE=1,
-    // all of them) are queued and traced exactly by their own kernel
-    const bool shq = c->dsc.qcap != 1 && !c->dsc.full;
-    if (shq)
-        for (int l = 0; l < lanes; ++l)
-            if ((rc = ensure_shadow_workspace(c, c->ws[l].b, ncap))) return rc;
-    // mixed scenes: NEE deferred to k_path_nee (one record per slot, one queue entry per Lambert vertex)
-    const bool nee = c->dsc.full && c->dsc.n_lights > 0;
-    if (nee)
-        for (int l = 0; l < lanes; ++l)
-            if ((rc = ensure_nee_workspace(c, c->ws[l].b, nmax * (size_t)nee_stride(c->dsc.n_lights), ncap))) return rc;
-    // mixed multi-level scenes: the trace kernel bins the hits by material class and each class is shaded by a kernel
-    // holding only its materials' code (k_path_shade_full<Q, 1 / 2>)
-    const bool bins = nee && c->dsc.qcap != 1 && kn.mat_bins;
-    // Concurrent lanes share the CUs.  Each launch still asks for every resident block (grid_div 1): the dispatcher
-    // hands blocks to whichever lane's kernel has them pending, so a VALU-bound trace and an HBM-bound shade of the
-    // other lane end up co-resident (Cornell A/B: 1 lane 1217, 2 lanes with half grids 1422, with full grids 1500)
-    const int grid = c->grid;
-    auto lstream = [&](int l) { return l == 0 ? st : c->ws[l].stream; };
+    return RT_OK;
+}
+
+// ---- path mode: up to PathPlan lanes batches in flight, batch k on lane k mod lanes (lane 0 = the caller's stream).
+// Within a lane everything is stream-ordered; across lanes only the film kernels are chained (batch k's film after
+// batch k-1's), so every pixel still adds its sample indices in increasing order.
+//
+// Concurrent lanes share the CUs.  Each launch still asks for every resident block (grid_div 1): the dispatcher hands
+// blocks to whichever lane's kernel has them pending, so a VALU-bound trace and an HBM-bound shade of the other lane
+// end up co-resident (Cornell A/B: 1 lane 1217, 2 lanes with half grids 1422, with full grids 1500)
+
+// what the stages of one path pass share
+struct PathPass {
+    rt_ctx* c;
+    BatchPlan bp;
+    PathPlan pp;
+    DevScene sc;  // pass_scene
+    DevCamera cam;
+    DevSampler smp;
+    DevFilm fd;
+    PassTarget target;
+    float4* film;
+};
+// one lane's batch in flight
+struct Lane {
+    Work* w = nullptr;
+    hipStream_t s = nullptr;
+    DevScene sc{};   // lane_scene
+    RecView rv{};
+    SampleIds ids{};
+    int nIdx = 0;    // sample indices of the batch
+    int nS = 0;      // its samples
+    int S = 0;       // shard stride of every queue of this batch: shard j at [j S, j S + len_j)
+    int cur = 0;     // the current ray queue of the two (ping-pong; ncap entries each)
+    float4* rays(const PathPass& p, int q) const { return w->b.rayO() + 2 * (size_t)q * p.bp.ncap; }
+    int* counters(int q) const { return w->qcount.get() + kQRegion * q; }
+};
+// one lane's bounce at one depth: what the stages hand on
+struct Bounce {
+    int depth;
+    DepthPlan d;
+    int* qc_cur;            // the counter regions of the current and the next queue
+    int* qc_nxt;
+    const float4* cO;       // the rays the trace and the shade read (the queue's, the filtered or the sorted ones)
+    QueueView qv;           // ... and their queue
+    TraceIO tio{};
+    PathIO pio{};           // the shade's, read by the NEE and shadow stages too
+    ShadowQueueIO sqio{};
+    NeeIO nio{};
+};
+
+int path_workspaces(const PathPass& p) {
+    rt_ctx* c = p.c;
+    const BatchPlan& bp = p.bp;
+    const PathPlan& pp = p.pp;
+    for (int l = 0; l < pp.lanes; ++l) {
+        Work& w = c->ws[l];
+        int rc;
+        if ((rc = ensure_workspace(c, w, bp.ncap, true, pp.hit_d()))) return rc;
+        if (pp.sort_rays && (rc = ensure_sort_workspace(c, w.b, bp.ncap))) return rc;
+        // the trace-fallback list (multi-level octrees): one entry per queue position at most
+        if (bp.dyn) HIPCHK(c, w.tfb.reserve(bp.ncap));
+    }
+    for (int l = 0; l < pp.lanes && pp.shq; ++l)
+        if (int rc = ensure_shadow_workspace(c, c->ws[l].b, bp.ncap)) return rc;
+    for (int l = 0; l < pp.lanes && pp.nee; ++l)
+        if (int rc = ensure_nee_workspace(c, c->ws[l].b, bp.nmax * (size_t)nee_stride(p.sc.n_lights), bp.ncap)) return rc;
+    return RT_OK;
+}
+
+// lane l takes the batch of indices [b0, min(b0 + B, ie)) and generates its camera rays
+int stage_generate(const PathPass& p, Lane& L, int l, int b0, int ie, hipStream_t st) {
+    rt_ctx* c = p.c;
+    L.w = &c->ws[l];
+    L.s = l == 0 ? st : L.w->stream;
+    L.sc = lane_scene(p.sc, *L.w);
+    L.rv = RecView{L.w->b.rec.get(), p.pp.rec_fs, p.pp.rec_ss, p.pp.rec_rng8};
+    L.ids = sample_ids(p.target.work, p.target.n, b0);
+    L.nIdx = std::min(p.bp.B, ie - b0);
+    L.nS = L.nIdx * p.target.n;
+    L.S = shard_stride(L.nS, p.bp.nsh);
+    L.cur = 0;
+    const Batch& b = L.w->b;
+    GenOut go{b.rayO(), b.rayD(), nullptr, nullptr, b.pdfA.get(), b.pdfB.get(), L.rv, p.pp.lean, 1};
+    // camera rays fill queue 0 densely (positions 0..nS-1: QueueView without lengths); both counter regions
+    // start at zero: k_generate zeroes them (a memset launch here waited for the other lane's resident blocks
+    // in two-lane mode, r05 kernel traces)
+    go.zero = L.w->qcount.get();
+    hipEvent_t e0 = ev_start(c, L.s);
+    HIPCHK(c, launch_generate(L.s, c->grid, L.nS, L.ids, p.cam, p.smp, p.fd, go));
+    ev_mark(c, L.s, ST_GEN, e0);
+    return RT_OK;
+}
+
+// emitter filter, coherence sort, the trace and its fallback
+int stage_trace(const PathPass& p, const Lane& L, Bounce& bo) {
+    rt_ctx* c = p.c;
+    const Batch& b = L.w->b;
+    const DepthPlan& d = bo.d;
+    const Knobs& kn = c->knobs;
+    bo.qc_cur = L.counters(L.cur);
+    bo.qc_nxt = L.counters(L.cur ^ 1);
+    bo.cO = L.rays(p, L.cur);
+    bo.qv = bo.depth == 0 ? QueueView{nullptr, L.S, L.nS, p.bp.nsh} : QueueView{bo.qc_cur + kQLen, L.S, 0, p.bp.nsh};
+    hipEvent_t e0;
+    // the next queue's length and the chunk tickets its trace and shade launches will use start at zero: depth 0
+    // (k_generate zeroed both regions) / the trace kernel zeroes it (below), except before the emitter filter, which
+    // appends to it ahead of the trace: its survivors go into the free next queue, whose rays the trace and shade
+    // kernels then take (the shade appends nothing at this depth)
+    if (d.efilter) {
+        HIPCHK(c, hipMemsetAsync(bo.qc_nxt, 0, kQRegion * sizeof(int), L.s));
+        const EmitIO eio{bo.qv, bo.cO, L.rays(p, L.cur ^ 1), bo.qc_nxt + kQLen};
+        e0 = ev_start(c, L.s);
+        HIPCHK(c, launch_emitter_filter(L.s, c->grid, L.sc, eio));
+        ev_mark(c, L.s, ST_FILTER, e0);
+        bo.cO = eio.nO;
+        bo.qv = QueueView{bo.qc_nxt + kQLen, L.S, 0, p.bp.nsh};
+    }
+    TraceIO& tio = bo.tio;
+    tio = TraceIO{bo.cO, bo.cO + 1, bo.qv, 0, b.hitB.get(), b.hitPrim.get(),
+                  p.bp.dyn ? bo.qc_cur + kQTraceTicket : nullptr, 1};
+    if (bo.depth > 0 && !d.efilter) tio.zero = bo.qc_nxt;
+    // packed hit records, depth 0: the hit word (prim, flip, front) in hitB's w lane, so the shade reads hitB alone
+    // (no hitPrim, no ray).  Nothing else reads this depth's hits on the simple path.
+    if (d.pack0) tio.hq_pack = 1;
+    // the hit queue's length word is this queue's shadow-queue length, which single-leaf scenes never use (zero before
+    // the launch like the rest of the region)
+    if (d.hit_compact) {
+        if (d.hit_pack) tio.hq_pack = 1;
+        else tio.hq_d = b.hitD.get();
+        tio.hq_len = bo.qc_cur + kQShadowLen;
+    }
+    if (p.bp.dyn) {  // ambiguous rays listed for k_trace_fallback
+        tio.fb_pos = L.w->tfb.get();
+        tio.fb_len = bo.qc_cur + kQTraceFallback;
+    }
+    // multi-level octrees: bounce rays sorted by (octant, direction cell, origin Morton code) before the trace.  The
+    // device reads the queue length itself, so only live rays are sorted and the host reads nothing back (sorting the
+    // capacity with padded keys: -0.6 %)
+    if (d.sort) {
+        SortRaysIO so{b.sQKey.get(), b.sS.get(), b.sKeys.get(), b.sKeysAlt.get(), b.sVals.get(), b.sValsAlt.get(),
+                      b.sTemp.get(), kn.sort_dir_bits, kn.sort_org_bits, bo.qc_cur + kQLen, L.S};
+        e0 = ev_start(c, L.s);
+        HIPCHK(c, launch_sort_rays(L.s, so));
+        ev_mark(c, L.s, ST_SORT, e0);
+        tio.perm = b.sS.get();  // the trace kernel gathers the sorted rays into the side queue
+        tio.so = b.sRay.get();
+        bo.cO = tio.so;
+    }
+    return trace_with_fallback(c, L.s, L.sc, tio, d.trace_fallback);
+}
+
+// the shade's arguments over the traced rays: PathIO, the shadow queue, the NEE queue
+void shade_io(const PathPass& p, const Lane& L, Bounce& bo) {
+    const rt_ctx* c = p.c;
+    const Batch& b = L.w->b;
+    const PathPlan& pp = p.pp;
+    const Knobs& kn = c->knobs;
+    PathIO& pio = bo.pio;
+    pio.lean = pp.lean;
+    pio.rayO = bo.cO; pio.rayD = bo.cO + 1; pio.q = bo.qv;
+    pio.hitB = b.hitB.get(); pio.hitPrim = b.hitPrim.get();
+    if (bo.d.hit_compact) {  // items = the hit records (PathIO hq_d)
+        pio.q = QueueView{bo.tio.hq_len, L.S, 0, p.bp.nsh};
+        pio.hq_d = bo.tio.hq_d;
+    }
+    pio.nO = L.rays(p, L.cur ^ 1); pio.nD = pio.nO + 1;
+    pio.nCount = bo.qc_nxt + kQLen;
+    pio.rec = L.rv; pio.pdfA = b.pdfA.get(); pio.pdfB = b.pdfB.get();
+    pio.depth = bo.depth; pio.max_depth = pp.max_depth;
+    pio.dim = -1;
+    if (pp.lean == 1) {
+        pio.dim = dim_after_camera(p.smp, p.cam);
+        for (int d = 0; d < bo.depth; ++d) pio.dim = dim_get2d(p.smp, dim_get2d(p.smp, pio.dim));
+    }
+    pio.ticket = p.bp.dyn ? bo.qc_cur + kQShadeTicket : nullptr;
+    if (bo.d.next_keys) {  // keys of the rays this shade appends (next sort)
+        pio.nkey.key = b.sQKey.get();
+        pio.nkey.lo = c->sort_lo;
+        pio.nkey.scale = c->sort_scale;
+        pio.nkey.dir_bits = kn.sort_dir_bits;
+        pio.nkey.org_bits = kn.sort_org_bits;
+        pio.nkey.org_major = pp.org_major;
+    }
+    if (pp.shq) {  // this queue's region holds the shadow-queue length and ticket (zeroed with it)
+        ShadowQueueIO& sq = bo.sqio;
+        sq.shO = b.shO.get(); sq.shD = b.shD.get(); sq.shLA = b.shLA.get(); sq.shLB = b.shLB.get();
+        sq.shCount = bo.qc_cur + kQShadowLen;
+        sq.shTicket = bo.qc_cur + kQShadowTicket;
+        sq.defer = pp.defer;
+    }
+    if (pp.nee)
+        bo.nio = NeeIO{b.neeRec.get(), b.nee.queue, bo.qc_cur + kQShadowLen, bo.qc_cur + kQShadowTicket, b.nee.fallback,
+                       bo.qc_cur + kQNeeFallback, pp.sort_nee ? b.nee.key : nullptr, c->sort_lo, c->sort_scale,
+                       kn.sort_nee_bits};
+    if (c->tx.live) bo.nio.tex = c->tx.dev.get();
+    bo.nio.ml = pp.ml;
+}
+
+// the shade: one kernel, or the hits binned by material and one kernel per bin over its index list
+int stage_shade(const PathPass& p, const Lane& L, Bounce& bo) {
+    rt_ctx* c = p.c;
+    const Batch& b = L.w->b;
+    shade_io(p, L, bo);
+    const DevSpectra* const d_spec = c->d_spec.get();
+    hipEvent_t e0 = ev_start(c, L.s);
+    if (p.pp.bins) {
+        BinIO bio{bo.qv, b.hitPrim.get(), {}, bo.qc_cur + kQBinLen};
+        for (int cl = 0; cl < kMatClasses; ++cl) bio.idx[cl] = b.nee.bin[cl];
+        if (bo.depth == 0) { bio.rayO = bo.cO; bio.rec = L.rv; }  // lean depth 0: the misses' L = 0 (BinIO)
+        HIPCHK(c, launch_bin_materials(L.s, c->grid, L.sc, bio));
+        for (int cl = 0; cl < kMatClasses; ++cl) {
+            PathIO bp = bo.pio;
+            bp.q = QueueView{bo.qc_cur + kQBinLen + cl * kShards * kQStride, L.S, 0, p.bp.nsh};
+            bp.ticket = bo.qc_cur + kQBinTicket + cl * kShards * kQStride;
+            bp.bin_idx = bio.idx[cl];
+            HIPCHK(c, launch_path_shade(L.s, c->grid, L.sc.qcap, L.sc, d_spec, p.smp, p.fd, L.ids, bp, c->d_ctr.get(),
+                                        bo.sqio, bo.nio, 1 + cl));
+        }
+    } else {
+        HIPCHK(c, launch_path_shade(L.s, c->grid, L.sc.qcap, L.sc, d_spec, p.smp, p.fd, L.ids, bo.pio, c->d_ctr.get(),
+                                    bo.sqio, bo.nio, 0, p.pp.hit_pack));
+    }
+    ev_mark(c, L.s, ST_SHADE, e0);
+    return RT_OK;
+}
+
+// mixed scenes: the NEE queue's sort, this bounce's shadow rays (before the next bounce reads L), their fallback
+int stage_nee(const PathPass& p, const Lane& L, const Bounce& bo) {
+    rt_ctx* c = p.c;
+    const Batch& b = L.w->b;
+    if (!p.pp.nee) return RT_OK;
+    hipEvent_t e0;
+    if (p.pp.sort_nee) {  // (no host round trip)
+        SortNeeIO so{b.nee.queue, bo.qc_cur + kQShadowLen, L.S, b.nee.key, b.sKeys.get(), b.sKeysAlt.get(),
+                     b.sVals.get(), b.sValsAlt.get(), b.sTemp.get(), c->knobs.sort_nee_bits};
+        e0 = ev_start(c, L.s);
+        HIPCHK(c, launch_sort_nee(L.s, so));
+        ev_mark(c, L.s, ST_SORT, e0);
+    }
+    e0 = ev_start(c, L.s);
+    HIPCHK(c, launch_path_nee(L.s, c->grid, L.sc.qcap, L.sc, c->d_spec.get(), bo.pio, bo.nio, c->d_ctr.get()));
+    if (bo.d.nee_fallback)
+        HIPCHK(c, launch_path_nee_fallback(L.s, c->grid, L.sc.qcap, L.sc, c->d_spec.get(), bo.pio, bo.nio, c->d_ctr.get()));
+    ev_mark(c, L.s, ST_SHADOW, e0);
+    return RT_OK;
+}
+
+// multi-level simple scenes: the queued shadow rays
+int stage_shadow(const PathPass& p, const Lane& L, const Bounce& bo) {
+    rt_ctx* c = p.c;
+    if (!bo.d.shadow) return RT_OK;
+    hipEvent_t e0 = ev_start(c, L.s);
+    HIPCHK(c, launch_path_shadow(L.s, c->grid, L.sc.qcap, c->knobs.shadow_dfs != 0, L.sc, bo.pio, bo.sqio, c->d_ctr.get()));
+    ev_mark(c, L.s, ST_SHADOW, e0);
+    return RT_OK;
+}
+
+// the batch's samples into the film, after the previous batch's (after: the lane of the most recent film launch)
+int stage_film(const PathPass& p, const Lane& L, const Work* after) {
+    rt_ctx* c = p.c;
+    const Batch& b = L.w->b;
+    if (after && after != L.w) HIPCHK(c, hipStreamWaitEvent(L.s, after->film_done, 0));
+    PathFilmIO fio{p.target.work, p.target.n, L.nIdx, L.rv, b.pdfA.get(), b.pdfB.get(), p.film};
+    fio.lean = p.pp.lean;
+    fio.mom = p.target.mom;
+    hipEvent_t e0 = ev_start(c, L.s);
+    HIPCHK(c, launch_path_film(L.s, 0, c->d_spec.get(), p.fd, fio, c->d_ctr.get()));
+    ev_mark(c, L.s, ST_FILM, e0);
+    HIPCHK(c, hipEventRecord(L.w->film_done, L.s));
+    return RT_OK;
+}
+
+int render_path(rt_ctx* c, const PassFacts& f, const BatchPlan& bp, int ib, int ie, float4* film, hipStream_t st,
+                const PassTarget& pass) {
+    const PathPass p{c, bp, plan_path(f, c->knobs, bp), pass_scene(c, bp), dev_camera(c->cam), dev_sampler(c),
+                     dev_film(c), pass, film};
+    const int lanes = p.pp.lanes;
+    int rc;
+    if ((rc = path_workspaces(p))) return rc;
     if (lanes > 1) {  // lanes 1.. start after the caller's earlier work on st
         HIPCHK(c, hipEventRecord(c->ws[0].film_done, st));
         for (int l = 1; l < lanes; ++l) HIPCHK(c, hipStreamWaitEvent(c->ws[l].stream, c->ws[0].film_done, 0));
     }
-    const size_t qs = ncap;  // one queue (nsh shards of stride Sq[lane])
-    // slot state layout (rt_internal.h RecView): records for multi-level scenes (sorted, scattered slots), SoA for
-    // single-leaf ones (slots stay in queue order)
-    const bool records = c->dsc.qcap != 1;
-    const size_t rec_fs = records ? 1 : nmax;
-    const unsigned rec_ss = records ? (unsigned)kRecF4 : 1u;
-    const int rec_rng8 = !records && lean == 1 ? 1 : 0;  // SoA simple path: dense 8-byte PCG states
-    int last_film = -1;      // lane of the most recent film launch
-    for (int g0 = ib; g0 < ie; g0 += B * lanes) {
-        int nIdx[kLanes] = {0}, cur[kLanes] = {0}, nSq[kLanes] = {0}, Sq[kLanes] = {0};
-        for (int l = 0; l < lanes; ++l) {
-            int b0 = g0 + l * B;
-            if (b0 >= ie) break;
-            Work& w = c->ws[l];
-            const Batch& b = w.b;
-            hipStream_t s = lstream(l);
-            const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
-            nIdx[l] = std::min(B, ie - b0);
-            int nS = nIdx[l] * n_work;
-            nSq[l] = nS;
-            Sq[l] = shard_stride(nS, nsh);  // every queue of this batch: shard j at [j S, j S + len_j)
-            SampleIds ids = sample_ids(work, n_work, b0);
-            GenOut go{b.rayO(), b.rayD(), nullptr, nullptr, b.pdfA.get(), b.pdfB.get(), rv, lean, 1};
-            // camera rays fill queue 0 densely (positions 0..nS-1: QueueView without lengths); both counter regions
-            // start at zero: k_generate zeroes them (a memset launch here waited for the other lane's resident blocks
-            // in two-lane mode, r05 kernel traces)
-            go.zero = w.qcount.get();
-            hipEvent_t e0 = ev_start(c, s);
-            HIPCHK(c, launch_generate(s, grid, nS, ids, cam, smp, fd, go));
-            ev_mark(c, s, ST_GEN, e0);
-        }
-        for (int depth = 0; depth <= c->integ.max_depth; ++depth) {
-            // the last trace can only add emitter hits, which count only after specular bounces or with MIS
-            if (depth == c->integ.max_depth && depth > 0 && !c->dsc.full) break;
-            for (int l = 0; l < lanes && nIdx[l] > 0; ++l) {
-                Work& w = c->ws[l];
-                const Batch& b = w.b;
-                hipStream_t s = lstream(l);
-                const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
-                SampleIds ids = sample_ids(work, n_work, g0 + l * B);
-                int nxt = cur[l] ^ 1;
-                const float4* cO = b.rayO() + 2 * (size_t)cur[l] * qs;
-                const float4* cD = cO + 1;
-                int* qc_cur = w.qcount.get() + kQRegion * cur[l];
-                int* qc_nxt = w.qcount.get() + kQRegion * nxt;
-                // the last depth of a mixed scene: only emitter hits still add to L, so the rays that hit no emissive
-                // surface are dropped first (k_emitter_filter, EmitIO) into the free next queue, whose rays the trace
-                // and shade kernels then take (the shade appends nothing at this depth); no coherence sort
-                const bool efilter = kn.emit_filter && c->dsc.full && depth == c->integ.max_depth && depth > 0 &&
-                                     c->dsc.n_emit_tris >= 0;
-                // the next queue's length and the chunk tickets its trace and shade launches will use start at zero:
-                // depth 0 (k_generate zeroed both regions) / the trace kernel zeroes it (below), except before the
-                // emitter filter, which appends to it ahead of the trace
-                if (efilter) HIPCHK(c, hipMemsetAsync(qc_nxt, 0, kQRegion * sizeof(int), s));
-                hipEvent_t e0;
-                // multi-level octrees: bounce rays sorted by (octant, direction cell, origin Morton code) before
-                // the trace.  The queue length is read back so only live rays are sorted (sorting the capacity with
-                // padded keys instead, without the host read: -0.6 %); the other lane keeps the GPU busy meanwhile.
-                QueueView qv = depth == 0 ? QueueView{nullptr, Sq[l], nSq[l], nsh}
-                                          : QueueView{qc_cur + kQLen, Sq[l], 0, nsh};
-                const DevScene dsl = lane_scene(c, w);
-                if (efilter) {
-                    const EmitIO eio{qv, cO, b.rayO() + 2 * (size_t)nxt * qs, qc_nxt + kQLen};
-                    e0 = ev_start(c, s);
-                    HIPCHK(c, launch_emitter_filter(s, grid, dsl, eio));
-                    ev_mark(c, s, ST_FILTER, e0);
-                    cO = eio.nO;
-                    cD = cO + 1;
-                    qv = QueueView{qc_nxt + kQLen, Sq[l], 0, nsh};
-                }
-                TraceIO tio{cO, cD, qv, 0, b.hitB.get(), b.hitPrim.get(), dyn ? qc_cur + kQTraceTicket : nullptr, 1};
-                if (depth > 0 && !efilter) tio.zero = qc_nxt;
-                // packed hit records, depth 0: the hit word (prim, flip, front) in hitB's w lane, so the shade reads
-                // hitB alone (no hitPrim, no ray).  Nothing else reads this depth's hits on the simple path.
-                if (hpack && depth == 0) tio.hq_pack = 1;
-                // single-leaf simple path, bounce depths: the trace appends its hits to a dense hit queue and the shade
-                // runs only those.  The length word is this queue's shadow-queue length, which single-leaf scenes
-                // never use (zero before the launch like the rest of the region).  Depth 0 keeps its dense queue:
-                // slot = position, and the lean path writes L = 0 for the camera misses there.
-                const bool hitc = kn.hit_compact && c->dsc.qcap == 1 && !c->dsc.full && depth > 0;
-                if (hitc) {
-                    if (hpack) tio.hq_pack = 1;  // one float4 per record: hitD is neither allocated nor touched
-                    else tio.hq_d = b.hitD.get();
-                    tio.hq_len = qc_cur + kQShadowLen;
-                }
-                if (c->dsc.qcap != 1) {  // ambiguous rays listed for k_trace_fallback (the trace holds no BFS)
-                    tio.fb_pos = w.tfb.get();
-                    tio.fb_len = qc_cur + kQTraceFallback;
-                }
-                const NeeSlots ns = nee ? b.nee : NeeSlots{};
-                BinIO bio{qv, b.hitPrim.get(), {}, qc_cur + kQBinLen};
-                for (int cl = 0; cl < kMatClasses; ++cl) bio.idx[cl] = ns.bin[cl];
-                if (depth == 0) { bio.rayO = cO; bio.rec = rv; }  // lean depth 0: the misses' L = 0 (BinIO)
-                if (sort_rays && depth > 0 && !efilter) {  // the device reads the queue length itself: no host read
-                    SortRaysIO so{b.sQKey.get(), b.sS.get(), b.sKeys.get(), b.sKeysAlt.get(), b.sVals.get(),
-                                  b.sValsAlt.get(), b.sTemp.get(), kn.sort_dir_bits, kn.sort_org_bits, qc_cur + kQLen,
-                                  Sq[l]};
-                    e0 = ev_start(c, s);
-                    HIPCHK(c, launch_sort_rays(s, so));
-                    ev_mark(c, s, ST_SORT, e0);
-                    tio.perm = b.sS.get();  // the trace kernel gathers the sorted rays into the side queue
-                    tio.so = b.sRay.get();
-                    cO = tio.so; cD = cO + 1;
-                }
-                e0 = ev_start(c, s);
-                HIPCHK(c, launch_trace_closest(s, grid, c->dsc.qcap, dsl, tio, d_ctr));
-                // (an ambiguous ray is listed only if the cooperative BFS's FIFO overflows, which the octree's exact
-                // queue bound excludes when coop_ok: then no launch, which in two-lane mode would wait for the other
-                // lane's resident blocks, r05 kernel traces: 1.28 ms per bounce)
-                if (tio.fb_pos && !c->dsc.coop_ok)
-                    HIPCHK(c, launch_trace_fallback(s, grid, c->dsc.qcap, dsl, tio, d_ctr));
-                ev_mark(c, s, ST_TRACE, e0);
-                PathIO pio{};
-                pio.lean = lean;
-                pio.rayO = cO; pio.rayD = cD; pio.q = qv;
-                pio.hitB = b.hitB.get(); pio.hitPrim = b.hitPrim.get();
-                if (hitc) {  // items = the hit records (PathIO hq_d)
-                    pio.q = QueueView{tio.hq_len, Sq[l], 0, nsh};
-                    pio.hq_d = tio.hq_d;
-                }
-                pio.nO =b.rayO() + 2 * (size_t)nxt * qs; pio.nD = pio.nO + 1;
-                pio.nCount = qc_nxt + kQLen;
-                pio.rec = rv; pio.pdfA = b.pdfA.get(); pio.pdfB = b.pdfB.get();
-                pio.depth = depth; pio.max_depth = c->integ.max_depth;
-                pio.dim = -1;
-                if (lean == 1) {
-                    pio.dim = dim_after_camera(smp, cam);
-                    for (int d = 0; d < depth; ++d) pio.dim = dim_get2d(smp, dim_get2d(smp, pio.dim));
-                }
-                pio.ticket = dyn ? qc_cur + kQShadeTicket : nullptr;
-                if (sort_rays && depth < c->integ.max_depth) {  // keys of the rays this shade appends (next sort)
-                    pio.nkey.key = b.sQKey.get();
-                    pio.nkey.lo = c->sort_lo;
-                    pio.nkey.scale = c->sort_scale;
-                    pio.nkey.dir_bits = kn.sort_dir_bits;
-                    pio.nkey.org_bits = kn.sort_org_bits;
-                    pio.nkey.org_major = kn.sort_org_major >= 0 ? kn.sort_org_major : (c->dsc.full ? 0 : 1);
-                }
-                ShadowQueueIO sqio{};
-                if (shq) {  // this queue's region holds the shadow-queue length and ticket (zeroed with it)
-                    sqio.shO = b.shO.get(); sqio.shD = b.shD.get(); sqio.shLA = b.shLA.get(); sqio.shLB = b.shLB.get();
-                    sqio.shCount = qc_cur + kQShadowLen;
-                    sqio.shTicket = qc_cur + kQShadowTicket;
-                    sqio.defer = kn.shadow_queue ? 0 : 1;
-                }
-                NeeIO nio{};
-                const bool sort_nee = nee && sort_rays && kn.sort_nee;
-                if (nee)
-                    nio = NeeIO{b.neeRec.get(), ns.queue, qc_cur + kQShadowLen, qc_cur + kQShadowTicket, ns.fallback,
-                                qc_cur + kQNeeFallback, sort_nee ? ns.key : nullptr, c->sort_lo, c->sort_scale,
-                                kn.sort_nee_bits};
-                if (c->tx.live) nio.tex = c->tx.dev.get();
-                nio.ml = c->ml.any ? 1 : 0;
-                e0 = ev_start(c, s);
-                if (bins) {  // the hits binned by material, then one kernel per bin over its index list
-                    HIPCHK(c, launch_bin_materials(s, grid, dsl, bio));
-                    for (int cl = 0; cl < kMatClasses; ++cl) {
-                        PathIO bp = pio;
-                        bp.q = QueueView{qc_cur + kQBinLen + cl * kShards * kQStride, Sq[l], 0, nsh};
-                        bp.ticket = qc_cur + kQBinTicket + cl * kShards * kQStride;
-                        bp.bin_idx = bio.idx[cl];
-                        HIPCHK(c, launch_path_shade(s, grid, c->dsc.qcap, dsl, d_spec, smp, fd, ids, bp, d_ctr,
-                                                    sqio, nio, 1 + cl));
-                    }
-                } else {
-                    HIPCHK(c, launch_path_shade(s, grid, c->dsc.qcap, dsl, d_spec, smp, fd, ids, pio, d_ctr, sqio,
-                                                nio, 0, hpack));
-                }
-                ev_mark(c, s, ST_SHADE, e0);
-                if (sort_nee) {  // NEE vertices in Morton order of their shading points (no host round trip)
-                    SortNeeIO so{ns.queue, qc_cur + kQShadowLen, Sq[l], ns.key, b.sKeys.get(), b.sKeysAlt.get(),
-                                 b.sVals.get(), b.sValsAlt.get(), b.sTemp.get(), kn.sort_nee_bits};
-                    e0 = ev_start(c, s);
-                    HIPCHK(c, launch_sort_nee(s, so));
-                    ev_mark(c, s, ST_SORT, e0);
-                }
-                if (nee) {  // this bounce's shadow rays, before the next bounce reads L
-                    e0 = ev_start(c, s);
-                    HIPCHK(c, launch_path_nee(s, grid, c->dsc.qcap, dsl, d_spec, pio, nio, d_ctr));
-                    // (no fallback launch when k_path_nee resolves its undecided shadow rays itself, coop_ok)
-                    if (c->dsc.qcap != 1 && !c->dsc.coop_ok)
-                        HIPCHK(c, launch_path_nee_fallback(s, grid, c->dsc.qcap, dsl, d_spec, pio, nio, d_ctr));
-                    ev_mark(c, s, ST_SHADOW, e0);
-                }
-                // (the deferred shadow rays are resolved in k_path_shade itself when coop_ok: no launch, which in
-                // two-lane mode waits for the other lane's resident blocks, r05 kernel traces: 0.87 ms per bounce)
-                if (shq && !(sqio.defer && c->dsc.coop_ok)) {
-                    e0 = ev_start(c, s);
-                    HIPCHK(c, launch_path_shadow(s, grid, c->dsc.qcap, kn.shadow_dfs != 0, dsl, pio, sqio, d_ctr));
-                    ev_mark(c, s, ST_SHADOW, e0);
-                }
-                cur[l] = nxt;
+    const Work* last_film = nullptr;  // lane of the most recent film launch
+    for (int g0 = ib; g0 < ie; g0 += bp.B * lanes) {
+        Lane lane[kLanes];
+        int n = 0;  // lanes with a batch in this round
+        for (; n < lanes && g0 + n * bp.B < ie; ++n)
+            if ((rc = stage_generate(p, lane[n], n, g0 + n * bp.B, ie, st))) return rc;
+        for (int depth = 0; p.pp.at(depth).traced; ++depth)
+            for (int l = 0; l < n; ++l) {
+                Lane& L = lane[l];
+                Bounce bo{depth, p.pp.at(depth)};
+                if ((rc = stage_trace(p, L, bo)) || (rc = stage_shade(p, L, bo)) || (rc = stage_nee(p, L, bo)) ||
+                    (rc = stage_shadow(p, L, bo)))
+                    return rc;
+                L.cur ^= 1;
             }
-        }
-        for (int l = 0; l < lanes && nIdx[l] > 0; ++l) {
-            Work& w = c->ws[l];
-            const Batch& b = w.b;
-            hipStream_t s = lstream(l);
-            const RecView rv{b.rec.get(), rec_fs, rec_ss, rec_rng8};
-            if (last_film >= 0 && last_film != l) HIPCHK(c, hipStreamWaitEvent(s, c->ws[last_film].film_done, 0));
-            PathFilmIO fio{work, n_work, nIdx[l], rv, b.pdfA.get(), b.pdfB.get(), film};
-            fio.lean = lean;
-            fio.mom = pass.mom;
-            hipEvent_t e0 = ev_start(c, s);
-            HIPCHK(c, launch_path_film(s, 0, d_spec, fd, fio, d_ctr));
-            ev_mark(c, s, ST_FILM, e0);
-            HIPCHK(c, hipEventRecord(w.film_done, s));
-            last_film = l;
+        for (int l = 0; l < n; ++l) {
+            if ((rc = stage_film(p, lane[l], last_film))) return rc;
+            last_film = lane[l].w;
         }
     }
     // the caller's stream resumes after every lane's last film
     for (int l = 1; l < lanes; ++l) HIPCHK(c, hipStreamWaitEvent(st, c->ws[l].film_done, 0));
     return RT_OK;
+}
+
+int render_device_body(rt_ctx* c, int ib, int ie, float4* film, hipStream_t st, const PassTarget& pass) {
+    if (int rc = pass_checks(c, ib, ie)) return rc;
+    const PassFacts f = pass_facts(c, pass.n, ib, ie);
+    const BatchPlan bp = plan_batches(f, c->knobs);
+    if (!bp.nbatch) return RT_OK;
+    return bp.path ? render_path(c, f, bp, ib, ie, film, st, pass) : render_reference(c, bp, ib, ie, film, st, pass);
 }
 
 // ---------------------------------------------------------------------------------- PixelSensor (a18, a20)
@@ -2834,31 +2811,23 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
     if ((rc = chain_check_depth(c, chain_arg))) return rc;
     const int chain_depth = chain_arg & ~RT_CHAIN_CURVED;
     const bool curved = (chain_arg & RT_CHAIN_CURVED) != 0;  // (without effect at depth 0)
-    if (ib < 0 || ie < ib) return fail(c, RT_E_ARG, "invalid index range");
-    if ((rc = ensure_sobol(c))) return rc;
-    DevSampler smp = dev_sampler(c);
-    if (c->smp.kind == RT_SAMPLER_STRATIFIED && !c->smp.jitter && ie > smp.spp)
-        return fail(c, RT_E_ARG, "StratifiedSampler without jitter supports indices < SamplesPerPixel (samplers.h:83-87)");
+    if ((rc = pass_checks(c, ib, ie))) return rc;
     if ((rc = build_work(c))) return rc;
     const int n_work = c->n_work;
-    if (ie == ib || n_work == 0) return RT_OK;
-    const bool path = c->integ.kind == RT_INTEGRATOR_PATH || c->integ.kind == RT_INTEGRATOR_PATH_MIS;
-    c->dsc.mis = c->integ.kind == RT_INTEGRATOR_PATH_MIS;
-    c->dsc.full = c->scene_full || c->dsc.mis || c->tx.live;  // (textures are fetched by the general kernels alone)
-    const size_t target = c->knobs.batch_samples ? c->knobs.batch_samples : (size_t)(c->dsc.qcap == 1 ? 16 : 32) << 20;
-    int B = (int)std::max<size_t>(1, target / (size_t)n_work);
-    B = std::min(B, ie - ib);
-    const size_t nmax = (size_t)B * n_work;
-    const int nsh = c->dsc.qcap == 1 ? 1 : kShards;
-    const size_t ncap = (size_t)nsh * (size_t)shard_stride((int)nmax, nsh);
+    const BatchPlan bp = plan_batches(pass_facts(c, n_work, ib, ie), c->knobs);
+    if (!bp.nbatch) return RT_OK;
+    const bool path = bp.path, dyn = bp.dyn;  // dyn: the bounce rays' trace takes per-wave tickets
+    const int B = bp.B, nsh = bp.nsh;
+    const size_t ncap = bp.ncap;
+    const DevSampler smp = dev_sampler(c);
     const DevCamera cam = dev_camera(c->cam);
     const DevFilm fd = dev_film(c);
+    const DevScene sc = pass_scene(c, bp);
     Work& w = c->ws[0];
     if ((rc = ensure_workspace(c, w, ncap, false))) return rc;
     if (alb && (rc = ensure_albedo_table(c, st))) return rc;
     // (the reference integrator consults no material: every chain has length 0)
     const bool chain = path && chain_depth > 0;
-    const bool dyn = c->dsc.qcap != 1;  // the bounce rays' trace: per-wave tickets on multi-level octrees
     float eta_bk7 = 0.f;
     if (chain) {
         if (ncap > ((size_t)1 << kChainSlotBits)) return fail(c, RT_E_LIMIT, "chain pass: more than 2^28 samples per batch");
@@ -2878,21 +2847,21 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
         HIPCHK(c, launch_generate(st, c->grid, nS, ids, cam, smp, fd, r.go));
         ev_mark(c, st, ST_GEN, e0);
         e0 = ev_start(c, st);
-        HIPCHK(c, launch_trace_closest(st, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()));
+        HIPCHK(c, launch_trace_closest(st, 0, sc.qcap, lane_scene(sc, w), r.tio, c->d_ctr.get()));
         ev_mark(c, st, ST_TRACE, e0);
         if (alb) {
             const AlbedoFilmIO aio{c->d_work.get(), n_work, nIdx, w.b.hitB.get(), w.b.hitPrim.get(), c->alb.table.get(),
                                    c->tx.live ? c->tx.dev.get() : nullptr, path ? 0 : 1, alb};
-            HIPCHK(c, launch_albedo_film(st, c->dsc, aio));
+            HIPCHK(c, launch_albedo_film(st, sc, aio));
         }
         if (!chain) {
             const FeatureIO fio{c->d_work.get(), n_work, nIdx, w.b.rayD(), 1, w.b.hitB.get(), w.b.hitPrim.get(), feat,
                                 w.b.rayO(), pos};
-            HIPCHK(c, launch_feature_film(st, c->dsc, fio));
+            HIPCHK(c, launch_feature_film(st, sc, fio));
             continue;
         }
         const Batch& b = w.b;
-        const DevScene dsl = lane_scene(c, w);
+        const DevScene dsl = lane_scene(sc, w);
         int* const ctr = w.chain_ctr.get();
         HIPCHK(c, hipMemsetAsync(ctr, 0, (size_t)chain_depth * kQRegion * sizeof(int), st));
         ChainIO cio{};
@@ -2922,11 +2891,7 @@ int features_device(rt_ctx* c, int ib, int ie, float4* feat, hipStream_t st, flo
                     tio.fb_pos = w.tfb.get();
                     tio.fb_len = reg + kQTraceFallback;
                 }
-                e0 = ev_start(c, st);
-                HIPCHK(c, launch_trace_closest(st, c->grid, c->dsc.qcap, dsl, tio, c->d_ctr.get()));
-                if (tio.fb_pos && !c->dsc.coop_ok)
-                    HIPCHK(c, launch_trace_fallback(st, c->grid, c->dsc.qcap, dsl, tio, c->d_ctr.get()));
-                ev_mark(c, st, ST_TRACE, e0);
+                if ((rc = trace_with_fallback(c, st, dsl, tio, bp.trace_fallback))) return rc;
             }
             HIPCHK(c, launch_chain_level(st, c->grid, dsl, cio));
         }
@@ -3605,7 +3570,7 @@ static int impl_rt_debug_trace(rt_ctx* c, int n, const float* ro, const float* r
             io.fb_pos = dF.get();
             io.fb_len = dT.get() + kQStride;
         }
-        const DevScene ls = lane_scene(c, c->ws[0]);
+        const DevScene ls = lane_scene(c->dsc, c->ws[0]);
         if ((path_kernel && hipMemsetAsync(dT.get(), 0, 2 * kQStride * sizeof(int), c->stream) != hipSuccess) ||
             upload_rays(n, ro, rd, nullptr, dO.get(), dD.get()) != hipSuccess ||
             launch_trace_closest(c->stream, 0, c->dsc.qcap, ls, io, c->d_ctr.get()) != hipSuccess ||
@@ -3635,7 +3600,7 @@ static int impl_rt_debug_occluded(rt_ctx* c, int n, const float* ro, const float
         DevBuf<int> dP;
         if (dO.reserve(n) || dD.reserve(n) || dP.reserve(n)) return fail(c, RT_E_OOM, "debug occlusion buffers");
         if (upload_rays(n, ro, rd, tmax, dO.get(), dD.get()) != hipSuccess ||
-            launch_occluded(c->stream, c->dsc.qcap, lane_scene(c, c->ws[0]), n, dO.get(), dD.get(), dP.get(),
+            launch_occluded(c->stream, c->dsc.qcap, lane_scene(c->dsc, c->ws[0]), n, dO.get(), dD.get(), dP.get(),
                             c->d_ctr.get(), c->knobs.debug_path && c->dsc.coop_ok) != hipSuccess ||
             hipStreamSynchronize(c->stream) != hipSuccess ||
             hipMemcpy(occluded, dP.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
@@ -3726,7 +3691,7 @@ static int impl_rt_debug_samples(rt_ctx* c, int n, const int32_t* pixel_ids, con
         RecordIO rio{n, r.go.rayO, r.go.rayD, r.go.lamA, r.go.lamB, r.go.pdfA, r.go.pdfB, r.tio.hitB, r.tio.hitPrim,
                      dout.get(), 39, 1};
         if (launch_generate(c->stream, 0, n, ids, dev_camera(c->cam), smp, fd, r.go) != hipSuccess ||
-            launch_trace_closest(c->stream, 0, c->dsc.qcap, lane_scene(c, w), r.tio, c->d_ctr.get()) != hipSuccess ||
+            launch_trace_closest(c->stream, 0, c->dsc.qcap, lane_scene(c->dsc, w), r.tio, c->d_ctr.get()) != hipSuccess ||
             launch_records(c->stream, c->dsc, c->d_spec.get(), fd, r.sio, rio) != hipSuccess ||
             hipStreamSynchronize(c->stream) != hipSuccess ||
             hipMemcpy(out, dout.get(), sizeof(rt_sample_record) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
