@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_cull.h"
 #include "rt_internal.h"
 #include "rt_mathf.h"
 #include "rt_texture.h"
@@ -49,11 +50,7 @@ RT_DEV float f_cosh(float x) {
     return f;
 }
 
-// helpers.h:50-54
-RT_DEV float gamma_n(int n) {
-    const float me = 0x1p-24f;  // numeric_limits<float>::epsilon() * 0.5
-    return ((float)n * me) / (1.0f - (float)n * me);
-}
+// (gamma_n, helpers.h:50-54: rt_cull.h)
 // glm scalar min/max/clamp
 RT_DEV float gmax(float x, float y) { return (x < y) ? y : x; }
 RT_DEV float gmin(float x, float y) { return (y < x) ? y : x; }
@@ -74,7 +71,7 @@ RT_DEV float max3f(float a, float b, float c) {
 }
 RT_DEV float lerpf_(float x, float a, float b) { return (1 - x) * a + x * b; }  // helpers.h:154-157
 
-struct V3 { float x, y, z; };
+// (struct V3: rt_cull.h)
 RT_DEV V3 v3(float x, float y, float z) { return {x, y, z}; }
 RT_DEV V3 vadd(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
 RT_DEV V3 vsub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
@@ -585,21 +582,7 @@ RT_DEV bool box_hit(float4 a, float4 b, V3 o, V3 inv, float tMax) {
     return !(mn > mx);
 }
 
-// Conservative box test for the single-leaf culling clusters only — never an octree node, whose test keeps
-// Bounds3::IntersectP's exact operations above.  Same slab distances and tFar factor as box_hit, reduced with
-// v_min/v_max (IEEE minNum/maxNum) instead of compare-and-select chains.  The one behavioural difference: a plane
-// distance that is NaN (d_axis == 0 with the origin exactly on that plane) makes the other plane of the axis decide
-// the slab; such a ray lies in the box's face plane, at least the cluster pad away from every triangle of the
-// cluster (rt_host.cpp upload), so no candidate test of the cluster can pass and skipping it is exact.
-RT_DEV bool cluster_hit(float4 a, float4 b, V3 o, V3 inv, float tMax) {
-    const float g = 1 + 2 * gamma_n(3);
-    const float x0 = (a.x - o.x) * inv.x, x1 = (b.x - o.x) * inv.x;
-    const float y0 = (a.y - o.y) * inv.y, y1 = (b.y - o.y) * inv.y;
-    const float z0 = (a.z - o.z) * inv.z, z1 = (b.z - o.z) * inv.z;
-    const float mn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), 0.f));
-    const float mx = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1)) * g;
-    return mn <= fminf(mx, tMax);
-}
+// (cluster_hit, cluster_hit_fma: the conservative test of the single-leaf culling clusters, rt_cull.h)
 
 // Sampling.h:809-840 Continuous_Inversion_Sampler::Sample: binary search of U in the CDF table, then linear
 // interpolation inside the bin (table built on the host, rt_host.cpp inversion_table).

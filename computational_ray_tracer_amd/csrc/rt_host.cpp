@@ -24,6 +24,7 @@
 #include "../../include/rtmi355x.h"
 #include "../data/spectra_data.h"
 #include "../data/sensor_data.h"
+#include "rt_cull.h"
 #include "rt_devbuf.h"
 #include "rt_guard.h"
 #include "rt_internal.h"
@@ -37,6 +38,7 @@ namespace {
 constexpr int kRingMax = 1 << 16;  // largest BFS group FIFO (HBM ring per resident thread, 4 B per entry)
 constexpr int kMaxLights = 64;
 constexpr float kClusterPadRel = 1e-5f;  // cluster-box inflation per unit of scene extent (see scene upload)
+constexpr float kClusterPadCentre = 0x1p-22f;  // ... and per unit of the scene centre's largest |coordinate| (RT_CULL_FMA)
 
 // ------------------------------------------------------------------------------ host float math
 // glm operation order, float, -ffp-contract=off (same contract as the device code)
@@ -2223,7 +2225,10 @@ static void shading_arrays(const rt_scene_desc* s, const SceneWorld& sw, Shading
 // inflation only has to cover those checks' rounding.  In the sheared frame every vertex coordinate carries
 // at most ~4 ulp(M) of error, M = the largest |vertex - origin|; with origins inside 8 extents of the scene
 // centre (cl_guard; farther rays never skip) M <= 9.8 ext, i.e. <= 2.4e-6 ext, and the pad is 1e-5 ext +
-// 1e-3 — small enough that a wave of rays leaving one wall (origin offset 1e-4 (1 + max|p|)) skips it.
+// 1e-3 — small enough that a wave of rays leaving one wall (origin offset 1e-4 (1 + max|p|)) skips it.  The box
+// test's own rounding comes on top (rt_cull.h, where the bound is derived): with the inverse direction's rounding its
+// FMA form moves a plane by up to 1.5e-6 ext + 3 * 2^-24 |c|, c = the scene's centre; the first part fits the pad
+// above (3.9e-6 ext in all), the second is what kClusterPadCentre |c| adds to it.
 struct LeafClusters {
     std::vector<float4> box[2];     // per tile set: (min, max) per cluster; empty for multi-level octrees
     unsigned long long fan_pairs[2] = {0, 0};
@@ -2233,6 +2238,11 @@ static void leaf_clusters(const OctBuild::Node& R, const FlatOctree& f, LeafClus
     float ext = std::max(std::max(R.mx.x - R.mn.x, R.mx.y - R.mn.y), R.mx.z - R.mn.z);
     float pad = kClusterPadRel * ext + 1e-3f;
     cl.guard = make_float4(.5f * (R.mn.x + R.mx.x), .5f * (R.mn.y + R.mx.y), .5f * (R.mn.z + R.mx.z), 64.f * ext * ext);
+#if RT_CULL_FMA
+    // the cull's FMA form rounds o / d, not plane - o: 3 * 2^-24 |c| of its error grows with the scene's distance |c|
+    // from the coordinate origin, not with its extent (rt_cull.h); that part is added to the pad (Cornell: +1 %)
+    pad += kClusterPadCentre * std::max(std::max(std::fabs(cl.guard.x), std::fabs(cl.guard.y)), std::fabs(cl.guard.z));
+#endif
     for (int st = 0; st < 2; ++st) {
         const std::vector<float4>& tl = f.tiles[st];
         int nt_leaf = (int)tl.size() / 3;

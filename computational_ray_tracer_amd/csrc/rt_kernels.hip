@@ -400,6 +400,11 @@ __device__ __forceinline__ int queue_append(int* counter, bool pred, int* lds) {
 
 
 typedef unsigned long long ctr_t;
+// A thread's counters in the packed single-leaf kernels (PK): such a launch has at most 2^24 items (the record's slot
+// field) of at most 64 triangle tests each (the LDS triangle table), so 32 bits hold any thread's counts — and half the
+// registers across the traversal.  count_add sums them in 64 bits as ever.
+template <bool PK>
+using thread_ctr_t = std::conditional_t<PK, uint32_t, ctr_t>;
 __device__ __forceinline__ void count_add(unsigned long long* ctr, int slot, unsigned long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -743,6 +748,9 @@ __device__ __forceinline__ bool occluded_dfs(const DevScene& sc, int set, V3 o, 
 // per group instead of once per cluster (scalar loads return out of order: every use waits for all of them).
 __device__ __forceinline__ uint32_t cluster_mask(const float4* cl, int ncl, bool far, V3 o, V3 inv, float tmax) {
     uint32_t hm = 0;
+#if RT_CULL_FMA
+    const V3 oi = cluster_oi(o, inv);  // formed here, from values live across the cull anyway (rt_cull.h)
+#endif
     for (int c0 = 0; c0 < ncl; c0 += 3) {
         float4 A[3], B[3];
 #pragma unroll
@@ -753,7 +761,11 @@ __device__ __forceinline__ uint32_t cluster_mask(const float4* cl, int ncl, bool
         }
 #pragma unroll
         for (int u = 0; u < 3; ++u)
+#if RT_CULL_FMA
+            if (c0 + u < ncl && (far || cluster_hit_fma(A[u], B[u], oi, inv, tmax))) hm |= 1u << (c0 + u);
+#else
             if (c0 + u < ncl && (far || cluster_hit(A[u], B[u], o, inv, tmax))) hm |= 1u << (c0 + u);
+#endif
     }
     return hm;
 }
@@ -791,9 +803,10 @@ __device__ __forceinline__ unsigned cluster_candidates(const TriRay& R, const fl
 // The whole octree is one leaf (e.g. the 36-triangle Cornell box: 36 < TRIANGLE_CAPACITY): every
 // lane walks the same triangle list, so it is read through the scalar cache into SGPRs once per
 // wave; four triangles (12 x s_load_dwordx4) are fetched per scalar-cache round trip.
-template <bool ANYHIT, int KZ>
+// (C: the caller's counter type, ctr_t or — the packed kernels, thread_ctr_t — 32 bits)
+template <bool ANYHIT, int KZ, class C = ctr_t>
 __device__ __forceinline__ int leaf1_walk(const DevScene& sc, int set, V3 o, V3 d, float tMaxInit, float& rb0,
-                                          float& rb1, float& rb2, float& rt, ctr_t& nn, ctr_t& nt) {
+                                          float& rb1, float& rb2, float& rt, C& nn, C& nt) {
     V3 inv = v3(1 / d.x, 1 / d.y, 1 / d.z);
     TriRay R = make_triray<KZ>(o, d);
     float tMax = tMaxInit;
@@ -1167,9 +1180,9 @@ __device__ __forceinline__ int bfs_walk(const DevScene& sc, int set, V3 o, V3 d,
     return best;
 }
 // the name the callers use: the single-leaf walk or the multi-level group-FIFO BFS
-template <int QCAP, bool ANYHIT, int KZ, bool DFS = false>
+template <int QCAP, bool ANYHIT, int KZ, bool DFS = false, class C = ctr_t>
 __device__ __forceinline__ int traverse(const DevScene& sc, int set, V3 o, V3 d, float tMaxInit, float& rb0, float& rb1,
-                                        float& rb2, float& rt, ctr_t& nn, ctr_t& nt) {
+                                        float& rb2, float& rt, C& nn, C& nt) {
     if constexpr (QCAP == 1) return leaf1_walk<ANYHIT, KZ>(sc, set, o, d, tMaxInit, rb0, rb1, rb2, rt, nn, nt);
     else return bfs_walk<QCAP, ANYHIT, KZ, DFS>(sc, set, o, d, tMaxInit, rb0, rb1, rb2, rt, nn, nt);
 }
@@ -1601,9 +1614,9 @@ __device__ __forceinline__ int bvh_anyhit(const DevScene& sc, int set, V3 o, V3 
     return -1;
 }
 
-template <int QCAP, bool ANYHIT, int KZ, bool DFS>
+template <int QCAP, bool ANYHIT, int KZ, bool DFS, class C = ctr_t>
 __device__ __forceinline__ int traverse_kz(const DevScene& sc, int set, V3 o, V3 d, float tMax, float& b0, float& b1,
-                                           float& b2, float& t, ctr_t& nn, ctr_t& nt, ctr_t& nfb) {
+                                           float& b2, float& t, C& nn, C& nt, C& nfb) {
     if constexpr (QCAP != 1) {
         bool amb = false;
         const int r = ANYHIT ? bvh_anyhit<KZ>(sc, set, o, d, tMax, nn, nt, amb)
@@ -1616,9 +1629,9 @@ __device__ __forceinline__ int traverse_kz(const DevScene& sc, int set, V3 o, V3
 
 // When every active lane of the wave has the same dominant ray axis (camera rays) the watertight test's coordinate
 // permutation is resolved at compile time; otherwise per lane.
-template <int QCAP, bool ANYHIT, bool DFS = false>
+template <int QCAP, bool ANYHIT, bool DFS = false, class C = ctr_t>
 __device__ __forceinline__ int traverse_any(const DevScene& sc, int set, V3 o, V3 d, float tMax, float& b0, float& b1,
-                                            float& b2, float& t, ctr_t& nn, ctr_t& nt, ctr_t& nfb) {
+                                            float& b2, float& t, C& nn, C& nt, C& nfb) {
     int kz = dominant_axis(d);
     uint64_t act = __ballot(true);
     if (__ballot(kz == 2) == act) return traverse_kz<QCAP, ANYHIT, 2, DFS>(sc, set, o, d, tMax, b0, b1, b2, t, nn, nt, nfb);
@@ -1649,10 +1662,13 @@ __device__ __forceinline__ int traverse_bvh(const DevScene& sc, int set, V3 o, V
 
 // Register budgets (amdgpu_waves_per_eu) of the multi-level instantiations: 4 waves/SIMD (128 VGPRs) on the trace,
 // path shade and mixed-scene shade kernels (CFG3 121 -> 144, CFG4 87 -> 111 Msamples/s; 5 waves spill too much).
-// The single-leaf instantiations (107 / 123 VGPRs) are unbudgeted (5 waves: trace -2 %, shade -7 %).
+// The single-leaf instantiations are unbudgeted (a forced 5-wave budget spilled: trace -2 %, shade -7 %); the four
+// packed ones fit 96 VGPRs, 5 waves, by themselves (89-95: 32-bit thread counters, thread_ctr_t; depth 0's constant
+// lean start, k_path_shade kLean0; tests/test_cluster_cull.py holds the line).
 // These budgets (RT_*_WAVES), the any-hit stack depth (RT_ANY_STACK), the radix digit widths (rt_sort.hip) and the
 // staged BVH levels (rt_internal.h) are numeric tuning constants a variant build may override (Makefile
-// `variants`); RT_SIMD_STATS selects the SIMD-efficiency measurement build.  No code path is switched by a macro.
+// `variants`); RT_SIMD_STATS selects the SIMD-efficiency measurement build and RT_CULL_FMA (rt_cull.h) the cluster
+// cull's box test.  No other code path is switched by a macro.
 #ifndef RT_MULTI_WAVES
 #define RT_MULTI_WAVES 4
 #endif
@@ -1715,7 +1731,7 @@ __global__ void __launch_bounds__(kBlock) RT_WAVES_ATTR(QCAP) k_trace_closest(De
     if constexpr (PK) stage_ng1(sc);
     if (io.zero && blockIdx.x == 0)
         for (int i = threadIdx.x; i < kQRegion; i += blockDim.x) io.zero[i] = 0;
-    ctr_t nn = 0, nt = 0, nh = 0, nr = 0, nfb = 0, novf = 0;
+    thread_ctr_t<PK> nn = 0, nt = 0, nh = 0, nr = 0, nfb = 0, novf = 0;
     // one ray at queue position p: octree (BVH / BFS), then the analytic shapes
     auto trace_one = [&](int p, float4 o4, float4 d4) __attribute__((always_inline)) {
         float b0 = 0, b1 = 0, b2 = 0, t = 0;
@@ -2239,9 +2255,12 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
     // atomic and one round of barriers per chunk: Cornell +3.5 %, r03)
     __shared__ float4 pend[QCAP == 1 ? 2 * kBlock : 1];
     bool pend0 = false;
-    ctr_t snn = 0, snt = 0, nsh = 0, sfb = 0, novf = 0;
+    thread_ctr_t<PK> snn = 0, snt = 0, nsh = 0, sfb = 0, novf = 0;
     // lean depth 0: k_generate stored no β = 1 / L = 0, so they start in registers and every path's L is written
-    const bool d0 = io.lean && io.depth == 0;
+    // (PK without HQ is launched for exactly that, launch_path_shade: as a constant, β = 1 and L = 0 need no
+    // registers and the depth-0 kernel fits 96 VGPRs; 1 * x and the zero it adds to are what the loads gave)
+    constexpr bool kLean0 = PK && !HQ;
+    const bool d0 = kLean0 || (io.lean && io.depth == 0);
     // multi-level octrees: per-wave tickets and appends (per-ray cost varies by 100x); single leaf: per block
     constexpr bool WAVE = QCAP != 1;
     // single leaf: the host gives the queues one shard (rt_host.cpp nsh)
@@ -3295,8 +3314,10 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
                              bool hit_pack) {
     const int gb = ring_clamp(grid > 0 ? grid : 1, qcap, sc);
     // packed hit records: the single-leaf simple path, a scene the LDS triangle table holds; depth 0 reads the dense
-    // camera queue's hit words, the bounce depths the hit queue's records
-    if (hit_pack && (qcap != 1 || sc.full || io.ticket || sc.n_tris > kHitPackTris || (io.depth == 0 && io.q.len)))
+    // camera queue's hit words (in a lean pass: its kernel starts β = 1, L = 0 in registers unconditionally), the
+    // bounce depths the hit queue's records
+    if (hit_pack && (qcap != 1 || sc.full || io.ticket || sc.n_tris > kHitPackTris ||
+                     (io.depth == 0 && (io.q.len || !io.lean))))
         return hipErrorInvalidValue;
     if (sc.full && sc.n_lights > 0 && !nee.rec) return hipErrorInvalidValue;  // NEE records are required
     if (!sc.full && qcap != 1 && !shq.shO) return hipErrorInvalidValue;       // so is the shadow queue
