@@ -16,7 +16,7 @@ STATUS_NAMES = {0: "RT_OK", -1: "RT_E_ARG", -2: "RT_E_HIP", -3: "RT_E_RCCL", -4:
                 -6: "RT_E_NODEVICE", -7: "RT_E_LIMIT"}
 RT_MAT_DIFFUSE, RT_MAT_MIRROR, RT_MAT_DIELECTRIC = 0, 1, 2
 RT_SHAPE_SPHERE, RT_SHAPE_DISK, RT_SHAPE_TRIANGLE = 0, 1, 2
-RT_LIGHT_QUAD, RT_LIGHT_DISK, RT_LIGHT_POINT, RT_LIGHT_DISTANT, RT_LIGHT_MESH = 0, 1, 2, 3, 4
+RT_LIGHT_QUAD, RT_LIGHT_DISK, RT_LIGHT_POINT, RT_LIGHT_DISTANT, RT_LIGHT_MESH, RT_LIGHT_ENV = 0, 1, 2, 3, 4, 5
 RT_CAMERA_PERSPECTIVE, RT_CAMERA_ORTHOGRAPHIC, RT_CAMERA_PINHOLE, RT_CAMERA_THINLENS = 0, 1, 2, 3
 RT_SAMPLER_INDEPENDENT, RT_SAMPLER_STRATIFIED, RT_SAMPLER_SOBOL = 0, 1, 2
 RT_SOBOL_NONE, RT_SOBOL_PERMUTE_DIGITS, RT_SOBOL_FAST_OWEN, RT_SOBOL_OWEN = 0, 1, 2, 3
@@ -167,6 +167,11 @@ class rt_texture_desc(C.Structure):
                 ("reserved", C.c_int * 4)]
 
 
+class rt_environment_desc(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("rgb", C.POINTER(C.c_float)), ("scale", C.c_float),
+                ("world_to_env", F9), ("reserved", C.c_int * 4)]
+
+
 class rt_albedo(C.Structure):
     """Albedo film entry: sums over the first hits of a feature pass."""
     _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("hits", C.c_float)]
@@ -196,6 +201,8 @@ EXPORTS = [
     "rt_scene_set_textures", "rt_texel_index", "rt_debug_texture_bake", "rt_debug_texture_eval",
     "rt_render_features_albedo", "rt_denoise_albedo", "rt_adaptive_denoise_albedo", "rt_debug_albedo_bake",
     "rt_debug_meshlight_table", "rt_debug_light_sample",
+    "rt_scene_set_environment", "rt_env_texel", "rt_debug_env_table", "rt_debug_env_sample", "rt_debug_env_eval",
+    "rt_debug_env_stats",
 ]
 
 _lib = None
@@ -306,6 +313,13 @@ def load_library(path=None):
         "rt_debug_meshlight_table": ([C.c_void_p, C.c_int, P(C.c_int), P(C.c_int32), P(C.c_float), P(C.c_float)], C.c_int),
         "rt_debug_light_sample": ([C.c_void_p, C.c_int, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                    P(C.c_float), P(C.c_float), P(C.c_int32)], C.c_int),
+        "rt_scene_set_environment": ([C.c_void_p, P(rt_environment_desc)], C.c_int),
+        "rt_env_texel": ([C.c_int, C.c_int, P(C.c_float), P(C.c_float), P(C.c_int), P(C.c_int), P(C.c_float)], C.c_int),
+        "rt_debug_env_table": ([C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_float), P(C.c_float), P(C.c_float),
+                                P(C.c_float)], C.c_int),
+        "rt_debug_env_sample": ([C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32)], C.c_int),
+        "rt_debug_env_eval": ([C.c_void_p, C.c_int, P(C.c_float), P(C.c_int32), P(C.c_float)], C.c_int),
+        "rt_debug_env_stats": ([C.c_void_p, P(C.c_double), P(C.c_int64)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

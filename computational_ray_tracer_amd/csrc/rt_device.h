@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "rt_cull.h"
+#include "rt_envmap.h"
 #include "rt_internal.h"
 #include "rt_mathf.h"
 #include "rt_texture.h"
@@ -728,10 +729,11 @@ RT_DEV float fr_dielectric(float cosi, float eta) {
 // disk: the concentric mapping of the Disk shape) and point lights aim at the point, tMax = 0.999 dist; a distant
 // light's direction is fixed (tMax = FLT_MAX; u0, u1 are drawn and unused).  k_path_shade_full evaluates it for the
 // light weights and k_path_nee again for the ray: the same code on the same inputs, so the same bits.
-// ML (the mesh-light instantiations): an RT_LIGHT_MESH picks the triangle i with the smallest
-// cdf_i > u0 (binary search of the light's table), remaps u0 to the triangle's cdf step, and takes a uniform point of
-// the triangle (pbrt-v4 SampleUniformTriangle); ms returns the triangle's geometric normal and its id.  Without ML
-// the function holds none of it and ms is left alone.
+// TL (the tabled-light instantiations): 0 none; >= 1 mesh lights: an RT_LIGHT_MESH picks the triangle i
+// with the smallest cdf_i > u0 (cdf_search over the light's table), remaps u0 to the triangle's cdf step, and takes a
+// uniform point of the triangle (pbrt-v4 SampleUniformTriangle); ms returns the triangle's geometric normal and its id.
+// 2: the environment light as well (§3j): env_sample's direction, tMax and dist2 as the distant light's; ms returns the
+// texel (tri) and pdf_omega (pdf).  An instantiation holds none of what its TL excludes and leaves ms alone.
 struct LightRay {
     V3 wi;
     float tmax, dist2;
@@ -739,14 +741,88 @@ struct LightRay {
 struct MeshSample {
     V3 nl;
     int tri;
+    float pdf;
 };
-template <bool ML = false>
+// §3i's search: the smallest i with u < cdf_i (lo = 0, hi = n - 1; a u of exactly 1 stays inside the table), u remapped
+// to that entry's step (up, clamped below 1) and the step itself.  The cdfs are not monotone by construction (ulp dips
+// behind slivers, §3i): the search still ends on an entry both of whose neighbours were compared or are the table's ends.
+RT_DEV int cdf_search(const float* cdf, int n, float u, float& up, float& step) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (u < cdf[mid]) hi = mid;
+        else lo = mid + 1;
+    }
+    const float c0 = lo > 0 ? cdf[lo - 1] : 0.f, c1 = cdf[lo];
+    step = c1 - c0;
+    up = fminf((u - c0) / step, 0x1.fffffep-1f);
+    return lo;
+}
+
+// ---- the environment light ----
+// glm transpose(M) v for the 3x3 column-major M: row r of the result = (M[3r] x + M[3r + 1] y) + M[3r + 2] z
+RT_DEV V3 m3t_mul(const float* M, V3 v) {
+    return v3((M[0] * v.x + M[1] * v.y) + M[2] * v.z, (M[3] * v.x + M[4] * v.y) + M[5] * v.z,
+              (M[6] * v.x + M[7] * v.y) + M[8] * v.z);
+}
+struct EnvSample {
+    V3 wi;
+    float pdf;  // pdf_omega; 0 or NaN: the sample is rejected (a texel of zero weight)
+    int texel;  // y W + x
+};
+// the table's pdf_st of texel (x, y): the product of its conditional and marginal cdf steps times W H
+RT_DEV float env_pdf_st(const EnvTab& T, float sx, float sm) { return (sx * sm) * (float)(T.W * T.H); }
+// One Get2D: u1 picks the row in the marginal, u0 the column in that row's conditional, (s, t) = the remapped point of
+// the texel, d = M^T vnorm(p).  k_path_shade_full and k_path_nee both call it: the same bits.
+RT_DEV EnvSample env_sample(const DevLight& Lt, float u0, float u1) {
+    const EnvTab T = env_tab(Lt);
+    float u0p, u1p, sx, sm;
+    const int y = cdf_search(T.marg, T.H, u1, u1p, sm);
+    const int x = cdf_search(T.cond + (size_t)y * T.W, T.W, u0, u0p, sx);
+    const float s = ((float)x + u0p) / (float)T.W, t = ((float)y + u1p) / (float)T.H;
+    float p[3];
+    env_st_to_point(s, t, p);
+    const V3 pv = v3(p[0], p[1], p[2]);
+    EnvSample r;
+    r.wi = m3t_mul(Lt.o2r, vnorm(pv));
+    r.pdf = env_pdf_omega(env_pdf_st(T, sx, sm), vdot(pv, pv));
+    r.texel = y * T.W + x;
+    return r;
+}
+// the same pdf_omega for a given direction (a miss after a BSDF bounce), from the direction -> texel lookup and the same
+// table differences
+RT_DEV float env_eval(const DevLight& Lt, V3 d, int& texel) {
+    const EnvTab T = env_tab(Lt);
+    const float dv[3] = {d.x, d.y, d.z};
+    int x, y;
+    float l2;
+    env_dir_to_texel(T.W, T.H, Lt.o2r, dv, x, y, l2);
+    const float* row = T.cond + (size_t)y * T.W;
+    const float sx = row[x] - (x > 0 ? row[x - 1] : 0.f), sm = T.marg[y] - (y > 0 ? T.marg[y - 1] : 0.f);
+    texel = y * T.W + x;
+    return env_pdf_omega(env_pdf_st(T, sx, sm), l2);
+}
+// Le(lambda) of a baked texel c = (c0, c1, c2, m): (scale m) sigmoid(lambda) D65(lambda) (pbrt-v4 RGBIlluminantSpectrum)
+RT_DEV float env_le(float scale, float4 c, float lambda, float d65) {
+    return ((scale * c.w) * sigmoid_eval(c.x, c.y, c.z, lambda)) * d65;
+}
+
+template <int TL = 0>
 RT_DEV LightRay light_ray(const DevLight& Lt, V3 po, float u0, float u1, const float4* triWorld, MeshSample& ms) {
     LightRay r;
     if (Lt.type == 3) {
         r.wi = v3(Lt.dir[0], Lt.dir[1], Lt.dir[2]);
         r.tmax = 3.402823466e+38f;
         r.dist2 = 1.0f;
+        return r;
+    }
+    if (TL == 2 && Lt.type == kLightEnv) {
+        const EnvSample es = env_sample(Lt, u0, u1);
+        r.wi = es.wi;
+        r.tmax = 3.402823466e+38f;
+        r.dist2 = 1.0f;
+        ms.tri = es.texel;
+        ms.pdf = es.pdf;
         return r;
     }
     V3 pl;
@@ -757,16 +833,10 @@ RT_DEV LightRay light_ray(const DevLight& Lt, V3 po, float u0, float u1, const f
         float dx, dy;
         disk_concentric(u0, u1, dx, dy);
         pl = m4_point(Lt.o2r, v3(Lt.ro * dx, Lt.ro * dy, Lt.h));
-    } else if (ML && Lt.type == 4) {
+    } else if (TL >= 1 && Lt.type == 4) {
         const MeshLightTab T = meshlight_tab(Lt);
-        int lo = 0, hi = T.n - 1;  // (u0 < 1 = cdf[n - 1]; a u0 of exactly 1 stays inside the table as well)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (u0 < T.cdf[mid]) hi = mid;
-            else lo = mid + 1;
-        }
-        const float c0 = lo > 0 ? T.cdf[lo - 1] : 0.f, c1 = T.cdf[lo];
-        const float up = fminf((u0 - c0) / (c1 - c0), 0x1.fffffep-1f);
+        float up, step;
+        const int lo = cdf_search(T.cdf, T.n, u0, up, step);
         const int t = T.tri[lo];
         const float4 P0 = triWorld[3 * t], P1 = triWorld[3 * t + 1], P2 = triWorld[3 * t + 2];
         const V3 p0 = v3(P0.x, P0.y, P0.z), p1 = v3(P1.x, P1.y, P1.z), p2 = v3(P2.x, P2.y, P2.z);

@@ -29,6 +29,7 @@
 #include "rt_guard.h"
 #include "rt_internal.h"
 #include "rt_pass_plan.h"
+#include "rt_envmap.h"
 #include "rt_texture.h"
 
 using namespace rtmi;
@@ -545,6 +546,21 @@ struct rt_ctx {
         const int* tri = nullptr;
         const float* cdf = nullptr;
     } ml;
+    // the environment light bound to the uploaded scene (rt_scene_set_environment): its baked texels and
+    // cdf tables, and the scene's light list with the environment's DevLight appended (dsc.lights points to it while
+    // live; base_lights / h_lights are the upload's list, which clearing restores).  live = the path kernels run their
+    // TL = 2 instantiations and every traced depth ends with k_env_miss.
+    struct Environment {
+        bool live = false;
+        int W = 0, H = 0;
+        float total = 0.f;
+        DevBuf<float4> coef;
+        DevBuf<float> cond, marg;
+        DevBuf<DevLight> lights;
+        DevLight dev{};
+    } env;
+    std::vector<DevLight> h_lights;         // the uploaded scene's DevLights (mesh lights completed)
+    const DevLight* base_lights = nullptr;  // ... on the device (in scene_allocs)
     // albedo textures of the uploaded scene (rt_scene_set_textures): live = the path kernels run their TEX
     // instantiations on dev (the DevTex in device memory that points to the other arrays).  table: the RGB -> sigmoid
     // coefficient table (kRgbRes z-nodes, then kRgbTableFloats coefficients), uploaded once per context on first use.
@@ -593,6 +609,7 @@ struct rt_ctx {
     int grid = 0;              // persistent grid size (blocks)
     // stats
     rt_stats stats{};
+    double ms_env_miss = 0;    // the environment's miss stage alone (also in stats.ms_shade); zeroed with the stats
     struct Ev { hipEvent_t a, b; int stage; };
     std::vector<Ev> pending;
     std::vector<hipEvent_t> pool;
@@ -688,8 +705,20 @@ void free_textures(rt_ctx* c) {
     c->alb.valid = false;
 }
 
+// (the scene's own light list again)
+void free_environment(rt_ctx* c) {
+    if (c->env.live) {
+        c->dsc.lights = c->base_lights;
+        c->dsc.n_lights = (int)c->h_lights.size();
+    }
+    c->env = rt_ctx::Environment{};
+}
+
 void free_scene(rt_ctx* c) {
     free_textures(c);
+    free_environment(c);
+    c->h_lights.clear();
+    c->base_lights = nullptr;
     c->tx.mat_flags.clear();
     c->scene_allocs.clear();
     c->dsc = DevScene{};
@@ -819,7 +848,7 @@ hipEvent_t ev_start(rt_ctx* c, hipStream_t st) {
     hipEventRecord(a, st);
     return a;
 }
-enum { ST_GEN = 0, ST_TRACE, ST_SHADE, ST_SHADOW, ST_FILM, ST_SORT, ST_FILTER };
+enum { ST_GEN = 0, ST_TRACE, ST_SHADE, ST_SHADOW, ST_FILM, ST_SORT, ST_FILTER, ST_ENVMISS };
 
 void harvest(rt_ctx* c) {
     for (auto& e : c->pending) {
@@ -833,6 +862,8 @@ void harvest(rt_ctx* c) {
             case ST_SHADOW: c->stats.ms_shadow += ms; break;
             case ST_SORT: c->stats.ms_sort += ms; break;
             case ST_FILTER: c->stats.ms_trace += ms; break;  // (the last depth's emitter filter: no trace launch)
+            // the environment's miss stage: part of the shading time, and on its own for rt_debug_env_stats
+            case ST_ENVMISS: c->stats.ms_shade += ms; c->ms_env_miss += ms; break;
             default: c->stats.ms_film += ms; break;
         }
         c->pool.push_back(e.a);
@@ -1159,6 +1190,7 @@ PassFacts pass_facts(const rt_ctx* c, int n_work, int ib, int ie) {
     f.qcap = c->dsc.qcap; f.n_tris = c->dsc.n_tris; f.n_lights = c->dsc.n_lights;
     f.n_emit_tris = c->dsc.n_emit_tris; f.coop_ok = c->dsc.coop_ok;
     f.scene_full = c->scene_full; f.textures = c->tx.live; f.mesh_light = c->ml.any;
+    f.environment = c->env.live;
     f.integ = c->integ.kind == RT_INTEGRATOR_PATH_MIS ? kIntegPathMis
               : c->integ.kind == RT_INTEGRATOR_PATH   ? kIntegPath : kIntegReference;
     f.max_depth = c->integ.max_depth;
@@ -1430,6 +1462,19 @@ int stage_shade(const PathPass& p, const Lane& L, Bounce& bo) {
     return RT_OK;
 }
 
+// the environment light's misses of this depth: over the queue the shade just read.  A missed slot gets
+// no other addition at this depth (the shade and the NEE kernels touch hits only), so the order of its sums is fixed.
+// Timed with the shade stage (rt_stats has no field of its own for it).
+int stage_env_miss(const PathPass& p, const Lane& L, const Bounce& bo) {
+    rt_ctx* c = p.c;
+    if (!bo.d.env_miss) return RT_OK;
+    const EnvMissIO eio{bo.qv, bo.cO, L.w->b.hitPrim.get(), L.rv, bo.depth, p.pp.lean, p.bp.mis ? 1 : 0, c->env.dev};
+    hipEvent_t e0 = ev_start(c, L.s);
+    HIPCHK(c, launch_env_miss(L.s, c->grid, c->d_spec.get(), eio));
+    ev_mark(c, L.s, ST_ENVMISS, e0);
+    return RT_OK;
+}
+
 // mixed scenes: the NEE queue's sort, this bounce's shadow rays (before the next bounce reads L), their fallback
 int stage_nee(const PathPass& p, const Lane& L, const Bounce& bo) {
     rt_ctx* c = p.c;
@@ -1497,7 +1542,8 @@ int render_path(rt_ctx* c, const PassFacts& f, const BatchPlan& bp, int ib, int 
             for (int l = 0; l < n; ++l) {
                 Lane& L = lane[l];
                 Bounce bo{depth, p.pp.at(depth)};
-                if ((rc = stage_trace(p, L, bo)) || (rc = stage_shade(p, L, bo)) || (rc = stage_nee(p, L, bo)) ||
+                if ((rc = stage_trace(p, L, bo)) || (rc = stage_shade(p, L, bo)) || (rc = stage_env_miss(p, L, bo)) ||
+                    (rc = stage_nee(p, L, bo)) ||
                     (rc = stage_shadow(p, L, bo)))
                     return rc;
                 L.cur ^= 1;
@@ -2333,6 +2379,8 @@ static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, 
         return rc;
     std::vector<DevLight> lights = a.lights;  // (mesh lights: completed from the device tables)
     if ((rc = mesh_light_tables(c, a, d.triWorld, lights)) || (rc = upload_array(c, lights, d.lights))) return rc;
+    c->h_lights = lights;
+    c->base_lights = d.lights;
     if (qcap == 1) {
         d.cl_guard = cl.guard;
         for (int st = 0; st < 2; ++st) {
@@ -3477,6 +3525,7 @@ static int reset_stats_one(rt_ctx* c) {
     HIPCHK(c, hipDeviceSynchronize());
     harvest(c);
     c->stats = rt_stats{};
+    c->ms_env_miss = 0;
     HIPCHK(c, hipMemset(c->d_ctr.get(), 0, sizeof(unsigned long long) * kCtrWords));
     return RT_OK;
 }
@@ -3866,7 +3915,8 @@ static int impl_rt_debug_light_sample(rt_ctx* c, int light, int n, const float* 
     if (!c || n < 0 || (n && (!po || !u || !wi || !tmax || !dist2 || !nl || !tri)))
         return c ? fail(c, RT_E_ARG, "light sample: invalid argument") : RT_E_ARG;
     if (!c->have_scene) return fail(c, RT_E_STATE, "no scene");
-    if (light < 0 || light >= c->dsc.n_lights) return fail(c, RT_E_ARG, "light sample: light index out of range");
+    if (light < 0 || light >= (int)c->h_lights.size())  // (the environment light: rt_debug_env_sample)
+        return fail(c, RT_E_ARG, "light sample: light index out of range");
     if (n == 0) return RT_OK;
     hipSetDevice(c->device);
     return ordered(c, c->stream, [&]() -> int {
@@ -3892,6 +3942,144 @@ static int impl_rt_debug_light_sample(rt_ctx* c, int light, int n, const float* 
         }
         return RT_OK;
     });
+}
+
+// ---- image environment light ------------------------------------------------------------------
+// what needs no device: the descriptor's sizes, pointers, scale and texels
+static int environment_check_desc(rt_ctx* c, const rt_environment_desc* d) {
+    if (d->width < 1 || d->height < 1) return fail(c, RT_E_ARG, "environment: width and height must be >= 1");
+    if (!d->rgb) return fail(c, RT_E_ARG, "environment: NULL rgb");
+    if ((uint64_t)d->width * (uint64_t)d->height > (1ull << 24))
+        return fail(c, RT_E_LIMIT, "environment: more than 2^24 texels");
+    if (!(d->scale >= 0.f) || !std::isfinite(d->scale)) return fail(c, RT_E_ARG, "environment: scale must be finite and >= 0");
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(d->world_to_env[i])) return fail(c, RT_E_ARG, "environment: world_to_env is not finite");
+    const size_t n = 3 * (size_t)d->width * (size_t)d->height;
+    for (size_t i = 0; i < n; ++i)
+        if (!(d->rgb[i] >= 0.f) || !std::isfinite(d->rgb[i]))
+            return fail(c, RT_E_ARG, "environment: texels must be finite and >= 0");
+    return RT_OK;
+}
+
+// one device of the context: bake and tabulate the map there, then swap it in (a failure leaves the old state)
+static int environment_set_one(rt_ctx* c, const rt_environment_desc* d) {
+    hipSetDevice(c->device);
+    if (!d || d->width == 0) {  // clear: the scene's own lights and kernels again
+        HIPCHK(c, hipDeviceSynchronize());  // (passes on a caller's stream included)
+        free_environment(c);
+        return RT_OK;
+    }
+    if ((int)c->h_lights.size() + 1 > kMaxLights)
+        return fail(c, RT_E_ARG, "environment: the scene's light list is full (at most " + std::to_string(kMaxLights) + " lights)");
+    int rc;
+    if ((rc = ensure_rgb_table(c))) return rc;
+    const int W = d->width, H = d->height;
+    const size_t n = (size_t)W * (size_t)H;
+    rt_ctx::Environment E;
+    DevBuf<float> rgb, wgt, rowsum, total;
+    HIPCHK(c, rgb.reserve(3 * n)); HIPCHK(c, wgt.reserve(n)); HIPCHK(c, rowsum.reserve(H)); HIPCHK(c, total.reserve(1));
+    HIPCHK(c, E.coef.reserve(n)); HIPCHK(c, E.cond.reserve(n)); HIPCHK(c, E.marg.reserve(H));
+    HIPCHK(c, E.lights.reserve(c->h_lights.size() + 1));
+    HIPCHK(c, hipMemcpy(rgb.get(), d->rgb, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+    HIPCHK(c, launch_env_bake(c->stream, c->tx.table.get(), W, H, rgb.get(), E.coef.get(), wgt.get()));
+    HIPCHK(c, launch_env_table(c->stream, W, H, wgt.get(), E.cond.get(), rowsum.get(), E.marg.get(), total.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(&E.total, total.get(), sizeof(float), hipMemcpyDeviceToHost));
+    if (!(E.total > 0.f) || !std::isfinite(E.total))
+        return fail(c, RT_E_ARG, "environment: the total of the map's weights is not a positive finite float");
+    E.W = W; E.H = H;
+    E.dev = DevLight{};
+    E.dev.type = kLightEnv;
+    E.dev.material = -1;
+    E.dev.shape = -1;
+    E.dev.scale = d->scale;
+    for (int i = 0; i < 9; ++i) E.dev.o2r[i] = d->world_to_env[i];
+    env_pack(E.dev, EnvTab{E.coef.get(), E.cond.get(), E.marg.get(), W, H});
+    std::vector<DevLight> lights = c->h_lights;
+    lights.push_back(E.dev);
+    HIPCHK(c, hipMemcpy(E.lights.get(), lights.data(), sizeof(DevLight) * lights.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipDeviceSynchronize());  // (passes still reading the old list or the old map)
+    free_environment(c);
+    c->env = std::move(E);
+    c->env.live = true;
+    c->dsc.lights = c->env.lights.get();
+    c->dsc.n_lights = (int)lights.size();
+    return RT_OK;
+}
+
+static int impl_rt_debug_env_table(rt_ctx* c, int* w, int* h, float* coeffs4, float* cond, float* marg, float* total) {
+    if (!c || !w || !h || !total) return c ? fail(c, RT_E_ARG, "environment table: w, h and total must not be NULL") : RT_E_ARG;
+    if (!c->env.live) return fail(c, RT_E_STATE, "no environment is bound");
+    const rt_ctx::Environment& E = c->env;
+    *w = E.W; *h = E.H; *total = E.total;
+    hipSetDevice(c->device);
+    const size_t n = (size_t)E.W * (size_t)E.H;
+    if ((coeffs4 && hipMemcpy(coeffs4, E.coef.get(), sizeof(float4) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (cond && hipMemcpy(cond, E.cond.get(), sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (marg && hipMemcpy(marg, E.marg.get(), sizeof(float) * (size_t)E.H, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(c, RT_E_HIP, std::string("environment table: ") + hipGetErrorString(hipGetLastError()));
+    return RT_OK;
+}
+
+static int impl_rt_debug_env_sample(rt_ctx* c, int n, const float* u, float* wi, float* pdf, int32_t* texel) {
+    if (!c || n < 0 || (n && (!u || !wi || !pdf || !texel)))
+        return c ? fail(c, RT_E_ARG, "environment sample: invalid argument") : RT_E_ARG;
+    if (!c->env.live) return fail(c, RT_E_STATE, "no environment is bound");
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float> du;
+        DevBuf<float4> dw;
+        DevBuf<int> dt;
+        if (du.reserve(2 * (size_t)n) || dw.reserve(n) || dt.reserve(n)) return fail(c, RT_E_OOM, "environment sample buffers");
+        std::vector<float4> hw(n);
+        if (hipMemcpy(du.get(), u, 8 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_env_sample(c->stream, c->env.dev, n, du.get(), dw.get(), dt.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(hw.data(), dw.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(texel, dt.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("environment sample: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) {
+            wi[3 * i] = hw[i].x; wi[3 * i + 1] = hw[i].y; wi[3 * i + 2] = hw[i].z;
+            pdf[i] = hw[i].w;
+        }
+        return RT_OK;
+    });
+}
+
+static int impl_rt_debug_env_eval(rt_ctx* c, int n, const float* dir, int32_t* texel, float* pdf) {
+    if (!c || n < 0 || (n && (!dir || !texel || !pdf)))
+        return c ? fail(c, RT_E_ARG, "environment eval: invalid argument") : RT_E_ARG;
+    if (!c->env.live) return fail(c, RT_E_STATE, "no environment is bound");
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float> dd, dp;
+        DevBuf<int> dt;
+        if (dd.reserve(3 * (size_t)n) || dp.reserve(n) || dt.reserve(n)) return fail(c, RT_E_OOM, "environment eval buffers");
+        if (hipMemcpy(dd.get(), dir, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_env_eval(c->stream, c->env.dev, n, dd.get(), dt.get(), dp.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(texel, dt.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(pdf, dp.get(), 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("environment eval: ") + hipGetErrorString(hipGetLastError()));
+        return RT_OK;
+    });
+}
+
+// the miss stage's HIP-event time since the last rt_reset_stats (also part of rt_stats.ms_shade)
+static int impl_rt_debug_env_stats(rt_ctx* c, double* ms_miss, int64_t* launches) {
+    if (!c || !ms_miss) return c ? fail(c, RT_E_ARG, "environment stats: NULL") : RT_E_ARG;
+    hipSetDevice(c->device);
+    HIPCHK(c, hipDeviceSynchronize());
+    harvest(c);
+    *ms_miss = c->ms_env_miss;
+    if (launches) {
+        long long n[6];
+        tabled_launch_counts(n);
+        for (int i = 0; i < 6; ++i) launches[i] = n[i];
+    }
+    return RT_OK;
 }
 
 // the albedo bake kernel alone, on explicit coefficients under the current sensor
@@ -3974,6 +4162,18 @@ static int impl_rt_scene_upload(rt_ctx* c, const rt_scene_desc* s) {
     if (!c) return RT_E_ARG;
     return on_all(c, [&](rt_ctx* x) { return scene_upload_one(x, s); });
 }
+static int impl_rt_scene_set_environment(rt_ctx* c, const rt_environment_desc* d) {
+    if (!c) return RT_E_ARG;
+    if (!c->have_scene) return fail(c, RT_E_STATE, "rt_scene_set_environment needs an uploaded scene");
+    if (c->ad.live) return fail(c, RT_E_STATE, "rt_scene_set_environment during an adaptive session (rt_adaptive_end first)");
+    if (c->tp.live) return fail(c, RT_E_STATE, "rt_scene_set_environment during a temporal session (rt_temporal_end first)");
+    if (d && d->width != 0)
+        if (int rc = environment_check_desc(c, d)) return rc;
+    // every device first bakes into buffers of its own: a device that refuses leaves the others' bound map for the
+    // caller to clear or replace (the first device's refusal, the usual one, changes nothing anywhere)
+    return on_all(c, [&](rt_ctx* x) { return environment_set_one(x, d); });
+}
+
 static int impl_rt_camera_set(rt_ctx* c, const rt_camera_desc* d) {
     if (!c) return RT_E_ARG;
     return on_all(c, [&](rt_ctx* x) { return camera_set_one(x, d); });
@@ -4152,6 +4352,26 @@ int rt_debug_meshlight_table(rt_ctx* c, int light, int* n, int32_t* tri, float* 
 int rt_debug_light_sample(rt_ctx* c, int light, int n, const float* po, const float* u, float* wi, float* tmax,
                           float* dist2, float* nl, int32_t* tri) {
     return entry(c, impl_rt_debug_light_sample, light, n, po, u, wi, tmax, dist2, nl, tri);
+}
+int rt_scene_set_environment(rt_ctx* c, const rt_environment_desc* d) { return entry(c, impl_rt_scene_set_environment, d); }
+int rt_env_texel(int width, int height, const float* world_to_env, const float* dir, int* x, int* y, float* jac) {
+    if (width < 1 || height < 1 || !world_to_env || !dir || !x || !y || !jac) return RT_E_ARG;
+    float l2;
+    env_dir_to_texel(width, height, world_to_env, dir, *x, *y, l2);
+    *jac = env_pdf_omega(1.f, l2);
+    return RT_OK;
+}
+int rt_debug_env_table(rt_ctx* c, int* w, int* h, float* coeffs4, float* cond, float* marg, float* total) {
+    return entry(c, impl_rt_debug_env_table, w, h, coeffs4, cond, marg, total);
+}
+int rt_debug_env_sample(rt_ctx* c, int n, const float* u, float* wi, float* pdf, int32_t* texel) {
+    return entry(c, impl_rt_debug_env_sample, n, u, wi, pdf, texel);
+}
+int rt_debug_env_eval(rt_ctx* c, int n, const float* dir, int32_t* texel, float* pdf) {
+    return entry(c, impl_rt_debug_env_eval, n, dir, texel, pdf);
+}
+int rt_debug_env_stats(rt_ctx* c, double* ms_miss, int64_t* launches) {
+    return entry(c, impl_rt_debug_env_stats, ms_miss, launches);
 }
 int rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
     return entry(c, impl_rt_debug_albedo_bake, n, coeffs, rgb);

@@ -112,6 +112,34 @@ inline __host__ __device__ MeshLightTab meshlight_tab(const DevLight& L) {
     return t;
 }
 
+// The environment light (type 5 = RT_LIGHT_ENV; rt_scene_set_environment appends it to the list): its
+// baked texels coef[y W + x] = (c0, c1, c2, m), the rows' conditional cdfs cond[y W + x] and the marginal cdf marg[y]
+// (k_env_table) travel in the words of p, e1, e2 and n, which it does not use; world_to_env (3x3, column-major) in
+// o2r[0..8]; scale in scale.  DevLight, DevScene and the kernels' arguments keep their size.
+struct EnvTab {
+    const float4* coef;
+    const float* cond;
+    const float* marg;
+    int W, H;
+};
+inline __host__ __device__ void env_pack(DevLight& L, const EnvTab& t) {
+    __builtin_memcpy(&L.p[0], &t.coef, 8);
+    __builtin_memcpy(&L.e1[0], &t.cond, 8);
+    __builtin_memcpy(&L.e2[0], &t.marg, 8);
+    __builtin_memcpy(&L.n[0], &t.W, 4);
+    __builtin_memcpy(&L.n[1], &t.H, 4);
+}
+inline __host__ __device__ EnvTab env_tab(const DevLight& L) {
+    EnvTab t;
+    __builtin_memcpy(&t.coef, &L.p[0], 8);
+    __builtin_memcpy(&t.cond, &L.e1[0], 8);
+    __builtin_memcpy(&t.marg, &L.e2[0], 8);
+    __builtin_memcpy(&t.W, &L.n[0], 4);
+    __builtin_memcpy(&t.H, &L.n[1], 4);
+    return t;
+}
+static const int kLightEnv = 5;      // DevLight type of the environment light (RT_LIGHT_ENV)
+
 struct DevMaterial {                // rt_material + the area light it feeds (MIS)
     float c0, c1, c2, emit;
     int type;
@@ -489,8 +517,9 @@ struct NeeIO {
     int* fb_len;   // re-run by k_path_nee<Q, true> with the exact traversal (their count: zeroed with the region)
     unsigned* key; // NEE sort (nullptr: none): the Morton code of the shading point per NEE queue position
     float4 lo, scale; int key_bits;  // its quantisation (SortRaysIO lo / scale) and bits per axis
-    // mesh lights: 1 = the scene has an RT_LIGHT_MESH, the launchers pick the ML instantiations of
-    // k_path_shade_full and k_path_nee (no kernel reads it).  Like tex below it sits in what was padding.
+    // tabled lights: bit 0 = the scene has an RT_LIGHT_MESH, bit 1 = an environment light (§3j); the
+    // launchers pick the TL instantiations of k_path_shade_full and k_path_nee by it (no kernel reads it).  Like tex
+    // below it sits in what was padding.
     int ml = 0;
     // albedo textures: the scene's DevTex in device memory, read by the TEX instantiations of
     // k_path_shade_full and k_path_nee alone (nullptr: no textures, the launchers pick the untextured kernels).  It
@@ -727,6 +756,33 @@ hipError_t launch_meshlight_table(hipStream_t st, const float4* triWorld, int n_
 // the path kernels' light_ray on explicit (po, u): a[i] = (wi, tmax), b[i] = (dist2, nl), tri[i]
 hipError_t launch_light_sample(hipStream_t st, const DevScene& sc, int light, int n, const float* po, const float* u,
                                float4* a, float4* b, int* tri);
+
+// Environment light (rt_envlight.hip).
+// bake: texel i of W x H, rgb[3 i ..] linear-sRGB floats -> coef[i] = (c0, c1, c2, m), m = 2 max(r, g, b) and (c0, c1, c2)
+// = rgb_to_sigmoid(rgb / m) (a black texel: all 0), and wgt[i] = max(r, g, b) / |p|^3 at the texel centre.
+hipError_t launch_env_bake(hipStream_t st, const float* table, int W, int H, const float* rgb, float4* coef, float* wgt);
+// table: cond = each row's inclusive prefix sums of wgt in k_meshlight_table's scan order divided by the row's total
+// (rowsum[y]; a zero row: all 0), marg = the same scan of rowsum divided by its total, *total = that total.
+hipError_t launch_env_table(hipStream_t st, int W, int H, const float* wgt, float* cond, float* rowsum, float* marg,
+                            float* total);
+// The misses of one depth (k_env_miss): for every queue position whose hitPrim < 0, L += beta Le(d), weighted by the
+// power heuristic against the map's own pdf when the slot's prevPdf != 0 (MIS), nothing when prevPdf != 0 without MIS.
+// Runs after the depth's shade (which zero-initialises L at lean depth 0) and before its queue buffers are reused.
+struct EnvMissIO {
+    QueueView q;              // the traced queue (the shade's)
+    const float4* ray;        // its rays, interleaved pairs: ray k at ray[2k] (w = slot), ray[2k + 1]
+    const int* hitPrim;       // at queue position
+    RecView rec;
+    int depth, lean, mis;
+    DevLight env;
+};
+hipError_t launch_env_miss(hipStream_t st, int grid, const DevSpectra* sp, const EnvMissIO& io);
+// parity entries: the kernels' own env_sample / env_eval (rt_device.h), one item per thread.
+// sample: u[2 i ..] -> wi[i] = (direction, pdf_omega), texel[i]; eval: dir[3 i ..] -> texel[i], pdf[i]
+// launches of k_path_shade_full (out[0..2]: TL 0, 1, 2) and k_path_nee (out[3..5]) since the process started (rt_kernels.hip)
+void tabled_launch_counts(long long out[6]);
+hipError_t launch_env_sample(hipStream_t st, const DevLight& env, int n, const float* u, float4* wi, int* texel);
+hipError_t launch_env_eval(hipStream_t st, const DevLight& env, int n, const float* dir, int* texel, float* pdf);
 
 // Albedo textures (rt_texture.hip).  table: the RGB -> sigmoid coefficient table on the device, kRgbRes
 // z-nodes followed by kRgbTableFloats coefficients (rt_texture.h).

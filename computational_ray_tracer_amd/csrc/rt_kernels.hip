@@ -13,6 +13,7 @@
 // and dominant-axis bin, so trace waves see one watertight-test permutation.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <unordered_map>
@@ -2601,10 +2602,11 @@ __global__ void __launch_bounds__(kBlock) k_occluded(DevScene sc, int n, const f
 // io.bin_idx: hits only: k_bin_materials appends no miss to any bin) — each bin kernel holds only its materials' code.
 // TEX (a scene with albedo textures): a textured triangle's (c0, c1, c2) come from its texel (tex_fetch)
 // and its NEE record's tag names the texel instead of the material; the untextured instantiations hold none of it.
-// ML (a scene with an RT_LIGHT_MESH): light_ray's table search and triangle sample, the sampled
-// triangle's normal in the light weight and the hit triangle's in the emitter-hit pdf; the other instantiations hold
-// none of it.
-template <int QCAP, int MC, bool TEX = false, bool ML = false>
+// TL (tabled lights) >= 1 (a scene with an RT_LIGHT_MESH): light_ray's table search and triangle sample,
+// the sampled triangle's normal in the light weight and the hit triangle's in the emitter-hit pdf.  TL == 2 (a scene
+// with an environment light, §3j): the mesh lights' code and the environment's sample (env_sample through light_ray)
+// with its weight cs / pdf_omega.  An instantiation holds none of what its TL excludes.
+template <int QCAP, int MC, bool TEX = false, int TL = 0>
 #ifndef RT_FULL_WAVES
 #define RT_FULL_WAVES RT_MULTI_WAVES  // the mixed-scene shade (variant builds)
 #endif
@@ -2706,7 +2708,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             V3 dv = vsub(p, ro);
                             float dist2 = vdot(dv, dv);
                             V3 ln = v3(Lt.n[0], Lt.n[1], Lt.n[2]);
-                            if (ML && Lt.type == 4) ln = nout;  // (a mesh light's triangles: the hit one's ng)
+                            if (TL >= 1 && Lt.type == 4) ln = nout;  // (a mesh light's triangles: the hit one's ng)
                             float cl = -vdot(ln, rayd);
                             if (cl > 0) {
                                 float wb = power_heuristic(prevPdf, dist2 / (cl * Lt.area));
@@ -2791,13 +2793,17 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                                 float u0, u1;
                                 sm.get2d(smp, u0, u1);
                                 MeshSample ms;
-                                const LightRay lr = light_ray<ML>(Lt, po, u0, u1, sc.triWorld, ms);
+                                const LightRay lr = light_ray<TL>(Lt, po, u0, u1, sc.triWorld, ms);
                                 const float cs = vdot(nrm, lr.wi);
                                 bool ok;
                                 float wgt;
-                                if (Lt.type <= 1 || (ML && Lt.type == 4)) {
+                                if (TL == 2 && Lt.type == kLightEnv) {
+                                    ok = cs > 0 && ms.pdf > 0;
+                                    wgt = cs / ms.pdf;
+                                    if (sc.mis) wgt = wgt * power_heuristic(ms.pdf, cs * InvPi);
+                                } else if (Lt.type <= 1 || (TL >= 1 && Lt.type == 4)) {
                                     V3 ln = v3(Lt.n[0], Lt.n[1], Lt.n[2]);
-                                    if (ML && Lt.type == 4) ln = ms.nl;
+                                    if (TL >= 1 && Lt.type == 4) ln = ms.nl;
                                     float cl = -vdot(ln, lr.wi);
                                     ok = cs > 0 && cl > 0;
                                     float G = (cs * cl) / lr.dist2;
@@ -2922,8 +2928,10 @@ __global__ void __launch_bounds__(kBlock) k_occluded_path(DevScene sc, int n, co
 // reference BFS for the ambiguous rays), so this kernel never holds the BFS's registers (128 VGPRs + spill -> 108).
 // A vertex's lights are always accumulated together, in light order, by one of the two.
 // TEX: the tag's low 31 bits are a material id below n_materials, else n_materials + a texel of the scene's texel array.
-// ML: light_ray with the mesh-light search (the record holds (u0, u1) alone: the triangle is found again).
-template <int QCAP, bool FB, bool TEX = false, bool ML = false>
+// TL >= 1: light_ray with the mesh-light search (the record holds (u0, u1) alone: the triangle is found again, DESIGN.md
+// §3i).  TL == 2: the environment light as well (§3j): its texel is found again the same way and its term uses the
+// texel's Le(lambda) per wavelength where the other lights use sc_le D65.
+template <int QCAP, bool FB, bool TEX = false, int TL = 0>
 #ifndef RT_NEE_WAVES
 #define RT_NEE_WAVES 4  // (variant builds: Makefile `variants`)
 #endif
@@ -2962,6 +2970,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
         uint64_t vis = 0;
         ctr_t nv = 0;
         bool defer = false;
+        int envTexel = 0;  // (TL == 2: the environment sample's texel, for its Le below)
         for (int li = 0; li < nl; ++li) {
             const bool act = live && !defer && ((wmask >> li) & 1u);
             bool occ = false, amb = false;
@@ -2969,7 +2978,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             if (act) {
                 ++nv;
                 MeshSample ms;
-                lr = light_ray<ML>(ldconst(sc.lights, li), po, uv[2 * li], uv[2 * li + 1], sc.triWorld, ms);
+                const DevLight Ls = ldconst(sc.lights, li);
+                lr = light_ray<TL>(Ls, po, uv[2 * li], uv[2 * li + 1], sc.triWorld, ms);
+                if (TL == 2 && Ls.type == kLightEnv) envTexel = ms.tri;
                 if constexpr (COOP) occ = scene_occluded_bvh(sc, po, lr.wi, lr.tmax, snn, snt, amb);
                 else occ = scene_occluded<QCAP>(sc, po, lr.wi, lr.tmax, snn, snt, sfb);
             }
@@ -3026,13 +3037,20 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                 for (int li = 0; li < nl; ++li) {
                     if (!((vis >> li) & 1)) continue;
                     const DevLight Lt = ldconst(sc.lights, li);
-                    const float sc_le = Lt.type <= 1 || (ML && Lt.type == 4) ? sc.materials[Lt.material].emit : Lt.scale;
+                    const float sc_le = Lt.type <= 1 || (TL >= 1 && Lt.type == 4) ? sc.materials[Lt.material].emit : Lt.scale;
                     if ((li >> 2) != wq) {
                         wq = li >> 2;
                         w4 = reinterpret_cast<const float4*>(wg)[wq];
                     }
                     const int l4 = li & 3;
                     const float wgt = l4 == 0 ? w4.x : l4 == 1 ? w4.y : l4 == 2 ? w4.z : w4.w;
+                    if (TL == 2 && Lt.type == kLightEnv) {
+                        const float4 ec = env_tab(Lt).coef[envTexel];
+#pragma unroll
+                        for (int i = 0; i < 8; ++i)
+                            L[i] += ((x[i] * env_le(Lt.scale, ec, lam[i], d65_query(sp, lam[i])))) * wgt;
+                        continue;
+                    }
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         float Le = sc_le * d65_query(sp, lam[i]);
@@ -3308,6 +3326,15 @@ hipError_t launch_path_shadow(hipStream_t st, int grid, int qcap, bool dfs, cons
     return launch_resident(k, gb, grid, st, sc, io, shq, ctr);
 }
 
+// Launches of k_path_shade_full ([0]) and k_path_nee ([1], the fallback included) per tabled-light instantiation TL since
+// the process started: what rt_debug_env_stats reports, so a test can see on the device's side which instantiations a
+// scene with and without a map runs.
+static std::atomic<long long> g_tl_launches[2][3];
+void tabled_launch_counts(long long out[6]) {
+    for (int k = 0; k < 2; ++k)
+        for (int t = 0; t < 3; ++t) out[3 * k + t] = g_tl_launches[k][t].load(std::memory_order_relaxed);
+}
+
 hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene& sc, const DevSpectra* sp,
                              const DevSampler& smp, const DevFilm& film, const SampleIds& ids, const PathIO& io,
                              unsigned long long* ctr, const ShadowQueueIO& shq, const NeeIO& nee, int matclass,
@@ -3323,11 +3350,11 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
     if (!sc.full && qcap != 1 && !shq.shO) return hipErrorInvalidValue;       // so is the shadow queue
     if (sc.full) {  // (the material bins exist on multi-level scenes only: a single leaf shades every material)
         void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, NeeIO);
-        // a textured scene: the TEX instantiations; a scene with a mesh light: the ML ones
-        const int v = (nee.tex ? 1 : 0) | (nee.ml ? 2 : 0);
+        // a textured scene: the TEX instantiations; a scene with a mesh light: TL 1; with an environment light: TL 2
+        const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);
 #define RT_SHADE_FULL(Q, M) \
-    (v == 0 ? k_path_shade_full<Q, M> : v == 1 ? k_path_shade_full<Q, M, true> : v == 2 ? k_path_shade_full<Q, M, false, true> \
-                                                                                       : k_path_shade_full<Q, M, true, true>)
+    (v == 0 ? k_path_shade_full<Q, M> : v == 1 ? k_path_shade_full<Q, M, true> : v == 2 ? k_path_shade_full<Q, M, false, 1> \
+     : v == 3 ? k_path_shade_full<Q, M, true, 1> : v == 4 ? k_path_shade_full<Q, M, false, 2> : k_path_shade_full<Q, M, true, 2>)
         switch (qcap) {
             case 0: k = matclass == 1 ? RT_SHADE_FULL(0, 1) : matclass == 2 ? RT_SHADE_FULL(0, 2) : RT_SHADE_FULL(0, 0); break;
             case 1: k = RT_SHADE_FULL(1, 0); break;
@@ -3335,6 +3362,7 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
             default: return hipErrorInvalidValue;
         }
 #undef RT_SHADE_FULL
+        g_tl_launches[0][v >> 1].fetch_add(1, std::memory_order_relaxed);
         return launch_resident(k, gb, grid, st, sc, sp, smp, film, ids, io, nee);
     }
     void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, unsigned long long*, ShadowQueueIO);
@@ -3355,10 +3383,10 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
     const int gb = ring_clamp(grid > 0 ? grid : 1, qcap, sc);
     if (qcap != 1 && (!nee.fb_slot || !nee.fb_len)) return hipErrorInvalidValue;  // the fallback list is required
     void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
-    const int v = (nee.tex ? 1 : 0) | (nee.ml ? 2 : 0);  // (as launch_path_shade)
+    const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);  // (as launch_path_shade)
 #define RT_NEE(Q) \
-    (v == 0 ? k_path_nee<Q, false> : v == 1 ? k_path_nee<Q, false, true> : v == 2 ? k_path_nee<Q, false, false, true> \
-                                                                              : k_path_nee<Q, false, true, true>)
+    (v == 0 ? k_path_nee<Q, false> : v == 1 ? k_path_nee<Q, false, true> : v == 2 ? k_path_nee<Q, false, false, 1> \
+     : v == 3 ? k_path_nee<Q, false, true, 1> : v == 4 ? k_path_nee<Q, false, false, 2> : k_path_nee<Q, false, true, 2>)
     switch (qcap) {
         case 0: k = RT_NEE(0); break;
         case 1: k = RT_NEE(1); break;
@@ -3366,6 +3394,7 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
         default: return hipErrorInvalidValue;
     }
 #undef RT_NEE
+    g_tl_launches[1][v >> 1].fetch_add(1, std::memory_order_relaxed);
     return launch_resident(k, gb, grid, st, sc, sp, io, nee, ctr);
 }
 
@@ -3374,16 +3403,17 @@ hipError_t launch_path_nee_fallback(hipStream_t st, int grid, int qcap, const De
                                     const PathIO& io, const NeeIO& nee, unsigned long long* ctr) {
     const int gb = ring_clamp(std::min(grid > 0 ? grid : 1, kFallbackBlocks), qcap, sc);
     void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
-    const int v = (nee.tex ? 1 : 0) | (nee.ml ? 2 : 0);
+    const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);
 #define RT_NEE_FB(Q) \
-    (v == 0 ? k_path_nee<Q, true> : v == 1 ? k_path_nee<Q, true, true> : v == 2 ? k_path_nee<Q, true, false, true> \
-                                                                            : k_path_nee<Q, true, true, true>)
+    (v == 0 ? k_path_nee<Q, true> : v == 1 ? k_path_nee<Q, true, true> : v == 2 ? k_path_nee<Q, true, false, 1> \
+     : v == 3 ? k_path_nee<Q, true, true, 1> : v == 4 ? k_path_nee<Q, true, false, 2> : k_path_nee<Q, true, true, 2>)
     switch (qcap) {
         case 0: k = RT_NEE_FB(0); break;
         case 16: k = RT_NEE_FB(16); break;
         default: return hipErrorInvalidValue;
     }
 #undef RT_NEE_FB
+    g_tl_launches[1][v >> 1].fetch_add(1, std::memory_order_relaxed);
     return launch_resident(k, gb, grid, st, sc, sp, io, nee, ctr);
 }
 

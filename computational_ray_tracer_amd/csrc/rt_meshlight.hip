@@ -56,7 +56,7 @@ hipError_t launch_meshlight_table(hipStream_t st, const float4* triWorld, int n_
     return hipGetLastError();
 }
 
-// light_ray as k_path_shade_full and k_path_nee call it (the ML instantiation), one sample per thread:
+// light_ray as k_path_shade_full and k_path_nee call it (the TL = 1 instantiation), one sample per thread:
 // out[i] = (wi, tmax), (dist2, nl), tri; nl = the light's n and tri = -1 unless the light is a mesh light
 __global__ void __launch_bounds__(kBlockThreads) k_light_sample(DevScene sc, int light, int n,
                                                                 const float* __restrict__ po,
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(kBlockThreads) k_light_sample(DevScene sc, int
     MeshSample ms;
     ms.nl = v3(Lt.n[0], Lt.n[1], Lt.n[2]);
     ms.tri = -1;
-    const LightRay r = light_ray<true>(Lt, v3(po[3 * i], po[3 * i + 1], po[3 * i + 2]), u[2 * i], u[2 * i + 1],
+    const LightRay r = light_ray<1>(Lt, v3(po[3 * i], po[3 * i + 1], po[3 * i + 2]), u[2 * i], u[2 * i + 1],
                                        sc.triWorld, ms);
     a[i] = make_float4(r.wi.x, r.wi.y, r.wi.z, r.tmax);
     b[i] = make_float4(r.dist2, ms.nl.x, ms.nl.y, ms.nl.z);

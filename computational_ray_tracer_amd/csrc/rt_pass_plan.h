@@ -103,13 +103,15 @@ inline Knobs read_knobs() {
 }
 
 // The facts a pass's decisions rest on: the uploaded scene (DevScene qcap, n_tris, n_lights, n_emit_tris, coop_ok; the
-// upload's scene_full; live textures; a mesh light), the integrator, and the pass's pixels and index range.
+// upload's scene_full; live textures; a mesh light; a bound environment light, which DevScene n_lights counts), the
+// integrator, and the pass's pixels and index range.
 enum PassIntegrator { kIntegReference = 0, kIntegPath, kIntegPathMis };
 struct PassFacts {
     int qcap = 0, n_tris = 0, n_lights = 0, n_emit_tris = -1, coop_ok = 0;
     bool scene_full = false;
     bool textures = false;
     bool mesh_light = false;
+    bool environment = false;
     PassIntegrator integ = kIntegReference;
     int max_depth = 0;
     int n_work = 0, ib = 0, ie = 0;
@@ -140,7 +142,8 @@ inline BatchPlan plan_batches(const PassFacts& f, const Knobs& kn) {
     BatchPlan p;
     p.path = f.integ != kIntegReference;
     p.mis = f.integ == kIntegPathMis;
-    p.full = f.scene_full || p.mis || f.textures;  // (textures are fetched by the general kernels alone)
+    // (textures are fetched, and the environment light sampled, by the general kernels alone)
+    p.full = f.scene_full || p.mis || f.textures || f.environment;
     p.nsh = f.qcap == 1 ? 1 : kShards;             // single-leaf scenes use one shard
     p.dyn = f.qcap != 1;
     p.trace_fallback = f.qcap != 1 && !f.coop_ok;
@@ -167,6 +170,9 @@ struct DepthPlan {
     bool hit_pack = false;     // ... as packed records: one float4 each, hitD is neither allocated nor touched
     bool pack0 = false;        // depth 0 of a packing pass: the hit word in hitB's w lane
     bool trace_fallback = false, nee_fallback = false, shadow = false;  // the launches after the trace / NEE / shade
+    // the environment light's miss stage (k_env_miss): after this depth's shade, which zero-initialises L
+    // of the misses at lean depth 0, and before the next depth reuses the queue's hit and ray buffers
+    bool env_miss = false;
 };
 
 // The path pass: computed once per pass.
@@ -196,7 +202,8 @@ struct PathPlan {
     // mixed multi-level scenes: the trace kernel bins the hits by material class and each class is shaded by a kernel
     // holding only its materials' code (k_path_shade_full<Q, 1 / 2>)
     bool bins = false;
-    int ml = 0;                // NeeIO ml: the scene has a mesh light
+    int ml = 0;                // NeeIO ml: bit 0 the scene has a mesh light, bit 1 an environment light
+    bool env = false;          // an environment light is bound: every traced depth ends with the miss stage
     // slot state layout (rt_internal.h RecView): records for multi-level scenes (sorted, scattered slots), SoA for
     // single-leaf ones (slots stay in queue order)
     bool records = false;
@@ -226,6 +233,7 @@ struct PathPlan {
         d.trace_fallback = trace_fallback;
         d.nee_fallback = nee_fallback;
         d.shadow = shadow;
+        d.env_miss = env;
         return d;
     }
 };
@@ -244,14 +252,16 @@ inline PathPlan plan_path(const PassFacts& f, const Knobs& kn, const BatchPlan& 
     p.nee = b.full && f.n_lights > 0;
     p.sort_nee = p.nee && p.sort_rays && kn.sort_nee;
     p.bins = p.nee && multi && kn.mat_bins;
-    p.ml = f.mesh_light ? 1 : 0;
+    p.env = f.environment && b.path;
+    p.ml = (f.mesh_light ? 1 : 0) | (p.env ? 2 : 0);
     p.records = multi;
     p.rec_fs = p.records ? 1 : b.nmax;
     p.rec_ss = p.records ? (unsigned)kRecF4 : 1u;
     p.rec_rng8 = !p.records && p.lean == 1 ? 1 : 0;
     p.max_depth = f.max_depth;
     p.full = b.full;
-    p.emit_filter = kn.emit_filter && b.full && f.n_emit_tris >= 0;
+    // (with an environment light the rays that reach no emitter still add the map's radiance: no filter)
+    p.emit_filter = kn.emit_filter && b.full && f.n_emit_tris >= 0 && !p.env;
     p.trace_fallback = b.trace_fallback;
     // (no launch either when k_path_nee resolves its undecided shadow rays itself, or k_path_shade the deferred ones,
     // coop_ok: in two-lane mode it waits for the other lane's resident blocks, r05 kernel traces: 0.87 ms per bounce)

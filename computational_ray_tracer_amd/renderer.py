@@ -142,6 +142,68 @@ class Renderer:
             tri.ctypes.data_as(C.POINTER(C.c_int32))))
         return dict(wi=wi, tmax=tmax, dist2=dist2, nl=nl, tri=tri)
 
+    # ---- image environment light (rt_scene_set_environment) -------------------------------------
+    def set_environment(self, env):
+        """Bind a scene.Environment to the uploaded scene as one more light at the end of its list (None clears it;
+        configure() drops it).  The path integrators sample it and shade their misses with it; the reference integrator
+        and the feature passes ignore it."""
+        if env is None:
+            self._chk("rt_scene_set_environment", self.lib.rt_scene_set_environment(self.h, None))
+            return
+        d = env.desc()
+        self._chk("rt_scene_set_environment", self.lib.rt_scene_set_environment(self.h, C.byref(d)))
+
+    def env_table(self):
+        """rt_debug_env_table: the bound map's device tables -> dict(coeffs (H, W, 4): c0, c1, c2, m; cond (H, W);
+        marg (H); total float32)."""
+        w, h, tot = C.c_int(0), C.c_int(0), C.c_float(0)
+        self._chk("rt_debug_env_table", self.lib.rt_debug_env_table(self.h, C.byref(w), C.byref(h), None, None, None,
+                                                                    C.byref(tot)))
+        co = np.zeros((h.value, w.value, 4), np.float32)
+        cond, marg = np.zeros((h.value, w.value), np.float32), np.zeros(h.value, np.float32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_env_table", self.lib.rt_debug_env_table(
+            self.h, C.byref(w), C.byref(h), co.ctypes.data_as(F), cond.ctypes.data_as(F), marg.ctypes.data_as(F),
+            C.byref(tot)))
+        return dict(coeffs=co, cond=cond, marg=marg, total=np.float32(tot.value))
+
+    def env_sample(self, u):
+        """rt_debug_env_sample: the path kernels' environment sampling for sample points u (n, 2) -> dict(wi (n, 3),
+        pdf (n): pdf_omega, texel int32 (n): y W + x)."""
+        u = np.ascontiguousarray(u, np.float32)
+        n = len(u)
+        assert u.shape == (n, 2)
+        wi, pdf, texel = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_env_sample", self.lib.rt_debug_env_sample(
+            self.h, n, u.ctypes.data_as(F), wi.ctypes.data_as(F), pdf.ctypes.data_as(F),
+            texel.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(wi=wi, pdf=pdf, texel=texel)
+
+    def env_eval(self, dirs):
+        """rt_debug_env_eval: the miss stage's lookup for directions dirs (n, 3) -> dict(texel int32 (n), pdf (n))."""
+        d = np.ascontiguousarray(dirs, np.float32)
+        n = len(d)
+        assert d.shape == (n, 3)
+        pdf, texel = np.zeros(n, np.float32), np.zeros(n, np.int32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_env_eval", self.lib.rt_debug_env_eval(
+            self.h, n, d.ctypes.data_as(F), texel.ctypes.data_as(C.POINTER(C.c_int32)), pdf.ctypes.data_as(F)))
+        return dict(texel=texel, pdf=pdf)
+
+    def env_miss_ms(self):
+        """rt_debug_env_stats: the miss stage's HIP-event time (ms) since the last reset_stats()."""
+        ms = C.c_double(0)
+        self._chk("rt_debug_env_stats", self.lib.rt_debug_env_stats(self.h, C.byref(ms), None))
+        return ms.value
+
+    def tabled_launches(self):
+        """rt_debug_env_stats' launch counts since the process started: dict(shade=(TL 0, 1, 2), nee=(TL 0, 1, 2)) of
+        k_path_shade_full and k_path_nee (debug only: which instantiations a scene runs)."""
+        ms, n = C.c_double(0), (C.c_int64 * 6)()
+        self._chk("rt_debug_env_stats", self.lib.rt_debug_env_stats(self.h, C.byref(ms), n))
+        return dict(shade=np.array(n[0:3], np.int64), nee=np.array(n[3:6], np.int64))
+
     def set_shard(self, tile_size, n_shards, shard_id):
         self._chk("rt_set_shard", self.lib.rt_set_shard(self.h, tile_size, n_shards, shard_id))
 

@@ -514,6 +514,56 @@ def texel_index(width, height, wrap, u, v):
     return out if out.ndim else int(out)
 
 
+@dataclass
+class Environment:
+    """An image environment light (rt_environment_desc).  rgb: (H, W, 3) float32 linear-sRGB texels,
+    finite and >= 0, row y at t in [y / H, (y + 1) / H) of the octahedral square; scale multiplies the radiance;
+    world_to_env: the 3x3 rotation M as a nested array M[row][col] (stored column-major in the descriptor)."""
+    rgb: np.ndarray
+    scale: float = 1.0
+    world_to_env: np.ndarray = None
+
+    def __post_init__(self):
+        p = np.asarray(self.rgb)
+        if p.ndim != 3 or p.shape[2] != 3:
+            raise ValueError("Environment rgb: (H, W, 3)")
+        if self.world_to_env is None:
+            self.world_to_env = np.eye(3)
+        if np.asarray(self.world_to_env).shape != (3, 3):
+            raise ValueError("Environment world_to_env: 3x3")
+
+    def matrix(self):
+        """world_to_env as the descriptor stores it: 9 float32, column-major."""
+        return np.ascontiguousarray(np.asarray(self.world_to_env, np.float64).T.reshape(-1), np.float32)
+
+    def desc(self):
+        d = capi.rt_environment_desc()
+        d._rgb = np.array(self.rgb, np.float32, order="C")  # (a copy: the descriptor owns its texels)
+        d.height, d.width = d._rgb.shape[0], d._rgb.shape[1]
+        d.rgb = d._rgb.ctypes.data_as(C.POINTER(C.c_float))
+        d.scale = float(self.scale)
+        d.world_to_env[:] = [float(v) for v in self.matrix()]
+        return d
+
+
+def env_texel(width, height, world_to_env9, dirs):
+    """rt_env_texel on directions dirs (n, 3) with the column-major world_to_env9: (x int32 (n), y int32 (n),
+    jac float32 (n)), the mapping the kernels use."""
+    lib = capi.load_library()
+    m = np.ascontiguousarray(world_to_env9, np.float32)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    xs, ys, js = np.zeros(len(d), np.int32), np.zeros(len(d), np.int32), np.zeros(len(d), np.float32)
+    F = C.POINTER(C.c_float)
+    x, y, j = C.c_int(0), C.c_int(0), C.c_float(0)
+    for i in range(len(d)):
+        r = lib.rt_env_texel(int(width), int(height), m.ctypes.data_as(F), d[i].ctypes.data_as(F), C.byref(x),
+                             C.byref(y), C.byref(j))
+        if r != capi.RT_OK:
+            raise capi.RTError("rt_env_texel", r, "width, height >= 1 and non-NULL pointers")
+        xs[i], ys[i], js[i] = x.value, y.value, j.value
+    return xs, ys, js
+
+
 def grey_sigmoid(g):
     """color.cpp:35-37 uniform branch: RGBSigmoidPolynomial(0, 0, (g - .5f) / sqrt(g (1 - g))) in float32."""
     g = np.float32(g)

@@ -89,7 +89,9 @@ typedef struct {
     int material;
 } rt_shape;
 
-enum { RT_LIGHT_QUAD = 0, RT_LIGHT_DISK = 1, RT_LIGHT_POINT = 2, RT_LIGHT_DISTANT = 3, RT_LIGHT_MESH = 4 };
+enum { RT_LIGHT_QUAD = 0, RT_LIGHT_DISK = 1, RT_LIGHT_POINT = 2, RT_LIGHT_DISTANT = 3, RT_LIGHT_MESH = 4,
+       RT_LIGHT_ENV = 5 };   /* ENV: the environment light's type on the device; bound with rt_scene_set_environment,
+                                rejected (RT_E_ARG) in a light list */
 /* Build-defined lights (Lights.h:1-10 is a comment stub naming area, point and sun lights).
  * QUAD: x = p + u·e1 + v·e2, emitting normal n, Le from `material` (the quad is also geometry: two
  *   emissive triangles of the mesh);  DISK: uniform area sampling of shapes[shape] (an emissive DISK
@@ -550,6 +552,61 @@ int rt_debug_meshlight_table(rt_ctx* ctx, int light, int* n, int32_t* tri, float
  * wv = pl - po, dist2 = dot(wv, wv), wi = wv (1 / sqrtf(dist2)), tmax = sqrtf(dist2) 0.999f. */
 int rt_debug_light_sample(rt_ctx* ctx, int light, int n, const float* po, const float* u, float* wi, float* tmax,
                           float* dist2, float* nl, int32_t* tri);
+
+/* ---- image environment light (additive) -------------------------------------------
+ * One HDR map lights the scene from infinity: W x H texels of linear-sRGB float32 RGB (finite, >= 0), texel (x, y) at
+ * index y W + x, laid over the unit square (s, t) by the plain octahedral mapping, with a rotation world_to_env (3x3,
+ * column-major, glm operation order) and a scalar scale.  Build-defined; float32 in the order written, nothing fused.
+ *   direction -> texel: e = M d; a = (|e.x| + |e.y|) + |e.z|; px = e.x / a, py = e.y / a; if e.z < 0:
+ *     (px, py) = ((1 - |py|) copysignf(1, px), (1 - |px|) copysignf(1, py)) (the old values on the right);
+ *     s = px 0.5f + 0.5f, t = py 0.5f + 0.5f; x = min((int)(s W), W - 1), y = min((int)(t H), H - 1); a NaN
+ *     coordinate counts as 0 (as rt_texel_index).
+ *   (s, t) -> direction: px = 2 s - 1, py = 2 t - 1, z = (1 - |px|) - |py|; if z < 0 the same fold; p = (px, py, z);
+ *     d = M^T normalize(p).
+ *   solid angle: d omega = 4 ds dt / |p|^3, so pdf_omega = (pdf_st (l2 sqrtf(l2))) / 4 with l2 = dot(p, p).
+ *   emission (pbrt-v4 RGBIlluminantSpectrum, D65): per texel m = 2 max(r, g, b), (c0, c1, c2) = rt_rgb_to_sigmoid(rgb / m)
+ *     (a black texel: m = 0); Le(lambda) = ((scale m) s(c0 lambda^2 + c1 lambda + c2)) D65(lambda).
+ *   distribution: piecewise constant over texels, weight max(r, g, b) / (l2c sqrtf(l2c)) with l2c = dot(p, p) at the
+ *     texel centre; per row the inclusive prefix sums in rt_debug_meshlight_table's scan order divided by the row total
+ *     (a zero row: all 0), the row totals scanned and divided the same way into the marginal.
+ *   sampling: one Get2D (u0, u1) per path vertex, the light being the last of the list: y = the smallest row with
+ *     u1 < marg_y, x = the smallest column with u0 < cond_x of that row, both remapped as rt_debug_light_sample's u';
+ *     s = (x + u0') / W, t = (y + u1') / H; pdf_st = ((cond_x - cond_{x-1}) (marg_y - marg_{y-1})) (float)(W H);
+ *     tmax = FLT_MAX; the sample counts when cos > 0 and pdf_omega > 0, weight cos / pdf_omega, under PATH_MIS times
+ *     the power heuristic of (pdf_omega, cos / pi).
+ *   misses: a ray of the path integrators that leaves the scene adds beta Le(d) when it is a camera ray or follows a
+ *     mirror or glass bounce, under PATH_MIS times the power heuristic of (the bounce's pdf, pdf_omega(d)) after a
+ *     diffuse bounce, and nothing after a diffuse bounce without MIS.  Camera rays see the map as background.
+ * RT_INTEGRATOR_REFERENCE and the feature, position and chain passes ignore the map: a miss there stays a miss.
+ * Limits: nearest texel, one map, W H <= 2^24, one sample per path vertex like every light. */
+typedef struct {
+    int width, height;
+    const float* rgb;                /* width * height * 3 floats                                          */
+    float scale;
+    float world_to_env[9];
+    int reserved[4];
+} rt_environment_desc;
+/* Binds the map to the uploaded scene as one more light at the end of its list (deep copy; baked and tabulated on
+ * every device of the context); NULL or width == 0 clears it; rt_scene_upload drops it.  RT_E_STATE: no scene, an open
+ * adaptive or temporal session, or the coefficient table is missing.  RT_E_ARG: a size < 1, NULL rgb, a negative or
+ * non-finite texel or scale, a map whose weights sum to 0 or to no finite float, or a full light list.  RT_E_LIMIT:
+ * width * height > 2^24.  A rejected call leaves the scene and a map bound before as they were. */
+int rt_scene_set_environment(rt_ctx* ctx, const rt_environment_desc* desc);
+/* The texel a direction selects (host only, no context), the mapping above: *x, *y, and *jac = (l2 sqrtf(l2)) / 4, the
+ * factor from pdf_st to pdf_omega there.  RT_E_ARG for a size < 1 or a NULL pointer. */
+int rt_env_texel(int width, int height, const float* world_to_env, const float* dir, int* x, int* y, float* jac);
+/* The bound map's device tables: *w, *h always; coeffs4 (4 w h: c0, c1, c2, m per texel), cond (w h), marg (h) when
+ * non-NULL; *total = the grand total of the weights.  RT_E_STATE without a map. */
+int rt_debug_env_table(rt_ctx* ctx, int* w, int* h, float* coeffs4, float* cond, float* marg, float* total);
+/* The path kernels' own device functions, one item per thread: sample u (2n) -> wi (3n), pdf (n: pdf_omega), texel (n:
+ * y w + x); eval dir (3n) -> texel (n), pdf (n). */
+int rt_debug_env_sample(rt_ctx* ctx, int n, const float* u, float* wi, float* pdf, int32_t* texel);
+int rt_debug_env_eval(rt_ctx* ctx, int n, const float* dir, int32_t* texel, float* pdf);
+/* Debug only (an addition to the entry points above; rt_stats keeps its layout): *ms_miss = the miss stage's HIP-event
+ * time in ms since the last rt_reset_stats (rt_stats.ms_shade includes it; 0 with RTMI_NO_STAGE_EVENTS); launches, when
+ * non-NULL, 6 counts since the process started: launches of k_path_shade_full without tabled lights, with mesh lights
+ * (TL = 1), with the environment (TL = 2), then the same three for k_path_nee. */
+int rt_debug_env_stats(rt_ctx* ctx, double* ms_miss, int64_t* launches);
 
 /* ---- albedo demodulation for the denoiser (additive) ------------------------------
  * The filter divides the film by a noise-free first-hit albedo, filters the demodulated irradiance (smooth across the
