@@ -14,7 +14,7 @@ LIB_PATH = PKG_DIR / "lib" / "librtmi355x.so"
 RT_OK, RT_E_ARG, RT_E_HIP, RT_E_RCCL, RT_E_OOM, RT_E_STATE, RT_E_NODEVICE, RT_E_LIMIT = 0, -1, -2, -3, -4, -5, -6, -7
 STATUS_NAMES = {0: "RT_OK", -1: "RT_E_ARG", -2: "RT_E_HIP", -3: "RT_E_RCCL", -4: "RT_E_OOM", -5: "RT_E_STATE",
                 -6: "RT_E_NODEVICE", -7: "RT_E_LIMIT"}
-RT_MAT_DIFFUSE, RT_MAT_MIRROR, RT_MAT_DIELECTRIC = 0, 1, 2
+RT_MAT_DIFFUSE, RT_MAT_MIRROR, RT_MAT_DIELECTRIC, RT_MAT_ROUGH = 0, 1, 2, 3
 RT_SHAPE_SPHERE, RT_SHAPE_DISK, RT_SHAPE_TRIANGLE = 0, 1, 2
 RT_LIGHT_QUAD, RT_LIGHT_DISK, RT_LIGHT_POINT, RT_LIGHT_DISTANT, RT_LIGHT_MESH, RT_LIGHT_ENV = 0, 1, 2, 3, 4, 5
 RT_CAMERA_PERSPECTIVE, RT_CAMERA_ORTHOGRAPHIC, RT_CAMERA_PINHOLE, RT_CAMERA_THINLENS = 0, 1, 2, 3
@@ -203,6 +203,7 @@ EXPORTS = [
     "rt_debug_meshlight_table", "rt_debug_light_sample",
     "rt_scene_set_environment", "rt_env_texel", "rt_debug_env_table", "rt_debug_env_sample", "rt_debug_env_eval",
     "rt_debug_env_stats",
+    "rt_ggx_eval", "rt_ggx_sample", "rt_debug_ggx_sample", "rt_debug_ggx_eval", "rt_debug_rough_stats",
 ]
 
 _lib = None
@@ -320,6 +321,14 @@ def load_library(path=None):
         "rt_debug_env_sample": ([C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32)], C.c_int),
         "rt_debug_env_eval": ([C.c_void_p, C.c_int, P(C.c_float), P(C.c_int32), P(C.c_float)], C.c_int),
         "rt_debug_env_stats": ([C.c_void_p, P(C.c_double), P(C.c_int64)], C.c_int),
+        "rt_ggx_eval": ([C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)], C.c_int),
+        "rt_ggx_sample": ([C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)],
+                          C.c_int),
+        "rt_debug_ggx_sample": ([C.c_void_p, C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                 P(C.c_float), P(C.c_float), P(C.c_float)], C.c_int),
+        "rt_debug_ggx_eval": ([C.c_void_p, C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                               P(C.c_float)], C.c_int),
+        "rt_debug_rough_stats": ([C.c_void_p, P(C.c_int64)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

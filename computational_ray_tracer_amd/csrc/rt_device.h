@@ -10,6 +10,7 @@
 
 #include "rt_cull.h"
 #include "rt_envmap.h"
+#include "rt_ggx.h"
 #include "rt_internal.h"
 #include "rt_mathf.h"
 #include "rt_texture.h"

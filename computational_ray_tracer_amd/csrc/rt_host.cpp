@@ -30,6 +30,7 @@
 #include "rt_internal.h"
 #include "rt_pass_plan.h"
 #include "rt_envmap.h"
+#include "rt_ggx.h"
 #include "rt_texture.h"
 
 using namespace rtmi;
@@ -533,6 +534,8 @@ struct rt_ctx {
     rt_octree_info info{};
     bool cull = false;
     bool scene_full = false;   // the scene needs the general path-shade kernel
+    bool scene_rough = false;  // a non-emissive RT_MAT_ROUGH material: the RGH instantiations
+    long long rgh_launches[2] = {0, 0};  // the last path pass's launches of them: shade, NEE (rt_debug_rough_stats)
     DevScene dsc{};
     std::vector<DevBuf<unsigned char>> scene_allocs;  // the arrays dsc points to
     const float* d_kappa = nullptr;  // per analytic shape: the curvature the curved chain guides use (in scene_allocs)
@@ -1191,6 +1194,7 @@ PassFacts pass_facts(const rt_ctx* c, int n_work, int ib, int ie) {
     f.n_emit_tris = c->dsc.n_emit_tris; f.coop_ok = c->dsc.coop_ok;
     f.scene_full = c->scene_full; f.textures = c->tx.live; f.mesh_light = c->ml.any;
     f.environment = c->env.live;
+    f.rough = c->scene_rough;
     f.integ = c->integ.kind == RT_INTEGRATOR_PATH_MIS ? kIntegPathMis
               : c->integ.kind == RT_INTEGRATOR_PATH   ? kIntegPath : kIntegReference;
     f.max_depth = c->integ.max_depth;
@@ -1301,7 +1305,7 @@ int path_workspaces(const PathPass& p) {
     for (int l = 0; l < pp.lanes && pp.shq; ++l)
         if (int rc = ensure_shadow_workspace(c, c->ws[l].b, bp.ncap)) return rc;
     for (int l = 0; l < pp.lanes && pp.nee; ++l)
-        if (int rc = ensure_nee_workspace(c, c->ws[l].b, bp.nmax * (size_t)nee_stride(p.sc.n_lights), bp.ncap)) return rc;
+        if (int rc = ensure_nee_workspace(c, c->ws[l].b, bp.nmax * (size_t)(nee_stride(p.sc.n_lights) + (pp.rgh ? 1 : 0)), bp.ncap)) return rc;
     return RT_OK;
 }
 
@@ -1453,10 +1457,12 @@ int stage_shade(const PathPass& p, const Lane& L, Bounce& bo) {
             bp.bin_idx = bio.idx[cl];
             HIPCHK(c, launch_path_shade(L.s, c->grid, L.sc.qcap, L.sc, d_spec, p.smp, p.fd, L.ids, bp, c->d_ctr.get(),
                                         bo.sqio, bo.nio, 1 + cl));
+            if (p.pp.rgh && cl == 0) ++c->rgh_launches[0];  // (the specular bin has no RGH instantiation)
         }
     } else {
         HIPCHK(c, launch_path_shade(L.s, c->grid, L.sc.qcap, L.sc, d_spec, p.smp, p.fd, L.ids, bo.pio, c->d_ctr.get(),
                                     bo.sqio, bo.nio, 0, p.pp.hit_pack));
+        if (p.pp.rgh && p.pp.nee) ++c->rgh_launches[0];
     }
     ev_mark(c, L.s, ST_SHADE, e0);
     return RT_OK;
@@ -1492,6 +1498,7 @@ int stage_nee(const PathPass& p, const Lane& L, const Bounce& bo) {
     HIPCHK(c, launch_path_nee(L.s, c->grid, L.sc.qcap, L.sc, c->d_spec.get(), bo.pio, bo.nio, c->d_ctr.get()));
     if (bo.d.nee_fallback)
         HIPCHK(c, launch_path_nee_fallback(L.s, c->grid, L.sc.qcap, L.sc, c->d_spec.get(), bo.pio, bo.nio, c->d_ctr.get()));
+    if (p.pp.rgh) c->rgh_launches[1] += bo.d.nee_fallback ? 2 : 1;
     ev_mark(c, L.s, ST_SHADOW, e0);
     return RT_OK;
 }
@@ -1527,6 +1534,7 @@ int render_path(rt_ctx* c, const PassFacts& f, const BatchPlan& bp, int ib, int 
                      dev_film(c), pass, film};
     const int lanes = p.pp.lanes;
     int rc;
+    c->rgh_launches[0] = c->rgh_launches[1] = 0;
     if ((rc = path_workspaces(p))) return rc;
     if (lanes > 1) {  // lanes 1.. start after the caller's earlier work on st
         HIPCHK(c, hipEventRecord(c->ws[0].film_done, st));
@@ -1944,8 +1952,11 @@ static std::string validate_scene(const rt_scene_desc* s, bool geometry_only = f
             if (!mat_ok(s->tri_material[t])) return "material id out of range";
     for (int i = 0; i < s->n_materials; ++i) {
         const rt_material& m = s->materials[i];
-        if (m.type < RT_MAT_DIFFUSE || m.type > RT_MAT_DIELECTRIC) return "unknown material type";
+        if (m.type < RT_MAT_DIFFUSE || m.type > RT_MAT_ROUGH) return "unknown material type";
         if (m.type == RT_MAT_DIELECTRIC && m.eta < 0) return "dielectric eta must be >= 0";
+        // (the roughness travels in eta; an emitter of type 3 is an emitter like any other: its eta is not read)
+        if (m.type == RT_MAT_ROUGH && !(m.emission_scale > 0) && !ggx_alpha_ok(m.eta))
+            return "rough material: alpha (rt_material.eta) must be in [0.01, 1] (below 0.01: RT_MAT_MIRROR)";
     }
     if (s->n_shapes < 0 || (s->n_shapes > 0 && !s->shapes)) return "shapes";
     for (int i = 0; i < s->n_shapes; ++i) {
@@ -2160,6 +2171,7 @@ struct ShadingArrays {
     // light's material in ascending id (n = 0: not a mesh light)
     std::vector<int> ml_first, ml_n, ml_tri;
     bool full = false;              // the scene needs the general path-shade kernel
+    bool rough = false;             // a non-emissive RT_MAT_ROUGH material (the RGH instantiations)
 };
 // The curvature magnitude the curved chain guides give a shape: 1 / (radius sigma) for a sphere whose
 // object_to_render linear part L is a rotation times a uniform scale sigma, 0 for every other shape.  In float64:
@@ -2197,7 +2209,9 @@ static void shading_arrays(const rt_scene_desc* s, const SceneWorld& sw, Shading
     std::vector<DevMaterial>& mats = a.mats;
     for (int i = 0; i < s->n_materials; ++i) {
         const rt_material& m = s->materials[i];
-        const int cls = m.emission_scale > 0 || m.type == RT_MAT_DIFFUSE ? 0 : 1;  // material bin (kMatClasses)
+        // material bin (kMatClasses): a rough reflector reads spectra and writes NEE records, like Lambert
+        const int cls = material_class(m.type, m.emission_scale > 0);  // (rt_pass_plan.h)
+        a.rough = a.rough || rough_fact(m.type, m.emission_scale > 0);
         mats.push_back(DevMaterial{m.sigmoid[0], m.sigmoid[1], m.sigmoid[2], m.emission_scale, m.type, m.eta, -1, cls});
     }
     if (mats.empty()) mats.push_back(DevMaterial{0.f, 0.f, 0.f, 0.f, RT_MAT_DIFFUSE, 0.f, -1, 0});
@@ -2422,6 +2436,7 @@ static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, 
     d.n_shapes = s->n_shapes;
     d.n_materials = (int)a.mats.size();
     c->scene_full = a.full;
+    c->scene_rough = a.rough;
     d.qcap = qcap;
     // the cooperative BFS's FIFO holds 16-bit group ids (first child = 1 + 8 g) and kCoopFifo of them
     d.coop_ok = c->knobs.coop && qcap != 1 && lim.bound <= kCoopFifo && lim.ids16 ? 1 : 0;
@@ -4082,6 +4097,71 @@ static int impl_rt_debug_env_stats(rt_ctx* c, double* ms_miss, int64_t* launches
     return RT_OK;
 }
 
+// ---- rough reflector: the shade kernel's GGX device functions on explicit inputs
+static int impl_rt_debug_ggx_sample(rt_ctx* c, float alpha, int n, const float* normal, const float* dir, const float* u,
+                                    float* disk_out, float* wi, float* wb, float* pdf) {
+    if (!c || n < 0 || !ggx_alpha_ok(alpha) || (n && (!normal || !dir || !u || !disk_out || !wi || !wb || !pdf)))
+        return c ? fail(c, RT_E_ARG, "ggx sample: invalid argument") : RT_E_ARG;
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float> dn, dd, du;
+        DevBuf<float2> dk, dp;
+        DevBuf<float4> dw;
+        if (dn.reserve(3 * (size_t)n) || dd.reserve(3 * (size_t)n) || du.reserve(2 * (size_t)n) || dk.reserve(n) ||
+            dp.reserve(n) || dw.reserve(n))
+            return fail(c, RT_E_OOM, "ggx sample buffers");
+        std::vector<float4> hw(n);
+        std::vector<float2> hp(n);
+        if (hipMemcpy(dn.get(), normal, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dd.get(), dir, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(du.get(), u, 8 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_ggx_sample(c->stream, alpha, n, dn.get(), dd.get(), du.get(), dk.get(), dw.get(), dp.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(disk_out, dk.get(), 8 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hw.data(), dw.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hp.data(), dp.get(), sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("ggx sample: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) {
+            wi[3 * i] = hw[i].x; wi[3 * i + 1] = hw[i].y; wi[3 * i + 2] = hw[i].z;
+            wb[i] = hp[i].x; pdf[i] = hp[i].y;
+        }
+        return RT_OK;
+    });
+}
+
+static int impl_rt_debug_ggx_eval(rt_ctx* c, float alpha, int n, const float* normal, const float* dir, const float* wi,
+                                  float* fcos, float* pdf) {
+    if (!c || n < 0 || !ggx_alpha_ok(alpha) || (n && (!normal || !dir || !wi || !fcos || !pdf)))
+        return c ? fail(c, RT_E_ARG, "ggx eval: invalid argument") : RT_E_ARG;
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float> dn, dd, dw;
+        DevBuf<float2> dp;
+        if (dn.reserve(3 * (size_t)n) || dd.reserve(3 * (size_t)n) || dw.reserve(3 * (size_t)n) || dp.reserve(n))
+            return fail(c, RT_E_OOM, "ggx eval buffers");
+        std::vector<float2> hp(n);
+        if (hipMemcpy(dn.get(), normal, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dd.get(), dir, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dw.get(), wi, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_ggx_eval(c->stream, alpha, n, dn.get(), dd.get(), dw.get(), dp.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(hp.data(), dp.get(), sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("ggx eval: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) { fcos[i] = hp[i].x; pdf[i] = hp[i].y; }
+        return RT_OK;
+    });
+}
+
+// launches of the RGH instantiations by the context's last path pass (render_path counts them)
+static int impl_rt_debug_rough_stats(rt_ctx* c, int64_t* launches) {
+    if (!c || !launches) return c ? fail(c, RT_E_ARG, "rough stats: NULL") : RT_E_ARG;
+    launches[0] = c->rgh_launches[0];
+    launches[1] = c->rgh_launches[1];
+    return RT_OK;
+}
+
 // the albedo bake kernel alone, on explicit coefficients under the current sensor
 static int impl_rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
     if (!c || n < 0 || (n && (!coeffs || !rgb))) return c ? fail(c, RT_E_ARG, "albedo bake: invalid argument") : RT_E_ARG;
@@ -4373,6 +4453,31 @@ int rt_debug_env_eval(rt_ctx* c, int n, const float* dir, int32_t* texel, float*
 int rt_debug_env_stats(rt_ctx* c, double* ms_miss, int64_t* launches) {
     return entry(c, impl_rt_debug_env_stats, ms_miss, launches);
 }
+int rt_ggx_eval(float alpha, int n, const float* wo, const float* wi, float* fcos, float* pdf) {
+    if (n < 0 || !ggx_alpha_ok(alpha) || (n && (!wo || !wi || !fcos || !pdf))) return RT_E_ARG;
+    for (int i = 0; i < n; ++i)
+        ggx_eval(alpha, V3{wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]}, V3{wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]}, fcos[i],
+                 pdf[i]);
+    return RT_OK;
+}
+int rt_ggx_sample(float alpha, int n, const float* wo, const float* disk, float* wi, float* wb, float* pdf) {
+    if (n < 0 || !ggx_alpha_ok(alpha) || (n && (!wo || !disk || !wi || !wb || !pdf))) return RT_E_ARG;
+    for (int i = 0; i < n; ++i) {
+        V3 w;
+        ggx_sample_disk(alpha, V3{wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]}, disk[2 * i], disk[2 * i + 1], w, wb[i], pdf[i]);
+        wi[3 * i] = w.x; wi[3 * i + 1] = w.y; wi[3 * i + 2] = w.z;
+    }
+    return RT_OK;
+}
+int rt_debug_ggx_sample(rt_ctx* c, float alpha, int n, const float* normal, const float* dir, const float* u,
+                        float* disk_out, float* wi, float* wb, float* pdf) {
+    return entry(c, impl_rt_debug_ggx_sample, alpha, n, normal, dir, u, disk_out, wi, wb, pdf);
+}
+int rt_debug_ggx_eval(rt_ctx* c, float alpha, int n, const float* normal, const float* dir, const float* wi, float* fcos,
+                      float* pdf) {
+    return entry(c, impl_rt_debug_ggx_eval, alpha, n, normal, dir, wi, fcos, pdf);
+}
+int rt_debug_rough_stats(rt_ctx* c, int64_t* launches) { return entry(c, impl_rt_debug_rough_stats, launches); }
 int rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
     return entry(c, impl_rt_debug_albedo_bake, n, coeffs, rgb);
 }

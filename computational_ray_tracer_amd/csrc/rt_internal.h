@@ -783,6 +783,12 @@ hipError_t launch_env_miss(hipStream_t st, int grid, const DevSpectra* sp, const
 void tabled_launch_counts(long long out[6]);
 hipError_t launch_env_sample(hipStream_t st, const DevLight& env, int n, const float* u, float4* wi, int* texel);
 hipError_t launch_env_eval(hipStream_t st, const DevLight& env, int n, const float* dir, int* texel, float* pdf);
+// ---- rough reflector (rt_rough.hip): the shade kernel's GGX device functions, one item per thread
+// sample: (nrm, dir, u) -> disk[i] = the disk point, wi[i] = (world direction, 0), wbpdf[i] = (wb, pdf); eval -> (fcos, pdf)
+hipError_t launch_ggx_sample(hipStream_t st, float alpha, int n, const float* nrm, const float* dir, const float* u,
+                             float2* disk, float4* wi, float2* wbpdf);
+hipError_t launch_ggx_eval(hipStream_t st, float alpha, int n, const float* nrm, const float* dir, const float* wi,
+                           float2* out);
 
 // Albedo textures (rt_texture.hip).  table: the RGB -> sigmoid coefficient table on the device, kRgbRes
 // z-nodes followed by kRgbTableFloats coefficients (rt_texture.h).

@@ -2606,7 +2606,12 @@ __global__ void __launch_bounds__(kBlock) k_occluded(DevScene sc, int n, const f
 // the sampled triangle's normal in the light weight and the hit triangle's in the emitter-hit pdf.  TL == 2 (a scene
 // with an environment light, §3j): the mesh lights' code and the environment's sample (env_sample through light_ray)
 // with its weight cs / pdf_omega.  An instantiation holds none of what its TL excludes.
-template <int QCAP, int MC, bool TEX = false, int TL = 0>
+// RGH (a scene with an RT_MAT_ROUGH material; MC 0 and 1 only: the specular bin never holds it): a rough
+// vertex takes the Lambert vertex's draws in the Lambert vertex's order; its light weights hold fcos = f mu_i / R
+// (rt_ggx.h ggx_eval) where Lambert's hold cs, its MIS weights the GGX pdf where Lambert's hold cs / pi, and its bounce is
+// ggx_sample_disk's with prevPdf = the GGX pdf.  The NEE record grows by one float4 (wb, rough ? 1 : 0, 0, 0) at its end,
+// from which k_path_nee<.., RGH> forms x = beta R (no 1 / pi) and the continued throughput beta (R wb).
+template <int QCAP, int MC, bool TEX = false, int TL = 0, bool RGH = false>
 #ifndef RT_FULL_WAVES
 #define RT_FULL_WAVES RT_MULTI_WAVES  // the mixed-scene shade (variant builds)
 #endif
@@ -2618,7 +2623,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
     __shared__ int lds[kBlock / 64 + 1];
     if constexpr (MC != 2) stage_spectra(sp);  // (the mirror / glass bin reads no spectrum table)
     const bool lds_mats = stage_materials(sc);
-    const int nee_f4 = nee_stride(sc.n_lights);
+    const int nee_f4 = nee_stride(sc.n_lights) + (RGH ? 1 : 0);
     DevTex tx{};
     if constexpr (TEX) tx = *nee.tex;
     // lean depth 0: k_generate stored no β = 1 / L = 0, so they start in registers and every path's L is written
@@ -2784,6 +2789,15 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             float* nuv = reinterpret_cast<float*>(nr + N_UV);
                             float* nwgt = nuv + 4 * ((sc.n_lights + 1) / 2);
                             if (nee.key) neeKey = morton_key(po.x, po.y, po.z, nee.lo, nee.scale, nee.key_bits);
+                            bool rough = false;  // (RGH: the vertex's frame and its local wo)
+                            V3 ss = v3(0, 0, 0), tt = ss, wol = ss;
+                            if constexpr (RGH) {
+                                rough = mt.type == 3;
+                                if (rough) {
+                                    ggx_frame(nrm, ss, tt);
+                                    wol = ggx_to_local(v3(-rayd.x, -rayd.y, -rayd.z), ss, tt, nrm);
+                                }
+                            }
                             // the record is written in whole float4s (two lights' samples, four lights' weights per
                             // store) instead of one 4-B store per value: 4 stores per vertex instead of 13 with 4 lights
                             float pu0 = 0.f, pu1 = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
@@ -2795,23 +2809,28 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                                 MeshSample ms;
                                 const LightRay lr = light_ray<TL>(Lt, po, u0, u1, sc.triWorld, ms);
                                 const float cs = vdot(nrm, lr.wi);
+                                float fc = cs, bpdf = 0.f;  // (rough: fcos and the GGX pdf for cs and cs / pi)
+                                if constexpr (RGH) {
+                                    if (rough) ggx_eval(mt.eta, wol, ggx_to_local(lr.wi, ss, tt, nrm), fc, bpdf);
+                                }
                                 bool ok;
                                 float wgt;
                                 if (TL == 2 && Lt.type == kLightEnv) {
                                     ok = cs > 0 && ms.pdf > 0;
-                                    wgt = cs / ms.pdf;
-                                    if (sc.mis) wgt = wgt * power_heuristic(ms.pdf, cs * InvPi);
+                                    wgt = fc / ms.pdf;
+                                    if (sc.mis) wgt = wgt * power_heuristic(ms.pdf, RGH && rough ? bpdf : cs * InvPi);
                                 } else if (Lt.type <= 1 || (TL >= 1 && Lt.type == 4)) {
                                     V3 ln = v3(Lt.n[0], Lt.n[1], Lt.n[2]);
                                     if (TL >= 1 && Lt.type == 4) ln = ms.nl;
                                     float cl = -vdot(ln, lr.wi);
                                     ok = cs > 0 && cl > 0;
-                                    float G = (cs * cl) / lr.dist2;
+                                    float G = (fc * cl) / lr.dist2;
                                     wgt = G * Lt.area;
-                                    if (sc.mis) wgt = wgt * power_heuristic(lr.dist2 / (cl * Lt.area), cs * InvPi);
+                                    if (sc.mis)
+                                        wgt = wgt * power_heuristic(lr.dist2 / (cl * Lt.area), RGH && rough ? bpdf : cs * InvPi);
                                 } else {
                                     ok = cs > 0;
-                                    wgt = cs * (Lt.type == 2 ? 1.0f / lr.dist2 : 1.0f);
+                                    wgt = fc * (Lt.type == 2 ? 1.0f / lr.dist2 : 1.0f);
                                 }
                                 const float wv = ok ? wgt : -1.0f;  // (an accepted light's weight is >= 0 or NaN)
                                 const int l4 = li & 3;
@@ -2832,21 +2851,44 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             sm.get2d(smp, u0, u1);
                             V3 wi;
                             float z;
-                            const bool bounced = cosine_bounce(u0, u1, nrm, wi, z);
-                            if (bounced) {
-                                if (!wantNee) {  // (with NEE, k_path_nee forms β R after the light terms)
+                            bool bounced;
+                            float rwb = 0.f;  // (RGH: the rough bounce's weight G2 / G1)
+                            if (RGH && rough) {
+                                float dx, dy, rpdf;
+                                disk_concentric(u0, u1, dx, dy);
+                                V3 wil;
+                                bounced = ggx_sample_disk(mt.eta, wol, dx, dy, wil, rwb, rpdf);
+                                if (bounced) {
+                                    wi = ggx_to_world(wil, ss, tt, nrm);
+                                    if (!wantNee) {  // (with NEE, k_path_nee forms β (R wb) after the light terms)
 #pragma unroll
-                                    for (int i = 0; i < 8; ++i) beta[i] *= R[i];
-                                    rstore8(io.rec, slot, R_BETA, beta);
+                                        for (int i = 0; i < 8; ++i) beta[i] *= (R[i] * rwb);
+                                        rstore8(io.rec, slot, R_BETA, beta);
+                                    }
+                                    wantNext = true;
+                                    nO = make_float4(po.x, po.y, po.z, 0.f);
+                                    nD = make_float4(wi.x, wi.y, wi.z, 0.f);
+                                    misc.y = rpdf;
                                 }
-                                wantNext = true;
-                                nO = make_float4(po.x, po.y, po.z, 0.f);
-                                nD = make_float4(wi.x, wi.y, wi.z, 0.f);
-                                misc.y = z * InvPi;
+                            } else {
+                                bounced = cosine_bounce(u0, u1, nrm, wi, z);
+                                if (bounced) {
+                                    if (!wantNee) {  // (with NEE, k_path_nee forms β R after the light terms)
+#pragma unroll
+                                        for (int i = 0; i < 8; ++i) beta[i] *= R[i];
+                                        rstore8(io.rec, slot, R_BETA, beta);
+                                    }
+                                    wantNext = true;
+                                    nO = make_float4(po.x, po.y, po.z, 0.f);
+                                    nD = make_float4(wi.x, wi.y, wi.z, 0.f);
+                                    misc.y = z * InvPi;
+                                }
                             }
-                            if (wantNee)
+                            if (wantNee) {
                                 nr[N_PO] = make_float4(po.x, po.y, po.z,
                                                        __uint_as_float(tagid | (bounced ? 0x80000000u : 0u)));
+                                if constexpr (RGH) nr[nee_f4 - 1] = make_float4(rwb, rough ? 1.f : 0.f, 0.f, 0.f);
+                            }
                         }
                         save_sampler(io, slot, sm, io.dim >= 0);
                         if (io.dim < 0) misc.x = __int_as_float(sm.dim);
@@ -2931,7 +2973,9 @@ __global__ void __launch_bounds__(kBlock) k_occluded_path(DevScene sc, int n, co
 // TL >= 1: light_ray with the mesh-light search (the record holds (u0, u1) alone: the triangle is found again, DESIGN.md
 // §3i).  TL == 2: the environment light as well (§3j): its texel is found again the same way and its term uses the
 // texel's Le(lambda) per wavelength where the other lights use sc_le D65.
-template <int QCAP, bool FB, bool TEX = false, int TL = 0>
+// RGH: the record's last float4 is (wb, rough, 0, 0); a rough vertex's x is beta R, its weights already
+// holding f mu_i / R, and its continued throughput beta (R wb).
+template <int QCAP, bool FB, bool TEX = false, int TL = 0, bool RGH = false>
 #ifndef RT_NEE_WAVES
 #define RT_NEE_WAVES 4  // (variant builds: Makefile `variants`)
 #endif
@@ -2940,7 +2984,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
     stage_spectra(sp);
     stage_scene<QCAP>(sc, 0);
     ctr_t snn = 0, snt = 0, nsh = 0, sfb = 0, nvx = 0, novf = 0;
-    const int nl = sc.n_lights, nf4 = nee_stride(nl);
+    const int nl = sc.n_lights, nf4 = nee_stride(nl) + (RGH ? 1 : 0);
     // one path vertex: visibility of each sampled light, then the unoccluded lights' contributions in order, then
     // the throughput of the continued path (NeeIO)
     const float InvPi = 0.31830988618379067154f;
@@ -3027,11 +3071,14 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) R[i] = sigmoid_eval(rc0, rc1, rc2, lam[i]);
+            float4 rg = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (RGH) rg = r[nf4 - 1];
+            const bool rough = RGH && rg.y != 0.f;
             if (vis) {
                 float L[8], x[8];
                 rload8(io.rec, slot, R_L, L);
 #pragma unroll
-                for (int i = 0; i < 8; ++i) x[i] = beta[i] * (R[i] * InvPi);
+                for (int i = 0; i < 8; ++i) x[i] = RGH && rough ? beta[i] * R[i] : beta[i] * (R[i] * InvPi);
                 float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);  // the weights again, four per 16-B load
                 int wq = -1;
                 for (int li = 0; li < nl; ++li) {
@@ -3061,7 +3108,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             }
             if (bounced) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) beta[i] *= R[i];
+                for (int i = 0; i < 8; ++i) beta[i] *= RGH && rough ? R[i] * rg.x : R[i];
                 rstore8(io.rec, slot, R_BETA, beta);
             }
         }
@@ -3352,16 +3399,21 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
         void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, NeeIO);
         // a textured scene: the TEX instantiations; a scene with a mesh light: TL 1; with an environment light: TL 2
         const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);
-#define RT_SHADE_FULL(Q, M) \
-    (v == 0 ? k_path_shade_full<Q, M> : v == 1 ? k_path_shade_full<Q, M, true> : v == 2 ? k_path_shade_full<Q, M, false, 1> \
-     : v == 3 ? k_path_shade_full<Q, M, true, 1> : v == 4 ? k_path_shade_full<Q, M, false, 2> : k_path_shade_full<Q, M, true, 2>)
+        // a scene with a rough material (NeeIO ml bit 2): the RGH instantiations, except for the specular bin
+        const bool rg = (nee.ml & 4) != 0;
+#define RT_SHADE_FULL_R(Q, M, R) \
+    (v == 0 ? k_path_shade_full<Q, M, false, 0, R> : v == 1 ? k_path_shade_full<Q, M, true, 0, R> \
+     : v == 2 ? k_path_shade_full<Q, M, false, 1, R> : v == 3 ? k_path_shade_full<Q, M, true, 1, R> \
+     : v == 4 ? k_path_shade_full<Q, M, false, 2, R> : k_path_shade_full<Q, M, true, 2, R>)
+#define RT_SHADE_FULL(Q, M) (rg ? RT_SHADE_FULL_R(Q, M, true) : RT_SHADE_FULL_R(Q, M, false))
         switch (qcap) {
-            case 0: k = matclass == 1 ? RT_SHADE_FULL(0, 1) : matclass == 2 ? RT_SHADE_FULL(0, 2) : RT_SHADE_FULL(0, 0); break;
+            case 0: k = matclass == 1 ? RT_SHADE_FULL(0, 1) : matclass == 2 ? RT_SHADE_FULL_R(0, 2, false) : RT_SHADE_FULL(0, 0); break;
             case 1: k = RT_SHADE_FULL(1, 0); break;
-            case 16: k = matclass == 1 ? RT_SHADE_FULL(16, 1) : matclass == 2 ? RT_SHADE_FULL(16, 2) : RT_SHADE_FULL(16, 0); break;
+            case 16: k = matclass == 1 ? RT_SHADE_FULL(16, 1) : matclass == 2 ? RT_SHADE_FULL_R(16, 2, false) : RT_SHADE_FULL(16, 0); break;
             default: return hipErrorInvalidValue;
         }
 #undef RT_SHADE_FULL
+#undef RT_SHADE_FULL_R
         g_tl_launches[0][v >> 1].fetch_add(1, std::memory_order_relaxed);
         return launch_resident(k, gb, grid, st, sc, sp, smp, film, ids, io, nee);
     }
@@ -3384,9 +3436,12 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
     if (qcap != 1 && (!nee.fb_slot || !nee.fb_len)) return hipErrorInvalidValue;  // the fallback list is required
     void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
     const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);  // (as launch_path_shade)
-#define RT_NEE(Q) \
-    (v == 0 ? k_path_nee<Q, false> : v == 1 ? k_path_nee<Q, false, true> : v == 2 ? k_path_nee<Q, false, false, 1> \
-     : v == 3 ? k_path_nee<Q, false, true, 1> : v == 4 ? k_path_nee<Q, false, false, 2> : k_path_nee<Q, false, true, 2>)
+    const bool rg = (nee.ml & 4) != 0;  // (as launch_path_shade)
+#define RT_NEE_R(Q, R) \
+    (v == 0 ? k_path_nee<Q, false, false, 0, R> : v == 1 ? k_path_nee<Q, false, true, 0, R> \
+     : v == 2 ? k_path_nee<Q, false, false, 1, R> : v == 3 ? k_path_nee<Q, false, true, 1, R> \
+     : v == 4 ? k_path_nee<Q, false, false, 2, R> : k_path_nee<Q, false, true, 2, R>)
+#define RT_NEE(Q) (rg ? RT_NEE_R(Q, true) : RT_NEE_R(Q, false))
     switch (qcap) {
         case 0: k = RT_NEE(0); break;
         case 1: k = RT_NEE(1); break;
@@ -3394,6 +3449,7 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
         default: return hipErrorInvalidValue;
     }
 #undef RT_NEE
+#undef RT_NEE_R
     g_tl_launches[1][v >> 1].fetch_add(1, std::memory_order_relaxed);
     return launch_resident(k, gb, grid, st, sc, sp, io, nee, ctr);
 }
@@ -3404,15 +3460,19 @@ hipError_t launch_path_nee_fallback(hipStream_t st, int grid, int qcap, const De
     const int gb = ring_clamp(std::min(grid > 0 ? grid : 1, kFallbackBlocks), qcap, sc);
     void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
     const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);
-#define RT_NEE_FB(Q) \
-    (v == 0 ? k_path_nee<Q, true> : v == 1 ? k_path_nee<Q, true, true> : v == 2 ? k_path_nee<Q, true, false, 1> \
-     : v == 3 ? k_path_nee<Q, true, true, 1> : v == 4 ? k_path_nee<Q, true, false, 2> : k_path_nee<Q, true, true, 2>)
+    const bool rg = (nee.ml & 4) != 0;
+#define RT_NEE_FB_R(Q, R) \
+    (v == 0 ? k_path_nee<Q, true, false, 0, R> : v == 1 ? k_path_nee<Q, true, true, 0, R> \
+     : v == 2 ? k_path_nee<Q, true, false, 1, R> : v == 3 ? k_path_nee<Q, true, true, 1, R> \
+     : v == 4 ? k_path_nee<Q, true, false, 2, R> : k_path_nee<Q, true, true, 2, R>)
+#define RT_NEE_FB(Q) (rg ? RT_NEE_FB_R(Q, true) : RT_NEE_FB_R(Q, false))
     switch (qcap) {
         case 0: k = RT_NEE_FB(0); break;
         case 16: k = RT_NEE_FB(16); break;
         default: return hipErrorInvalidValue;
     }
 #undef RT_NEE_FB
+#undef RT_NEE_FB_R
     g_tl_launches[1][v >> 1].fetch_add(1, std::memory_order_relaxed);
     return launch_resident(k, gb, grid, st, sc, sp, io, nee, ctr);
 }

@@ -112,10 +112,17 @@ struct PassFacts {
     bool textures = false;
     bool mesh_light = false;
     bool environment = false;
+    bool rough = false;        // a non-emissive RT_MAT_ROUGH material (it also makes the scene full)
     PassIntegrator integ = kIntegReference;
     int max_depth = 0;
     int n_work = 0, ib = 0, ie = 0;
 };
+
+// The material bin of a material (DevMaterial cls, kMatClasses) by its rt_material type and whether it emits: 0 = the bin
+// that reads spectra and writes NEE records (an emitter, Lambert 0, rough 3), 1 = the specular bin (mirror 1, glass 2),
+// whose kernels hold no RGH code.  rough_fact: the material makes the scene's `rough` fact (an emitter of type 3 does not).
+inline int material_class(int type, bool emissive) { return emissive || type == 0 || type == 3 ? 0 : 1; }
+inline bool rough_fact(int type, bool emissive) { return type == 3 && !emissive; }
 
 // Batch sizing and scene flags, shared by the render pass and the feature pass.
 struct BatchPlan {
@@ -202,7 +209,10 @@ struct PathPlan {
     // mixed multi-level scenes: the trace kernel bins the hits by material class and each class is shaded by a kernel
     // holding only its materials' code (k_path_shade_full<Q, 1 / 2>)
     bool bins = false;
-    int ml = 0;                // NeeIO ml: bit 0 the scene has a mesh light, bit 1 an environment light
+    int ml = 0;                // NeeIO ml: bit 0 the scene has a mesh light, bit 1 an environment light, bit 2 = rgh
+    // a rough material: the RGH instantiations of k_path_shade_full (classes 0 and 1) and k_path_nee,
+    // whose NEE record is one float4 longer
+    bool rgh = false;
     bool env = false;          // an environment light is bound: every traced depth ends with the miss stage
     // slot state layout (rt_internal.h RecView): records for multi-level scenes (sorted, scattered slots), SoA for
     // single-leaf ones (slots stay in queue order)
@@ -253,7 +263,8 @@ inline PathPlan plan_path(const PassFacts& f, const Knobs& kn, const BatchPlan& 
     p.sort_nee = p.nee && p.sort_rays && kn.sort_nee;
     p.bins = p.nee && multi && kn.mat_bins;
     p.env = f.environment && b.path;
-    p.ml = (f.mesh_light ? 1 : 0) | (p.env ? 2 : 0);
+    p.rgh = f.rough && b.path;
+    p.ml = (f.mesh_light ? 1 : 0) | (p.env ? 2 : 0) | (p.rgh ? 4 : 0);
     p.records = multi;
     p.rec_fs = p.records ? 1 : b.nmax;
     p.rec_ss = p.records ? (unsigned)kRecF4 : 1u;

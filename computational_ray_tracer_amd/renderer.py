@@ -204,8 +204,48 @@ class Renderer:
         self._chk("rt_debug_env_stats", self.lib.rt_debug_env_stats(self.h, C.byref(ms), n))
         return dict(shade=np.array(n[0:3], np.int64), nee=np.array(n[3:6], np.int64))
 
+    # ---- rough reflector (capi.RT_MAT_ROUGH) ----------------------------------------------------
+    def ggx_sample(self, alpha, normal, dirs, u):
+        """rt_debug_ggx_sample: the shade kernel's rough bounce for shading-side normals normal (n, 3), incoming ray
+        directions dirs (n, 3) and the bounce's sample points u (n, 2) -> dict(disk (n, 2): the disk point used,
+        wi (n, 3): world space, wb (n), pdf (n); all 0 where there is no bounce)."""
+        nr = np.ascontiguousarray(normal, np.float32)
+        d = np.ascontiguousarray(dirs, np.float32)
+        u = np.ascontiguousarray(u, np.float32)
+        n = len(nr)
+        assert nr.shape == (n, 3) and d.shape == (n, 3) and u.shape == (n, 2)
+        disk, wi = np.zeros((n, 2), np.float32), np.zeros((n, 3), np.float32)
+        wb, pdf = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_ggx_sample", self.lib.rt_debug_ggx_sample(
+            self.h, float(alpha), n, nr.ctypes.data_as(F), d.ctypes.data_as(F), u.ctypes.data_as(F),
+            disk.ctypes.data_as(F), wi.ctypes.data_as(F), wb.ctypes.data_as(F), pdf.ctypes.data_as(F)))
+        return dict(disk=disk, wi=wi, wb=wb, pdf=pdf)
+
+    def ggx_eval(self, alpha, normal, dirs, wi):
+        """rt_debug_ggx_eval: the shade kernel's rough light term for normals (n, 3), incoming ray directions (n, 3) and
+        world-space light directions wi (n, 3) -> dict(fcos (n): f mu_i / R, pdf (n))."""
+        nr = np.ascontiguousarray(normal, np.float32)
+        d = np.ascontiguousarray(dirs, np.float32)
+        w = np.ascontiguousarray(wi, np.float32)
+        n = len(nr)
+        assert nr.shape == (n, 3) and d.shape == (n, 3) and w.shape == (n, 3)
+        fcos, pdf = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_ggx_eval", self.lib.rt_debug_ggx_eval(
+            self.h, float(alpha), n, nr.ctypes.data_as(F), d.ctypes.data_as(F), w.ctypes.data_as(F),
+            fcos.ctypes.data_as(F), pdf.ctypes.data_as(F)))
+        return dict(fcos=fcos, pdf=pdf)
+
+    def rough_launches(self):
+        """rt_debug_rough_stats: launches of the RGH instantiations of k_path_shade_full and k_path_nee by the last
+        path pass, summed (0 for a scene without a rough material)."""
+        n = (C.c_int64 * 2)()
+        self._chk("rt_debug_rough_stats", self.lib.rt_debug_rough_stats(self.h, n))
+        return int(n[0]) + int(n[1])
+
     def set_shard(self, tile_size, n_shards, shard_id):
-        self._chk("rt_set_shard", self.lib.rt_set_shard(self.h, tile_size, n_shards, shard_id))
+        self._chk("rt_set_shard",self.lib.rt_set_shard(self.h, tile_size, n_shards, shard_id))
 
     def new_film(self):
         return np.zeros((self.res[0] * self.res[1], 4), dtype=np.float32)

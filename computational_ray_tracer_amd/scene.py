@@ -570,6 +570,41 @@ def grey_sigmoid(g):
     return (0.0, 0.0, float((g - np.float32(0.5)) / np.sqrt(g * (np.float32(1) - g))))
 
 
+def rough(sigmoid, alpha):
+    """The material tuple of a rough GGX reflector (capi.RT_MAT_ROUGH): reflectance sigmoid (c0, c1, c2)
+    and roughness alpha in [0.01, 1], which travels in rt_material.eta (below 0.01 use RT_MAT_MIRROR)."""
+    return (tuple(sigmoid), 0.0, capi.RT_MAT_ROUGH, float(alpha))
+
+
+def ggx_eval(alpha, wo, wi):
+    """rt_ggx_eval (host only): local-frame wo, wi (n, 3) -> (fcos (n): f mu_i / R, pdf (n))."""
+    wo, wi = np.ascontiguousarray(wo, np.float32), np.ascontiguousarray(wi, np.float32)
+    n = len(wo)
+    assert wo.shape == (n, 3) and wi.shape == (n, 3)
+    fcos, pdf = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    F = C.POINTER(C.c_float)
+    r = capi.load_library().rt_ggx_eval(float(alpha), n, wo.ctypes.data_as(F), wi.ctypes.data_as(F),
+                                        fcos.ctypes.data_as(F), pdf.ctypes.data_as(F))
+    if r != capi.RT_OK:
+        raise capi.RTError("rt_ggx_eval", r, "alpha in [0.01, 1] and non-NULL pointers")
+    return fcos, pdf
+
+
+def ggx_sample(alpha, wo, disk):
+    """rt_ggx_sample (host only): local-frame wo (n, 3) and disk points (n, 2) -> (wi (n, 3), wb (n), pdf (n)), all 0
+    where there is no bounce."""
+    wo, disk = np.ascontiguousarray(wo, np.float32), np.ascontiguousarray(disk, np.float32)
+    n = len(wo)
+    assert wo.shape == (n, 3) and disk.shape == (n, 2)
+    wi, wb, pdf = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    F = C.POINTER(C.c_float)
+    r = capi.load_library().rt_ggx_sample(float(alpha), n, wo.ctypes.data_as(F), disk.ctypes.data_as(F),
+                                          wi.ctypes.data_as(F), wb.ctypes.data_as(F), pdf.ctypes.data_as(F))
+    if r != capi.RT_OK:
+        raise capi.RTError("rt_ggx_sample", r, "alpha in [0.01, 1] and non-NULL pointers")
+    return wi, wb, pdf
+
+
 def _flat_mesh(faces_xyz):
     """(nt, 3, 3) float64 corner positions -> one-vertex-per-corner float32 mesh with flat normals."""
     p = np.asarray(faces_xyz, dtype=np.float64)

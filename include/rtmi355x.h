@@ -59,12 +59,41 @@ typedef struct { float r, g, b, w; } rt_pixel;
  * sum = sum + v and sumsq = sumsq + v * v for every sample, in the film's index order (float32, nothing fused). */
 typedef struct { float sum, sumsq; } rt_moment;
 
-enum { RT_MAT_DIFFUSE = 0, RT_MAT_MIRROR = 1, RT_MAT_DIELECTRIC = 2 };
+enum { RT_MAT_DIFFUSE = 0, RT_MAT_MIRROR = 1, RT_MAT_DIELECTRIC = 2, RT_MAT_ROUGH = 3 };
 /* Build-defined material (the reference has none: Shading.h:1-21 is a comment stub).
  * DIFFUSE: Lambert R/π; MIRROR: perfect specular reflection scaled by R; R(λ) is an RGBSigmoidPolynomial
  *   (color.h:363-403): R(λ) = s(c0 λ² + c1 λ + c2).
  * DIELECTRIC: smooth Fresnel glass; eta > 0 is a constant IOR, eta == 0 selects the dispersive
  *   "glass-BK7" table (spectrum.cpp:2674-2691) with SampledWavelengths::TerminateSecondary (spectrum.h:302-310).
+ * ROUGH (additive): an isotropic, reflection-only GGX (Trowbridge-Reitz) microfacet reflector, MIRROR
+ *   spread into a lobe.  The roughness alpha travels in `eta` (rt_scene_upload: RT_E_ARG unless it is finite and in
+ *   [0.01, 1]; below 0.01 the caller wants RT_MAT_MIRROR; an emissive material's eta is not read).  float32 in the order
+ *   written, nothing fused; vectors local to the pbrt CoordinateSystem frame (ss, tt, n) of the shading-side normal n
+ *   (v_local = (v.ss, v.tt, v.n), glm dots), wo = -ray direction, mu_o = wo.z; a = alpha, a2 = a a:
+ *     D(h)      = 1 / ((pi a2) (t t)),  t = (h.x h.x + h.y h.y) / a2 + h.z h.z   (= a2 / (pi (h.z^2 (a2 - 1) + 1)^2) for a
+ *                 unit h; the form that does not cancel at alpha = 0.01)
+ *     Lambda(w) = (sqrtf(1 + (a2 (1 - w.z w.z)) / (w.z w.z)) - 1) / 2,  G1(w) = 1 / (1 + Lambda(w)),
+ *     G2        = 1 / ((1 + Lambda(wo)) + Lambda(wi))   (height-correlated)
+ *     f(wo, wi) = R(lambda) D(h) G2 / (4 mu_o mu_i), h = normalize(wo + wi), 0 when mu_i <= 0 or mu_o <= 0.  The "Fresnel"
+ *                 term is the material's (or its texel's) sigmoid R(lambda) at every angle, as MIRROR is reflection
+ *                 scaled by R: f is R(lambda) times one scalar fcos / mu_i, fcos = (D G2) / (4 mu_o).
+ *     sampling: Heitz's visible normals as pbrt-v4 TrowbridgeReitzDistribution::Sample_wm on the disk point (dx, dy) =
+ *       disk_concentric(u0, u1) of the vertex's bounce Get2D:
+ *       wh = normalize(a wo.x, a wo.y, wo.z); T1 = wh.z < 0.99999f ? normalize(cross((0, 0, 1), wh)) : (1, 0, 0);
+ *       T2 = cross(wh, T1); hh = sqrtf(1 - dx dx); s = (1 + wh.z) / 2; dy' = (1 - s) hh + s dy;
+ *       pz = sqrtf(max(0, (1 - dx dx) - dy' dy')); nh = (T1 dx + T2 dy') + wh pz;
+ *       h = normalize(a nh.x, a nh.y, max(1e-6f, nh.z)); wi = (2 (wo.h)) h - wo;
+ *       pdf(wo, wi) = (G1(wo) D(h)) / (4 mu_o); the bounce weight f mu_i / pdf = R(lambda) wb, wb = G2 / G1(wo) in [0, 1];
+ *       wi.z <= 0 or mu_o <= 0: no bounce, the path ends (single-scattering GGX loses that energy: 20 % of the samples
+ *       at alpha 0.5 and normal incidence).
+ *   In the path integrators a rough vertex draws what a Lambert vertex draws, in the same order (one Get2D per light,
+ *   one for the bounce); its light terms hold f mu_i where Lambert's hold (R / pi) cos, for every kind of light, and its
+ *   MIS weights pdf(wo, wi) where Lambert's hold cos / pi; the bounce multiplies beta by R(lambda) wb and hands
+ *   pdf(wo, wi) to the next emitter hit or environment miss.  An albedo texture supplies R as for Lambert.
+ *   RT_INTEGRATOR_REFERENCE never sees materials; the feature, position and chain passes end a chain on a rough surface,
+ *   as on a Lambert one; rt_render_features_albedo demodulates it by A of its material or texel, as Lambert (exact: f
+ *   is R(lambda) times a scalar).  Limits: no transmission, no anisotropy, no Schlick or conductor Fresnel (the grazing
+ *   rise would need a second scalar per light and per bounce), no multiple-scattering compensation, no roughness textures.
  * emission_scale > 0 makes the surface a pure one-sided emitter with Le = scale · stdillum-D65. */
 typedef struct {
     int type;
@@ -607,6 +636,25 @@ int rt_debug_env_eval(rt_ctx* ctx, int n, const float* dir, int32_t* texel, floa
  * non-NULL, 6 counts since the process started: launches of k_path_shade_full without tabled lights, with mesh lights
  * (TL = 1), with the environment (TL = 2), then the same three for k_path_nee. */
 int rt_debug_env_stats(rt_ctx* ctx, double* ms_miss, int64_t* launches);
+
+/* ---- rough reflector (additive): RT_MAT_ROUGH above ------------------------------------
+ * The material's own functions on n local-frame vector pairs (host only, no context, like rt_env_texel): wo, wi 3n
+ * floats each.  eval: fcos[i] = f mu_i / R = (D G2) / (4 mu_o) and pdf[i] = pdf(wo, wi), both 0 when wo.z <= 0 or
+ * wi.z <= 0.  sample: disk 2n floats, the disk point (dx, dy); wi (3n), wb (n), pdf (n), all 0 where there is no bounce.
+ * RT_E_ARG: a NULL pointer with n > 0, n < 0, alpha not in [0.01, 1]. */
+int rt_ggx_eval(float alpha, int n, const float* wo, const float* wi, float* fcos, float* pdf);
+int rt_ggx_sample(float alpha, int n, const float* wo, const float* disk, float* wi, float* wb, float* pdf);
+/* The path kernels' own device functions, one item per thread, on world-space vectors: normal (3n) the shading-side
+ * normal (unit), dir (3n) the incoming ray's unit direction (wo = -dir), the frame built as the shade kernel builds it.
+ * sample: u (2n) the bounce's Get2D -> disk_out (2n) the disk point used, wi (3n, world space), wb, pdf (n).
+ * eval: wi (3n, world space) -> fcos, pdf (n). */
+int rt_debug_ggx_sample(rt_ctx* ctx, float alpha, int n, const float* normal, const float* dir, const float* u,
+                        float* disk_out, float* wi, float* wb, float* pdf);
+int rt_debug_ggx_eval(rt_ctx* ctx, float alpha, int n, const float* normal, const float* dir, const float* wi,
+                      float* fcos, float* pdf);
+/* launches[2]: launches of the RGH instantiations of k_path_shade_full and of k_path_nee (the fallback included) by the
+ * context's last path pass (0, 0 for a scene without a rough material). */
+int rt_debug_rough_stats(rt_ctx* ctx, int64_t* launches);
 
 /* ---- albedo demodulation for the denoiser (additive) ------------------------------
  * The filter divides the film by a noise-free first-hit albedo, filters the demodulated irradiance (smooth across the

@@ -1,0 +1,612 @@
+"""The rough reflector (capi.RT_MAT_ROUGH) restated twice, independently of the library.
+
+Part 1, numpy float32, one operation per C operation of csrc/rt_ggx.h: the frame, D, Lambda, ggx_eval, ggx_sample_disk,
+the substitutions a rough vertex makes in the light weights of k_path_shade_full and the throughput k_path_nee forms.
+The library's rt_ggx_eval / rt_ggx_sample and the device's rt_debug_ggx_* must give these bits.
+
+Part 2, float64, what the arithmetic means: f and the pdf from the issue's own formulas (D in its alpha^2 / (pi (h.z^2
+(alpha^2 - 1) + 1)^2) form, which part 1 does not use), visible-normal sampling, the directional albedo E(mu_o, alpha)
+by hemisphere quadrature doubled until its Richardson value moves by less than 1e-9, and the closed forms of the film
+cases G1, G2, G3, G3m, G4, G5 and G6 of tests/test_gpu_rough.py.
+
+Reads only the committed tables (through radiometry_reference) and the descriptors.
+"""
+import functools
+import math
+
+import numpy as np
+
+import envlight_reference as env
+import radiometry_reference as ref
+from computational_ray_tracer_amd import capi, scene
+
+f32 = np.float32
+ALPHA_MIN, ALPHA_MAX = 0.01, 1.0
+PI32 = f32(3.14159265358979323846)
+
+# Largest relative error of part 1 (float32) against part 2 (float64) over the inputs of
+# tests/test_rough_reference.py::reference_inputs (seed 7, 2000 inputs for each alpha of ALPHAS), measured on the CPU,
+# never from GPU output.  fcos, pdf: ggx_eval; wb, spdf: ggx_sample_disk's weight and pdf from the same disk point; wi:
+# the largest absolute component error of the sampled direction.  alpha = 0.01 sets fcos, pdf, spdf and wi (the tilt of
+# h is divided by alpha: D is that sensitive to it); wb's worst is a bounce 4e-3 above the horizon at alpha = 0.5.
+MEASURED = dict(fcos=8.54e-5, pdf=8.53e-5, wb=7.73e-5, spdf=1.24e-4, wi=2.19e-5)
+FACTOR = 2.0
+ALPHAS = (0.01, 0.05, 0.2, 0.5, 1.0)
+TINY_PDF = 1e-30            # float64 pdfs below this are compared absolutely
+
+
+def bounds():
+    return {k: FACTOR * v for k, v in MEASURED.items()}
+
+
+# ------------------------------------------------------------------------------------------- part 1: float32
+
+
+def _v(a):
+    a = np.asarray(a, f32)
+    assert a.dtype == f32 and a.shape[-1] == 3
+    return a
+
+
+def dot32(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def norm32(v):
+    s = f32(1) / np.sqrt(dot32(v, v))
+    return v * s[..., None]
+
+
+def cross32(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - b[..., 1] * a[..., 2], a[..., 2] * b[..., 0] - b[..., 2] * a[..., 0],
+                     a[..., 0] * b[..., 1] - b[..., 0] * a[..., 1]], -1)
+
+
+def frame32(n):
+    """ggx_frame: pbrt's CoordinateSystem of the shading-side normal, cosine_bounce's operations."""
+    n = _v(n)
+    sign = np.copysign(f32(1), n[..., 2])
+    a = f32(-1) / (sign + n[..., 2])
+    b = n[..., 0] * n[..., 1] * a
+    ss = np.stack([f32(1) + sign * (n[..., 0] * n[..., 0]) * a, sign * b, -sign * n[..., 0]], -1)
+    tt = np.stack([b, sign + (n[..., 1] * n[..., 1]) * a, -n[..., 1]], -1)
+    return ss, tt
+
+
+def to_local32(v, ss, tt, n):
+    return np.stack([dot32(v, ss), dot32(v, tt), dot32(v, n)], -1)
+
+
+def to_world32(l, ss, tt, n):
+    return np.stack([(ss[..., k] * l[..., 0] + tt[..., k] * l[..., 1]) + n[..., k] * l[..., 2] for k in range(3)], -1)
+
+
+def D32(a2, h, alpha_for_a2=False):
+    """alpha_for_a2: the sabotaged variant with alpha where alpha^2 belongs."""
+    t = (h[..., 0] * h[..., 0] + h[..., 1] * h[..., 1]) / a2 + h[..., 2] * h[..., 2]
+    return f32(1) / ((PI32 * a2) * (t * t))
+
+
+def lambda32(a2, w):
+    z2 = w[..., 2] * w[..., 2]
+    return (np.sqrt(f32(1) + (a2 * (f32(1) - z2)) / z2) - f32(1)) / f32(2)
+
+
+def eval32(alpha, wo, wi):
+    """ggx_eval: (fcos = f mu_i / R, pdf), both 0 when wo.z <= 0 or wi.z <= 0."""
+    wo, wi = _v(wo), _v(wi)
+    a = f32(alpha)
+    a2 = a * a
+    with np.errstate(all="ignore"):
+        ok = (wo[..., 2] > 0) & (wi[..., 2] > 0)
+        h = norm32(wo + wi)
+        D = D32(a2, h)
+        lo = f32(1) + lambda32(a2, wo)
+        G2, G1 = f32(1) / (lo + lambda32(a2, wi)), f32(1) / lo
+        d4 = f32(4) * wo[..., 2]
+        fcos, pdf = (D * G2) / d4, (G1 * D) / d4
+    return np.where(ok, fcos, f32(0)), np.where(ok, pdf, f32(0))
+
+
+def sample32(alpha, wo, disk):
+    """ggx_sample_disk: (wi, wb, pdf, bounced); the outputs are 0 where there is no bounce."""
+    wo, disk = _v(wo), np.asarray(disk, f32)
+    assert disk.dtype == f32 and disk.shape == wo.shape[:-1] + (2,)
+    a = f32(alpha)
+    a2 = a * a
+    dx, dy = disk[..., 0], disk[..., 1]
+    with np.errstate(all="ignore"):
+        wh = norm32(np.stack([a * wo[..., 0], a * wo[..., 1], wo[..., 2]], -1))
+        z = np.broadcast_to(np.array([0, 0, 1], f32), wh.shape)
+        T1 = np.where((wh[..., 2] < f32(0.99999))[..., None], norm32(cross32(z, wh)), np.array([1, 0, 0], f32))
+        T2 = cross32(wh, T1)
+        c2 = f32(1) - dx * dx
+        hh = np.sqrt(c2)
+        s = (f32(1) + wh[..., 2]) / f32(2)
+        dy = (f32(1) - s) * hh + s * dy
+        pz = c2 - dy * dy
+        pz = np.sqrt(np.where(pz > 0, pz, f32(0)))
+        nh = np.stack([(T1[..., k] * dx + T2[..., k] * dy) + wh[..., k] * pz for k in range(3)], -1)
+        h = norm32(np.stack([a * nh[..., 0], a * nh[..., 1], np.where(nh[..., 2] > f32(1e-6), nh[..., 2], f32(1e-6))], -1))
+        d2 = f32(2) * dot32(wo, h)
+        w = d2[..., None] * h - wo
+        ok = (wo[..., 2] > 0) & (w[..., 2] > 0)
+        D = D32(a2, h)
+        lo = f32(1) + lambda32(a2, wo)
+        G2, G1 = f32(1) / (lo + lambda32(a2, w)), f32(1) / lo
+        pdf = (G1 * D) / (f32(4) * wo[..., 2])
+        wb = G2 / G1
+    z1 = f32(0)
+    return np.where(ok[..., None], w, z1), np.where(ok, wb, z1), np.where(ok, pdf, z1), ok
+
+
+def debug_sample32(alpha, normal, dirs, disk):
+    """rt_debug_ggx_sample from the disk point on: the shade kernel's frame, local wo, bounce, world wi."""
+    n, d = _v(normal), _v(dirs)
+    ss, tt = frame32(n)
+    wol = to_local32(-d, ss, tt, n)
+    wil, wb, pdf, ok = sample32(alpha, wol, disk)
+    return np.where(ok[..., None], to_world32(wil, ss, tt, n), f32(0)), wb, pdf, ok
+
+
+def debug_eval32(alpha, normal, dirs, wi):
+    n, d, wi = _v(normal), _v(dirs), _v(wi)
+    ss, tt = frame32(n)
+    return eval32(alpha, to_local32(-d, ss, tt, n), to_local32(wi, ss, tt, n))
+
+
+def power_heuristic32(f, g):
+    """rt_device.h power_heuristic: f f / (f f + g g), 1 for an infinite f."""
+    f, g = np.asarray(f, f32), np.asarray(g, f32)
+    with np.errstate(all="ignore"):
+        return np.where(np.isinf(f), f32(1), (f * f) / (f * f + g * g))
+
+
+def light_weight32(kind, fc, bpdf, cl=None, dist2=None, area=None, pdf_env=None, mis=False):
+    """The weight k_path_shade_full stores for one light at a rough vertex: Lambert's with fc = fcos for cs and bpdf =
+    the GGX pdf for cs / pi.  kind: 'area' (quad, disk, mesh), 'point', 'distant', 'env'."""
+    fc, bpdf = np.asarray(fc, f32), np.asarray(bpdf, f32)
+    if kind == "env":
+        w = fc / pdf_env
+        return w * power_heuristic32(pdf_env, bpdf) if mis else w
+    if kind == "area":
+        w = ((fc * cl) / dist2) * area
+        return w * power_heuristic32(dist2 / (cl * area), bpdf) if mis else w
+    return fc * (f32(1) / dist2) if kind == "point" else fc * f32(1)
+
+
+def nee_term32(beta, R, Le, wgt):
+    """k_path_nee<.., RGH> at a rough vertex: x = beta R (no 1 / pi), L += (x Le) wgt."""
+    return ((np.asarray(beta, f32) * np.asarray(R, f32)) * np.asarray(Le, f32)) * np.asarray(wgt, f32)
+
+
+def bounce_beta32(beta, R, wb):
+    """The throughput after a rough bounce: beta (R wb)."""
+    return np.asarray(beta, f32) * (np.asarray(R, f32) * np.asarray(wb, f32))
+
+
+# ------------------------------------------------------------------------------------------- part 2: float64
+
+
+def nrm64(v):
+    v = np.asarray(v, np.float64)
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def lam64(muz, a):
+    c2 = np.asarray(muz, np.float64) ** 2
+    with np.errstate(all="ignore"):
+        return (np.sqrt(1 + a * a * (1 - c2) / c2) - 1) / 2
+
+
+def D64(hz, a, alpha_for_alpha2=False):
+    k = a if alpha_for_alpha2 else a * a
+    return k / (math.pi * (np.asarray(hz, np.float64) ** 2 * (k - 1) + 1) ** 2)
+
+
+def G2_64(muo, mui, a, separable=False):
+    if separable:
+        return 1 / ((1 + lam64(muo, a)) * (1 + lam64(mui, a)))
+    return 1 / (1 + lam64(muo, a) + lam64(mui, a))
+
+
+def f_cos64(a, wo, wi, separable=False, alpha_for_alpha2=False, no_4mu=False):
+    """f mu_i / R = D G2 / (4 mu_o) for unit local wo, wi (0 below the horizon)."""
+    wo, wi = np.asarray(wo, np.float64), np.asarray(wi, np.float64)
+    ok = (wo[..., 2] > 0) & (wi[..., 2] > 0)
+    with np.errstate(all="ignore"):
+        h = nrm64(wo + wi)
+        v = D64(h[..., 2], a, alpha_for_alpha2) * G2_64(wo[..., 2], wi[..., 2], a, separable)
+        v = v if no_4mu else v / (4 * wo[..., 2])
+    return np.where(ok, v, 0.0)
+
+
+def f64(a, wo, wi, **kw):
+    """The BSDF over R: D G2 / (4 mu_o mu_i)."""
+    with np.errstate(all="ignore"):
+        return np.where(np.asarray(wi)[..., 2] > 0, f_cos64(a, wo, wi, **kw) / np.asarray(wi, np.float64)[..., 2], 0.0)
+
+
+def pdf_h64(a, wo, h, no_g1=False, no_4mu=False, alpha_for_alpha2=False):
+    """pdf(wo, wi) from the half vector: G1(wo) D(h) / (4 mu_o)."""
+    g1 = 1.0 if no_g1 else 1 / (1 + lam64(wo[..., 2], a))
+    v = g1 * D64(h[..., 2], a, alpha_for_alpha2)
+    return v if no_4mu else v / (4 * wo[..., 2])
+
+
+def pdf64(a, wo, wi, **kw):
+    wo, wi = np.asarray(wo, np.float64), np.asarray(wi, np.float64)
+    ok = (wo[..., 2] > 0) & (wi[..., 2] > 0)
+    with np.errstate(all="ignore"):
+        return np.where(ok, pdf_h64(a, wo, nrm64(wo + wi), **kw), 0.0)
+
+
+def disk64(u):
+    """Shirley's concentric map (camera_reference.concentric_disk states the same thing)."""
+    u = np.asarray(u, np.float64)
+    ox, oy = 2 * u[..., 0] - 1, 2 * u[..., 1] - 1
+    wide = np.abs(ox) > np.abs(oy)
+    with np.errstate(all="ignore"):
+        r = np.where(wide, ox, oy)
+        th = np.where(wide, (math.pi / 4) * (oy / ox), math.pi / 2 - (math.pi / 4) * (ox / oy))
+    th = np.where((ox == 0) & (oy == 0), 0.0, th)
+    return np.stack([r * np.cos(th), r * np.sin(th)], -1)
+
+
+def sample64(a, wo, disk, wb_is_g2=False):
+    """Visible-normal sampling from a disk point: (wi, h, wb, pdf, up); wb and pdf are 0 where wi.z <= 0."""
+    wo, disk = np.asarray(wo, np.float64), np.asarray(disk, np.float64)
+    wo = np.broadcast_to(wo, disk.shape[:-1] + (3,))
+    wh = nrm64(np.stack([a * wo[..., 0], a * wo[..., 1], wo[..., 2]], -1))
+    z = np.broadcast_to(np.array([0.0, 0.0, 1.0]), wh.shape)
+    with np.errstate(all="ignore"):
+        T1 = np.where(wh[..., 2:3] < 0.99999, nrm64(np.cross(z, wh)), np.array([1.0, 0.0, 0.0]))
+    T2 = np.cross(wh, T1)
+    dx, dy = disk[..., 0], disk[..., 1]
+    hh = np.sqrt(np.maximum(0.0, 1 - dx * dx))
+    s = (1 + wh[..., 2]) / 2
+    dy = (1 - s) * hh + s * dy
+    pz = np.sqrt(np.maximum(0.0, 1 - dx * dx - dy * dy))
+    nh = dx[..., None] * T1 + dy[..., None] * T2 + pz[..., None] * wh
+    h = nrm64(np.stack([a * nh[..., 0], a * nh[..., 1], np.maximum(1e-6, nh[..., 2])], -1))
+    wi = 2 * np.sum(wo * h, -1, keepdims=True) * h - wo
+    up = (wi[..., 2] > 0) & (wo[..., 2] > 0)
+    with np.errstate(all="ignore"):
+        g2 = G2_64(wo[..., 2], wi[..., 2], a)
+        wb = g2 if wb_is_g2 else g2 * (1 + lam64(wo[..., 2], a))
+        pdf = pdf_h64(a, wo, h)
+    return wi, h, np.where(up, wb, 0.0), np.where(up, pdf, 0.0), up
+
+
+def wo_of(mu):
+    return np.array([math.sqrt(max(0.0, 1 - mu * mu)), 0.0, mu])
+
+
+def _albedo_rule(a, mu, n, **kw):
+    """Midpoint rule of f mu_i over the hemisphere in (cos theta, phi), n x n cells over phi in [0, pi] (the integrand is
+    even in phi about wo's azimuth)."""
+    ct = (np.arange(n) + 0.5) / n
+    ph = (np.arange(n) + 0.5) / n * math.pi
+    CT, PH = np.meshgrid(ct, ph, indexing="ij")
+    st = np.sqrt(1 - CT * CT)
+    wi = np.stack([st * np.cos(PH), st * np.sin(PH), CT], -1)
+    return 2.0 * np.sum(f_cos64(a, wo_of(mu), wi, **kw)) * (1.0 / n) * (math.pi / n)
+
+
+def albedo(a, mu, rel=1e-9, n0=32, nmax=4096, **kw):
+    """E(mu_o, alpha) = the hemisphere integral of D G2 / (4 mu_o): the midpoint rule doubled until its Richardson
+    value (4 I_2n - I_n) / 3 moves by less than `rel`."""
+    n, prev, rich = n0, _albedo_rule(a, mu, n0, **kw), None
+    while n < nmax:
+        cur = _albedo_rule(a, mu, 2 * n, **kw)
+        r = (4 * cur - prev) / 3
+        if rich is not None and abs(r - rich) < rel * max(abs(r), 1e-300):
+            return r
+        n, prev, rich = 2 * n, cur, r
+    raise AssertionError(f"albedo({a}, {mu}) did not converge to {rel}")
+
+
+CHEB_DEG = 24
+MU_MIN = 0.05               # the table's domain is [MU_MIN, 1]: towards mu_o = 0 the lobe hugs the horizon and the rule stalls
+
+
+@functools.lru_cache(maxsize=None)
+def albedo_table(a):
+    """E(., alpha) on [MU_MIN, 1] as a Chebyshev interpolant through albedo() at CHEB_DEG + 1 nodes (E is analytic in
+    mu_o: 4 mu_o Lambda(wo) = 2 (sqrt(mu^2 + alpha^2 (1 - mu^2)) - mu)); tests compare it with albedo() between the nodes."""
+    return np.polynomial.chebyshev.Chebyshev.interpolate(lambda t: np.array([albedo(a, x) for x in t]), CHEB_DEG,
+                                                         domain=[MU_MIN, 1.0])
+
+
+def albedo_at(a, mu):
+    mu = np.asarray(mu, np.float64)
+    assert np.all((mu >= MU_MIN) & (mu <= 1.0))
+    return albedo_table(a)(mu)
+
+
+# ------------------------------------------------------------------------------------------- film cases
+
+
+def fcos_sup(a):
+    """sup of f mu_i / R over all directions: D <= 1 / (pi alpha^2), G2 <= G1(wo) and G1(mu) / mu = 2 / (mu + sqrt(mu^2
+    + alpha^2 (1 - mu^2))) <= 2 / alpha, so f mu_i / R <= 1 / (2 pi alpha^3)."""
+    return 1 / (2 * math.pi * a ** 3)
+
+
+def finish(name, cfg, mu, vmax, include, spp):
+    """radiometry_reference._finish's preconditions; instead of its 2 % power bound, the power the +-3 % rejections
+    need: the whole-frame tolerance stays below 3 % of the mean."""
+    vmax = np.asarray(vmax, np.float64)
+    assert mu.shape == (cfg.film.res[0] * cfg.film.res[1], 3) and np.all(np.isfinite(mu)) and np.all(mu >= 0)
+    assert np.all(vmax < 1.0), f"{name}: a sample can clamp, vmax {vmax}"
+    assert np.all(mu[include] <= vmax[None, :]), f"{name}: vmax is no bound of mu"
+    assert 1.0 - include.mean() <= ref.EXCLUDED_MAX, f"{name}: too many pixels excluded"
+    power = ref.tolerance(mu[include], vmax, spp) / mu[include].mean(axis=0)
+    assert np.all(power < 0.03), f"{name}: whole-frame tolerance {power} of the mean"
+    assert cfg.index_end - cfg.index_begin == spp == cfg.sampler.spp()
+    return cfg, mu, vmax, include
+
+
+UP = np.array([0.0, 1.0, 0.0])
+G6_BYTE = 128
+
+
+def _floor_fcos(cfg, a, wi_world, offsets):
+    """f mu_i / R at the floor points of every pixel's sub-samples for one world direction towards the light: the floor's
+    normal is +y, the BSDF isotropic, so only mu_o, mu_i and h.n enter."""
+    o, w = ref.camera_rays(cfg, offsets)
+    wo = -w
+    wi = nrm64(wi_world)
+    h = nrm64(wo + wi)
+    muo, mui = wo[..., 1], wi[1]
+    return D64(h[..., 1], a) * G2_64(muo, mui, a) / (4 * muo)
+
+
+def g1_distant(alpha, tessellated=False, spp=256, albedo_c=None, sensor="xyz", texture=False, target=0.5):
+    """G1 (G5 with albedo_c and a sensor, G6 with a one-texel texture): K2's distant light over the rough floor at PATH
+    depth 1.  L = E R fcos(wo, wi) per floor point; the irradiance E is scaled so that vmax = `target`, with fcos
+    bounded by its largest value on every footprint's lattice times 1.05 (fcos varies by less than 5 % across a quarter
+    pixel: its logarithmic derivative along the floor is below 0.05 per pixel at alpha >= 0.2)."""
+    d = ref.K2_DIR
+    film = ref._film(sensor)
+    rho_c = scene.grey_sigmoid(ref.RHO) if albedo_c is None else albedo_c
+    probe = ref._config("g1", ref._floor_model(tessellated), ref._down_camera(), spp, capi.RT_INTEGRATOR_PATH, 1, film=film)
+    w, m8 = ref._per_rho(film, albedo_c)                       # response and sample maximum of D65 rho, over RHO
+    fc_lat = _floor_fcos(probe, alpha, d, ref._lattice())
+    fc_max = 1.05 * fc_lat.max()
+    e = float(f32(target / (ref.RHO * fc_max * m8.max())))
+    lights = [dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)]
+    floor_mat = scene.rough(scene.grey_sigmoid(0.25) if texture else rho_c, alpha)   # (a texture overrides the sigmoid)
+    model = ref._floor_model(tessellated, lights=lights)
+    model.materials[0] = floor_mat
+    rho = ref.RHO
+    if texture:      # one grey texel over the whole floor: R = 128 / 255 at every wavelength (the uniform branch)
+        model.texcoords = np.full((len(model.positions), 2), 0.5, f32)
+        model.textures = [scene.Texture(np.full((1, 1, 3), G6_BYTE, np.uint8), wrap="clamp")]
+        model.material_texture = [0] + [-1] * (len(model.materials) - 1)
+        rho = float(f32(G6_BYTE) / f32(255))
+    cfg = ref._config("g1_distant", model, ref._down_camera(), spp, capi.RT_INTEGRATOR_PATH, 1, film=film)
+    k = rho * e * _floor_fcos(cfg, alpha, d, ref._midpoints()).mean(axis=1)
+    mu = k[:, None] * w[None, :]
+    vmax = rho * e * fc_max * m8
+    return finish("g1_distant", cfg, mu, vmax, np.ones(len(mu), bool), spp)
+
+
+def quad_fcos_integral(a, x, wo, p, e1, e2, nl, rel=1e-6, orders=(8, 12, 16, 24, 32, 48)):
+    """The integral over the quad p + s e1 + t e2 of fcos(wo, wi) cos_l / d^2 dA for floor points x (k, 3) with unit
+    wo (k, 3), normal +y: tensor Gauss-Legendre rules of rising order until two in a row agree within `rel` at every
+    point (the integrand is smooth: the light's front faces every floor point and alpha is not small)."""
+    area = np.linalg.norm(np.cross(e1, e2))
+
+    def rule(n):
+        t, wt = np.polynomial.legendre.leggauss(n)
+        g, wt = 0.5 * (t + 1), 0.5 * wt
+        q = (p[None, None] + g[:, None, None] * e1[None, None] + g[None, :, None] * e2[None, None]).reshape(-1, 3)
+        ww = (wt[:, None] * wt[None, :]).reshape(-1)
+        out = np.empty(len(x))
+        for c0 in range(0, len(x), 4096):
+            xs, wos = x[c0:c0 + 4096], wo[c0:c0 + 4096]
+            v = q[None] - xs[:, None, :]
+            d2 = np.sum(v * v, -1)
+            wi = v / np.sqrt(d2)[..., None]
+            cl = np.maximum(-(wi @ nl), 0.0)
+            h = nrm64(wos[:, None, :] + wi)
+            muo, mui = wos[:, None, 1], wi[..., 1]
+            with np.errstate(all="ignore"):
+                fc = np.where(mui > 0, D64(h[..., 1], a) * G2_64(muo, mui, a) / (4 * muo), 0.0)
+            out[c0:c0 + 4096] = (fc * cl / d2) @ ww * area
+        return out
+    prev = rule(orders[0])
+    for n in orders[1:]:
+        cur = rule(n)
+        if np.all(np.abs(cur - prev) <= rel * np.abs(cur)):
+            return cur
+        prev = cur
+    raise AssertionError("quad integral did not converge")
+
+
+def _quad_sups(a, cfg, p, e1, e2, nl, n=33, slack=1.1):
+    """(sup of fcos cos_l A / d^2, sup of pdf(wo, wi)) over the seen floor rectangle and the quad, on an n x n lattice
+    of each (edges and corners included) times `slack`: both are smooth with their maxima interior or on an edge, and
+    neighbouring lattice points differ by a few per cent (400 / 32 floor units at 450 or more from the light against a
+    lobe of width alpha = 0.3)."""
+    x0, x1, z0, z1 = ref._view_box(cfg)
+    eye = np.asarray(cfg.camera.position, np.float64)
+    gx, gz = np.meshgrid(np.linspace(x0, x1, n), np.linspace(z0, z1, n), indexing="ij")
+    x = np.stack([gx, 0 * gx, gz], -1).reshape(-1, 1, 3)
+    wo = nrm64(eye[None, None] - x)
+    g = np.linspace(0, 1, n)
+    q = (p[None, None] + g[:, None, None] * e1[None, None] + g[None, :, None] * e2[None, None]).reshape(1, -1, 3)
+    v = q - x
+    d2 = np.sum(v * v, -1)
+    wi = v / np.sqrt(d2)[..., None]
+    cl = np.maximum(-(wi @ nl), 0.0)
+    h = nrm64(wo + wi)
+    D = D64(h[..., 1], a)
+    fc = D * G2_64(wo[..., 1], wi[..., 1], a) / (4 * wo[..., 1])
+    pb = D / (1 + lam64(wo[..., 1], a)) / (4 * wo[..., 1])
+    area = np.linalg.norm(np.cross(e1, e2))
+    return slack * float(np.max(fc * cl * area / d2)), slack * float(pb.max())
+
+
+def g2_quad(alpha=0.3, mis=False, spp=256, target=0.5):
+    """G2: K3's quad light over the rough floor at depth 1, PATH and PATH_MIS.  mu = R Le times the quad integral of
+    f mu_i G at each sub-sample's floor point.  One sample's value: the NEE term is at most R Le g, g = sup(fcos cos_l
+    A / d^2) (its MIS weight is <= 1); under PATH_MIS a bounce that hits the light adds R wb Le w_b with wb <= 1 and
+    w_b = p_b^2 / (p_b^2 + p_l^2) <= P^2 / (P^2 + p_lmin^2), P = sup pdf(wo, wi) towards the light and p_lmin =
+    d_min^2 / A (cos_l <= 1).  The emission is scaled so that vmax = target."""
+    base = ref.k3_quad(mis=mis, max_depth=1, spp=spp)[0]
+    lt = base.model.lights[0]
+    p, e1, e2, nl = (np.array(lt[k], np.float64) for k in ("p", "e1", "e2", "n"))
+    film = ref._film()
+    w, m8 = ref._per_rho(film, None)
+    area = np.linalg.norm(np.cross(e1, e2))
+    g_sup, p_sup = _quad_sups(alpha, base, p, e1, e2, nl)
+    p_lmin = ref.QUAD_H ** 2 / area
+    geo_sup = g_sup + (p_sup ** 2 / (p_sup ** 2 + p_lmin ** 2) if mis else 0.0)
+    emit = float(f32(target / (ref.RHO * geo_sup * m8.max())))
+    model = base.model
+    mats = list(model.materials)
+    mats[0] = scene.rough(scene.grey_sigmoid(ref.RHO), alpha)
+    em = lt["material"]
+    mats[em] = (mats[em][0], emit) + tuple(mats[em][2:])
+    model.materials = mats
+    kind = capi.RT_INTEGRATOR_PATH_MIS if mis else capi.RT_INTEGRATOR_PATH
+    cfg = ref._config("g2_quad", model, base.camera, spp, kind, 1, film=film)
+    o, wdir = ref.camera_rays(cfg, ref._midpoints(2))
+    xs = ref._floor_points(cfg, ref._midpoints(2))
+    npx, k = xs.shape[:2]
+    integ = quad_fcos_integral(alpha, xs.reshape(-1, 3), (-wdir).reshape(-1, 3), p, e1, e2, nl).reshape(npx, k).mean(axis=1)
+    mu = (ref.RHO * emit * integ)[:, None] * w[None, :]
+    vmax = ref.RHO * emit * geo_sup * m8
+    return finish("g2_quad", cfg, mu, vmax, np.ones(npx, bool), spp)
+
+
+G3_R, G3_ALPHA = 0.9, 0.5
+
+
+def _sphere_pixels(cfg):
+    """E4's silhouette rule for the sphere of radius FURNACE_R at the origin: (on: every lattice ray hits it; include:
+    on, or no lattice ray hits it, without the pixels of `on` whose mu_o falls below the albedo table's domain; mu_o of
+    the sub-samples' float64 hits, 1 where the pixel is not compared on the sphere)."""
+    o, d = ref.camera_rays(cfg, ref._lattice())
+    bq = d @ o
+    disc = bq * bq - (o @ o - ref.FURNACE_R ** 2)
+    hit = disc > 0
+    on = np.all(hit, axis=1)
+    include = on | ~np.any(hit, axis=1)
+    o, d = ref.camera_rays(cfg, ref._midpoints())
+    bq = d @ o
+    disc = bq * bq - (o @ o - ref.FURNACE_R ** 2)
+    t = -bq - np.sqrt(np.maximum(disc, 0.0))
+    x = o + t[..., None] * d
+    muo = np.clip(-np.sum(x * d, axis=-1) / ref.FURNACE_R, 0.0, 1.0)
+    graze = on & (muo.min(axis=1) < MU_MIN)        # the rim of the silhouette, outside the table's domain: not compared
+    include &= ~graze
+    return on, include, np.where((on & ~graze)[:, None], muo, 1.0)
+
+
+def g3_sphere(mis=False, max_depth=1, spp=256, target=0.9):
+    """G3: E4's sphere under a constant 1 x 1 map of radiance c D65, rough with R = 0.9 and alpha = 0.5.  On the sphere
+    mu = c R E(mu_o, alpha), mu_o from the float64 hit (a convex body sees only the sky: every depth has this
+    expectation; without MIS the bounces add nothing); off it c response(1).  Pixels by E4's silhouette rule.  One
+    sample: under PATH the NEE term c R fcos / pdf_env <= c R fcos_sup / pdf_min; under PATH_MIS the NEE term
+    f pdf_l / (pdf_l^2 + pdf_b^2) <= f / (2 pdf_b) <= R / 2 plus the miss's R wb w <= R, so c R 3 / 2; a camera miss is c."""
+    film = ref._film()
+    m8, _ = ref.sample_maxima(film.imaging_ratio)
+    probe = env.constant_map(1, 1, (1.0, 1.0, 1.0))
+    per_c = 1.5 * G3_R if mis else G3_R * fcos_sup(G3_ALPHA) / env.pdf_min(probe)
+    per_c = max(per_c, 1.0) * (1 + 1e-5)
+    c = float(f32(target / (per_c * m8.max())))
+    model = ref._model([ref.FAR_TRIANGLE], [0], [(scene.grey_sigmoid(ref.RHO), 0.0),
+                                                  scene.rough(scene.grey_sigmoid(G3_R), G3_ALPHA)], (),
+                       [scene.Sphere(np.eye(4), 1, radius=ref.FURNACE_R)])
+    cam = scene.PerspectiveCamera(near=1.0, far=5000.0, fov=ref._fov(0.42), position=tuple(ref.FURNACE_EYE),
+                                  look=(0, 0, 1), worldup=(0, 1, 0), res=ref.RES, aspect_fix=True)
+    kind = capi.RT_INTEGRATOR_PATH_MIS if mis else capi.RT_INTEGRATOR_PATH
+    cfg = ref._config("g3_sphere", model, cam, spp, kind, max_depth, film=film)
+    w = ref.sensor_white(film.imaging_ratio)
+    on, include, muo = _sphere_pixels(cfg)
+    rs = float(ref.sigmoid(scene.grey_sigmoid(G3_R), np.array([550.0]))[0])          # the float32 sigmoid's value of 0.9
+    k = np.where(on, rs * albedo_at(G3_ALPHA, muo).mean(axis=1), 1.0)
+    mu = (c * k)[:, None] * w[None, :]
+    vmax = c * per_c * m8
+    cfg, mu, vmax, include = finish("g3_sphere", cfg, mu, vmax, include, spp)
+    return cfg, scene.Environment(env.constant_map(1, 1, (c, c, c))), mu, vmax, include
+
+
+def g3m_box(max_depth=1, spp=256, target=0.9):
+    """G3m: G3's sphere inside K6's closed emissive box (12 inward-facing triangles of radiance L0 D65) declared as an
+    RT_LIGHT_MESH, no map, PATH_MIS.  The sphere sees the box in every direction, so mu = L0 R E(mu_o, alpha) on it and
+    L0 response(1) off it, at every depth (a bounce ends on the emitter).  One sample: the NEE term's weight is
+    fcos p_l / (p_l^2 + p_b^2) <= fcos / (2 p_b) = wb / 2, the BSDF-sampled hit adds R wb w_b <= R: at most L0 R 3 / 2."""
+    film = ref._film()
+    m8, _ = ref.sample_maxima(film.imaging_ratio)
+    per_l0 = max(1.5 * G3_R, 1.0) * (1 + 1e-5)
+    l0 = float(f32(target / (per_l0 * m8.max())))
+    mats = [((0.0, 0.0, 0.0), l0), scene.rough(scene.grey_sigmoid(G3_R), G3_ALPHA)]
+    model = ref._model(ref._box_tris(ref.BOX_HALF), [0] * 12, mats, [dict(type=capi.RT_LIGHT_MESH, material=0)],
+                       [scene.Sphere(np.eye(4), 1, radius=ref.FURNACE_R)])
+    cam = scene.PerspectiveCamera(near=1.0, far=5000.0, fov=ref._fov(0.42), position=tuple(ref.FURNACE_EYE),
+                                  look=(0, 0, 1), worldup=(0, 1, 0), res=ref.RES, aspect_fix=True)
+    cfg = ref._config("g3m_box", model, cam, spp, capi.RT_INTEGRATOR_PATH_MIS, max_depth, film=film)
+    w = ref.sensor_white(film.imaging_ratio)
+    on, include, muo = _sphere_pixels(cfg)
+    rs = float(ref.sigmoid(scene.grey_sigmoid(G3_R), np.array([550.0]))[0])
+    k = np.where(on, rs * albedo_at(G3_ALPHA, muo).mean(axis=1), 1.0)
+    mu = (l0 * k)[:, None] * w[None, :]
+    return finish("g3m_box", cfg, mu, l0 * per_l0 * m8, include, spp)
+
+
+G4_X, G4_H, G4_R = -150.0, 400.0, 0.9
+
+
+def g4_mirror(alpha=0.5, spp=256, target=0.5):
+    """G4: G1 (tessellated floor: a multi-level octree, so both material bins run) with a vertical MIRROR wall (R = 0.9)
+    in the plane x = G4_X, facing +x, |z| <= 200, 0 <= y <= G4_H, PATH depth 2.  A camera ray bound for a floor point with
+    x < G4_X meets the wall first (at a height below 250) and is reflected, d' = (-d.x, d.y, d.z), onto the floor at
+    x > G4_X: the pixel shows L = 0.9 E R fcos(-d', wi).  Pixels whose floor points have x > G4_X keep G1's value: the
+    light comes from +x, so the wall shades no seen floor point, and a floor bounce that meets the wall reaches the floor
+    again only at the last depth, where nothing but an emitter counts.  Pixels whose lattice straddles the wall's foot
+    are left out."""
+    d = ref.K2_DIR
+    assert d[0] > 0
+    film = ref._film()
+    w, m8 = ref._per_rho(film, None)
+    wall = np.array([[(G4_X, 0.0, -200.0), (G4_X, 0.0, 200.0), (G4_X, G4_H, 200.0)],
+                     [(G4_X, 0.0, -200.0), (G4_X, G4_H, 200.0), (G4_X, G4_H, -200.0)]])
+    mirror = (scene.grey_sigmoid(G4_R), 0.0, capi.RT_MAT_MIRROR, 0.0)
+
+    def model(e):
+        m = ref._floor_model(True, wall, [1, 1], [mirror], [dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)])
+        m.materials[0] = scene.rough(scene.grey_sigmoid(ref.RHO), alpha)
+        return m
+
+    def values(cfg, offsets):
+        """(side: -1 mirrored, +1 direct, per sub-sample; fcos with the mirrored wo where mirrored)"""
+        o, wd = ref.camera_rays(cfg, offsets)
+        xf = ref._floor_points(cfg, offsets)
+        mirrored = xf[..., 0] < G4_X
+        ycross = o[1] + wd[..., 1] * ((G4_X - o[0]) / np.where(mirrored, wd[..., 0], -1.0))
+        assert np.all(ycross[mirrored] < G4_H) and np.all(ycross[mirrored] > 0)
+        wo = -wd * np.where(mirrored, -1.0, 1.0)[..., None] * np.array([1.0, 0.0, 0.0]) - wd * np.array([0.0, 1.0, 1.0])
+        wi = nrm64(d)
+        h = nrm64(wo + wi)
+        fc = D64(h[..., 1], alpha) * G2_64(wo[..., 1], wi[1], alpha) / (4 * wo[..., 1])
+        return mirrored, xf[..., 0], fc
+    probe = ref._config("g4", model(1.0), ref._down_camera(), spp, capi.RT_INTEGRATOR_PATH, 2, film=film)
+    fc_max = 1.05 * values(probe, ref._lattice())[2].max()
+    e = float(f32(target / (ref.RHO * fc_max * m8.max())))
+    cfg = ref._config("g4_mirror", model(e), ref._down_camera(), spp, capi.RT_INTEGRATOR_PATH, 2, film=film)
+    ml, xl, _ = values(cfg, ref._lattice())
+    eps = 0.5                                     # floor units: the ray offsets move the wall's foot by far less
+    seen_mirror = np.all(xl < G4_X - eps, axis=1)
+    seen_floor = np.all(xl > G4_X + eps, axis=1)
+    include = seen_mirror | seen_floor
+    assert seen_mirror.mean() > 0.08 and seen_floor.mean() > 0.8
+    mm, _, fc = values(cfg, ref._midpoints())
+    rs = float(ref.sigmoid(scene.grey_sigmoid(G4_R), np.array([550.0]))[0])
+    k = ref.RHO * e * (fc * np.where(mm, rs, 1.0)).mean(axis=1)
+    mu = k[:, None] * w[None, :]
+    cfg, mu, vmax, include = finish("g4_mirror", cfg, mu, ref.RHO * e * fc_max * m8, include, spp)
+    return cfg, mu, vmax, include, seen_mirror
