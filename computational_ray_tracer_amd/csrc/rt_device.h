@@ -10,6 +10,7 @@
 
 #include "rt_cull.h"
 #include "rt_envmap.h"
+#include "rt_fresnel.h"
 #include "rt_ggx.h"
 #include "rt_internal.h"
 #include "rt_mathf.h"
@@ -383,6 +384,12 @@ RT_DEV float dense_query(const float* tab, float lambda) {  // spectrum.h:386-39
     long off = (long)roundf(lambda) - 360;  // std::lround: half away from zero
     if (off < 0 || off >= kSpecN) return 0;
     return tab[off];
+}
+// a metal's (n, k) at dense_query's index (DevSpectra NK, rt_fresnel.h): a plain global load, (0, 0) outside 360-830
+RT_DEV float2 metal_nk_query(const DevSpectra* sp, int metal, float lambda) {
+    const long off = metal_index(lambda);
+    if (off < 0 || off >= kSpecN) return make_float2(0.f, 0.f);
+    return sp->NK[metal][off];
 }
 RT_DEV float piecewise_query(const float* lam, const float* val, int n, float lambda) {  // spectrum.cpp:60-71
     if (n == 0 || lambda < lam[0] || lambda > lam[n - 1]) return 0;

@@ -109,4 +109,22 @@ RT_HD bool ggx_sample_disk(float alpha, V3 wo, float dx, float dy, V3& wi, float
     return true;
 }
 
+// ---- the variants a conductor vertex uses (RT_MAT_CONDUCTOR): the same fcos / pdf / wi / wb bits, and
+// ch = the clamped cosine between wo and the half vector of (wo, wi), the argument of rt_fresnel.h fresnel_conductor.
+// One definition for a light's wi and for the bounce's: h = normalize(wo + wi), ch = fminf(fmaxf(wo.h, 0), 1), so a
+// direction has the same F whether NEE or the bounce found it (the two branches of an MIS pair).
+RT_HD float ggx_cos_h(V3 wo, V3 wi) {
+    const V3 h = ggx_norm(V3{wo.x + wi.x, wo.y + wi.y, wo.z + wi.z});
+    return fminf(fmaxf(ggx_dot(wo, h), 0.f), 1.f);
+}
+RT_HD void ggx_eval_h(float alpha, V3 wo, V3 wi, float& fcos, float& pdf, float& ch) {
+    ggx_eval(alpha, wo, wi, fcos, pdf);
+    ch = ggx_cos_h(wo, wi);
+}
+RT_HD bool ggx_sample_disk_h(float alpha, V3 wo, float dx, float dy, V3& wi, float& wb, float& pdf, float& ch) {
+    const bool ok = ggx_sample_disk(alpha, wo, dx, dy, wi, wb, pdf);
+    ch = ok ? ggx_cos_h(wo, wi) : 0.f;
+    return ok;
+}
+
 }  // namespace rtmi

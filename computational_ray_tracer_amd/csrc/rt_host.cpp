@@ -30,6 +30,7 @@
 #include "rt_internal.h"
 #include "rt_pass_plan.h"
 #include "rt_envmap.h"
+#include "rt_fresnel.h"
 #include "rt_ggx.h"
 #include "rt_texture.h"
 
@@ -150,6 +151,20 @@ float inner_product(const A& f, const B& g) {  // spectrum.h:762-768
     float acc = 0;
     for (float lambda = 360; lambda <= 830; ++lambda) acc += f.query(lambda) * g.query(lambda);
     return acc;
+}
+// The metals' dense (n, k) table NK[4][471] (rt_fresnel.h), built once per process from the measured
+// tables; every context uploads its copy (create_one) and rt_metal_nk reads this one.
+static const std::vector<float>& metal_nk_table() {
+    static const std::vector<float> t = [] {
+        std::vector<float> v(2 * (size_t)kMetals * kMetalSpecN);
+        const float* eta[kMetals] = {rtdata::metal_ag_eta, rtdata::metal_al_eta, rtdata::metal_au_eta, rtdata::metal_cu_eta};
+        const float* kk[kMetals] = {rtdata::metal_ag_k, rtdata::metal_al_k, rtdata::metal_au_k, rtdata::metal_cu_k};
+        const int en[kMetals] = {rtdata::metal_ag_eta_n, rtdata::metal_al_eta_n, rtdata::metal_au_eta_n, rtdata::metal_cu_eta_n};
+        const int kn[kMetals] = {rtdata::metal_ag_k_n, rtdata::metal_al_k_n, rtdata::metal_au_k_n, rtdata::metal_cu_k_n};
+        for (int m = 0; m < kMetals; ++m) metal_nk_build(eta[m], en[m], kk[m], kn[m], v.data() + 2 * (size_t)m * kMetalSpecN);
+        return v;
+    }();
+    return t;
 }
 struct HostSpectra {
     DenseS X, Y, Z, D65d;
@@ -536,6 +551,8 @@ struct rt_ctx {
     bool scene_full = false;   // the scene needs the general path-shade kernel
     bool scene_rough = false;  // a non-emissive RT_MAT_ROUGH material: the RGH instantiations
     long long rgh_launches[2] = {0, 0};  // the last path pass's launches of them: shade, NEE (rt_debug_rough_stats)
+    bool scene_conductor = false;  // a non-emissive RT_MAT_CONDUCTOR material: RGH level 2
+    long long cnd_launches[2] = {0, 0};  // the last path pass's level-2 launches: shade, NEE (rt_debug_conductor_stats)
     DevScene dsc{};
     std::vector<DevBuf<unsigned char>> scene_allocs;  // the arrays dsc points to
     const float* d_kappa = nullptr;  // per analytic shape: the curvature the curved chain guides use (in scene_allocs)
@@ -567,7 +584,7 @@ struct rt_ctx {
     // albedo textures of the uploaded scene (rt_scene_set_textures): live = the path kernels run their TEX
     // instantiations on dev (the DevTex in device memory that points to the other arrays).  table: the RGB -> sigmoid
     // coefficient table (kRgbRes z-nodes, then kRgbTableFloats coefficients), uploaded once per context on first use.
-    // mat_flags: per material of the scene, bit 0 = it emits, bit 1 = an analytic shape uses it (neither takes a texture).
+    // mat_flags: per material of the scene, bit 0 = it emits, bit 1 = an analytic shape uses it, bit 2 = a conductor (none takes a texture).
     struct Textures {
         bool live = false;
         DevBuf<float4> texels;
@@ -1195,6 +1212,7 @@ PassFacts pass_facts(const rt_ctx* c, int n_work, int ib, int ie) {
     f.scene_full = c->scene_full; f.textures = c->tx.live; f.mesh_light = c->ml.any;
     f.environment = c->env.live;
     f.rough = c->scene_rough;
+    f.conductor = c->scene_conductor;
     f.integ = c->integ.kind == RT_INTEGRATOR_PATH_MIS ? kIntegPathMis
               : c->integ.kind == RT_INTEGRATOR_PATH   ? kIntegPath : kIntegReference;
     f.max_depth = c->integ.max_depth;
@@ -1305,7 +1323,7 @@ int path_workspaces(const PathPass& p) {
     for (int l = 0; l < pp.lanes && pp.shq; ++l)
         if (int rc = ensure_shadow_workspace(c, c->ws[l].b, bp.ncap)) return rc;
     for (int l = 0; l < pp.lanes && pp.nee; ++l)
-        if (int rc = ensure_nee_workspace(c, c->ws[l].b, bp.nmax * (size_t)(nee_stride(p.sc.n_lights) + (pp.rgh ? 1 : 0)), bp.ncap)) return rc;
+        if (int rc = ensure_nee_workspace(c, c->ws[l].b, bp.nmax * (size_t)(nee_stride(p.sc.n_lights) + nee_extra_f4(rgh_level(pp), p.sc.n_lights)), bp.ncap)) return rc;
     return RT_OK;
 }
 
@@ -1458,11 +1476,13 @@ int stage_shade(const PathPass& p, const Lane& L, Bounce& bo) {
             HIPCHK(c, launch_path_shade(L.s, c->grid, L.sc.qcap, L.sc, d_spec, p.smp, p.fd, L.ids, bp, c->d_ctr.get(),
                                         bo.sqio, bo.nio, 1 + cl));
             if (p.pp.rgh && cl == 0) ++c->rgh_launches[0];  // (the specular bin has no RGH instantiation)
+            if (p.pp.cnd && cl == 0) ++c->cnd_launches[0];
         }
     } else {
         HIPCHK(c, launch_path_shade(L.s, c->grid, L.sc.qcap, L.sc, d_spec, p.smp, p.fd, L.ids, bo.pio, c->d_ctr.get(),
                                     bo.sqio, bo.nio, 0, p.pp.hit_pack));
         if (p.pp.rgh && p.pp.nee) ++c->rgh_launches[0];
+        if (p.pp.cnd && p.pp.nee) ++c->cnd_launches[0];
     }
     ev_mark(c, L.s, ST_SHADE, e0);
     return RT_OK;
@@ -1499,6 +1519,7 @@ int stage_nee(const PathPass& p, const Lane& L, const Bounce& bo) {
     if (bo.d.nee_fallback)
         HIPCHK(c, launch_path_nee_fallback(L.s, c->grid, L.sc.qcap, L.sc, c->d_spec.get(), bo.pio, bo.nio, c->d_ctr.get()));
     if (p.pp.rgh) c->rgh_launches[1] += bo.d.nee_fallback ? 2 : 1;
+    if (p.pp.cnd) c->cnd_launches[1] += bo.d.nee_fallback ? 2 : 1;
     ev_mark(c, L.s, ST_SHADOW, e0);
     return RT_OK;
 }
@@ -1535,6 +1556,7 @@ int render_path(rt_ctx* c, const PassFacts& f, const BatchPlan& bp, int ib, int 
     const int lanes = p.pp.lanes;
     int rc;
     c->rgh_launches[0] = c->rgh_launches[1] = 0;
+    c->cnd_launches[0] = c->cnd_launches[1] = 0;
     if ((rc = path_workspaces(p))) return rc;
     if (lanes > 1) {  // lanes 1.. start after the caller's earlier work on st
         HIPCHK(c, hipEventRecord(c->ws[0].film_done, st));
@@ -1838,6 +1860,8 @@ static int create_one(const rt_options* opt, rt_ctx** out) {
     ds.bk7_n = (int)c->hs.BK7.l.size();
     std::memcpy(ds.bk7_lambda, c->hs.BK7.l.data(), 4 * ds.bk7_n);
     std::memcpy(ds.bk7_value, c->hs.BK7.v.data(), 4 * ds.bk7_n);
+    static_assert(sizeof(ds.NK) == sizeof(float) * 2 * kMetals * kMetalSpecN && kMetalSpecN == kSpecN, "NK layout");
+    std::memcpy(ds.NK, metal_nk_table().data(), sizeof(ds.NK));
     hipMemcpy(c->d_spec.get(), &ds, sizeof(ds), hipMemcpyHostToDevice);
     hipMemset(c->d_ctr.get(), 0, sizeof(unsigned long long) * kCtrWords);
     {
@@ -1952,11 +1976,17 @@ static std::string validate_scene(const rt_scene_desc* s, bool geometry_only = f
             if (!mat_ok(s->tri_material[t])) return "material id out of range";
     for (int i = 0; i < s->n_materials; ++i) {
         const rt_material& m = s->materials[i];
-        if (m.type < RT_MAT_DIFFUSE || m.type > RT_MAT_ROUGH) return "unknown material type";
+        if (m.type < RT_MAT_DIFFUSE || m.type > RT_MAT_CONDUCTOR) return "unknown material type";
         if (m.type == RT_MAT_DIELECTRIC && m.eta < 0) return "dielectric eta must be >= 0";
         // (the roughness travels in eta; an emitter of type 3 is an emitter like any other: its eta is not read)
         if (m.type == RT_MAT_ROUGH && !(m.emission_scale > 0) && !ggx_alpha_ok(m.eta))
             return "rough material: alpha (rt_material.eta) must be in [0.01, 1] (below 0.01: RT_MAT_MIRROR)";
+        // a conductor: alpha by the rough rule, the metal in sigmoid[0], the other two coefficients unused
+        if (m.type == RT_MAT_CONDUCTOR && !(m.emission_scale > 0)) {
+            if (!ggx_alpha_ok(m.eta)) return "conductor material: alpha (rt_material.eta) must be in [0.01, 1]";
+            if (!metal_id_ok(m.sigmoid[0])) return "conductor material: sigmoid[0] must be a metal, RT_METAL_AG .. RT_METAL_CU";
+            if (!(m.sigmoid[1] == 0.f && m.sigmoid[2] == 0.f)) return "conductor material: sigmoid[1] and sigmoid[2] must be 0";
+        }
     }
     if (s->n_shapes < 0 || (s->n_shapes > 0 && !s->shapes)) return "shapes";
     for (int i = 0; i < s->n_shapes; ++i) {
@@ -2172,6 +2202,7 @@ struct ShadingArrays {
     std::vector<int> ml_first, ml_n, ml_tri;
     bool full = false;              // the scene needs the general path-shade kernel
     bool rough = false;             // a non-emissive RT_MAT_ROUGH material (the RGH instantiations)
+    bool conductor = false;         // a non-emissive RT_MAT_CONDUCTOR material (RGH level 2)
 };
 // The curvature magnitude the curved chain guides give a shape: 1 / (radius sigma) for a sphere whose
 // object_to_render linear part L is a rotation times a uniform scale sigma, 0 for every other shape.  In float64:
@@ -2212,6 +2243,7 @@ static void shading_arrays(const rt_scene_desc* s, const SceneWorld& sw, Shading
         // material bin (kMatClasses): a rough reflector reads spectra and writes NEE records, like Lambert
         const int cls = material_class(m.type, m.emission_scale > 0);  // (rt_pass_plan.h)
         a.rough = a.rough || rough_fact(m.type, m.emission_scale > 0);
+        a.conductor = a.conductor || conductor_fact(m.type, m.emission_scale > 0);
         mats.push_back(DevMaterial{m.sigmoid[0], m.sigmoid[1], m.sigmoid[2], m.emission_scale, m.type, m.eta, -1, cls});
     }
     if (mats.empty()) mats.push_back(DevMaterial{0.f, 0.f, 0.f, 0.f, RT_MAT_DIFFUSE, 0.f, -1, 0});
@@ -2437,6 +2469,7 @@ static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, 
     d.n_materials = (int)a.mats.size();
     c->scene_full = a.full;
     c->scene_rough = a.rough;
+    c->scene_conductor = a.conductor;
     d.qcap = qcap;
     // the cooperative BFS's FIFO holds 16-bit group ids (first child = 1 + 8 g) and kCoopFifo of them
     d.coop_ok = c->knobs.coop && qcap != 1 && lim.bound <= kCoopFifo && lim.ids16 ? 1 : 0;
@@ -2507,7 +2540,8 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
     if (lim.qcap == 1) leaf_clusters(ob.nodes[0], flat, clus);
     if ((rc = upload_scene(c, s, flat, lim, shade, clus, bvh, wabs, oguard))) return rc;
     c->tx.mat_flags.assign(shade.mats.size(), 0);
-    for (size_t i = 0; i < shade.mats.size(); ++i) c->tx.mat_flags[i] = shade.mats[i].emit > 0 ? 1 : 0;
+    for (size_t i = 0; i < shade.mats.size(); ++i)
+        c->tx.mat_flags[i] = shade.mats[i].emit > 0 ? 1 : shade.mats[i].type == RT_MAT_CONDUCTOR ? 4 : 0;
     for (const DevShape& h : shade.shapes) c->tx.mat_flags[h.material] |= 2;
     return RT_OK;
 }
@@ -2863,6 +2897,13 @@ int ensure_albedo_table(rt_ctx* c, hipStream_t st) {
     HIPCHK(c, c->alb.table.reserve(n));
     HIPCHK(c, launch_albedo_bake(st, c->d_spec.get(), c->dsc.n_materials, c->dsc.materials, (int)c->tx.n_texels,
                                  c->tx.texels.get(), c->alb.table.get()));
+    // a conductor's entry is (1, 1, 1), which leaves it un-demodulated: its colour depends on the angle, and it has no
+    // texture detail to protect.  This loop is the only place that knows the rule: a test in k_albedo_film
+    // or k_albedo_bake would change those kernels' register figures for every scene
+    static const float4 one = make_float4(1.f, 1.f, 1.f, 0.f);
+    for (int m = 0; m < c->dsc.n_materials && m < (int)c->tx.mat_flags.size(); ++m)
+        if (c->tx.mat_flags[m] & 4)
+            HIPCHK(c, hipMemcpyAsync(c->alb.table.get() + m, &one, sizeof(one), hipMemcpyHostToDevice, st));
     c->alb.valid = true;
     return RT_OK;
 }
@@ -3817,6 +3858,8 @@ static int impl_rt_scene_set_textures(rt_ctx* c, const rt_texture_desc* d) {
         const int t = d->material_texture[m];
         if (t < -1 || t >= d->n_textures) return fail(c, RT_E_ARG, "texture id out of range");
         if (t >= 0 && (c->tx.mat_flags[m] & 1)) return fail(c, RT_E_ARG, "a texture cannot be bound to an emissive material");
+        if (t >= 0 && (c->tx.mat_flags[m] & 4))
+            return fail(c, RT_E_ARG, "a texture cannot be bound to a conductor material (its colour is F(lambda, angle))");
         if (t >= 0 && (c->tx.mat_flags[m] & 2))
             return fail(c, RT_E_ARG, "a texture cannot be bound to a material an analytic shape uses");
     }
@@ -4162,6 +4205,43 @@ static int impl_rt_debug_rough_stats(rt_ctx* c, int64_t* launches) {
     return RT_OK;
 }
 
+// ---- metal: the level-2 kernels' device functions for a light's wi, on explicit inputs
+static int impl_rt_debug_conductor_eval(rt_ctx* c, int metal, float alpha, int n, const float* normal, const float* dir,
+                                        const float* wi, const float* lambda, float* fcos, float* pdf, float* F) {
+    if (!c || n < 0 || metal < 0 || metal >= kMetals || !ggx_alpha_ok(alpha) ||
+        (n && (!normal || !dir || !wi || !lambda || !fcos || !pdf || !F)))
+        return c ? fail(c, RT_E_ARG, "conductor eval: invalid argument") : RT_E_ARG;
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float> dn, dd, dw, dl;
+        DevBuf<float4> dp;
+        if (dn.reserve(3 * (size_t)n) || dd.reserve(3 * (size_t)n) || dw.reserve(3 * (size_t)n) || dl.reserve(n) ||
+            dp.reserve(n))
+            return fail(c, RT_E_OOM, "conductor eval buffers");
+        std::vector<float4> hp(n);
+        if (hipMemcpy(dn.get(), normal, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dd.get(), dir, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dw.get(), wi, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dl.get(), lambda, 4 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_conductor_eval(c->stream, c->d_spec.get(), metal, alpha, n, dn.get(), dd.get(), dw.get(), dl.get(),
+                                  dp.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(hp.data(), dp.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("conductor eval: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) { fcos[i] = hp[i].x; pdf[i] = hp[i].y; F[i] = hp[i].z; }
+        return RT_OK;
+    });
+}
+
+// launches of the level-2 instantiations by the context's last path pass (render_path counts them)
+static int impl_rt_debug_conductor_stats(rt_ctx* c, int64_t* launches) {
+    if (!c || !launches) return c ? fail(c, RT_E_ARG, "conductor stats: NULL") : RT_E_ARG;
+    launches[0] = c->cnd_launches[0];
+    launches[1] = c->cnd_launches[1];
+    return RT_OK;
+}
+
 // the albedo bake kernel alone, on explicit coefficients under the current sensor
 static int impl_rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
     if (!c || n < 0 || (n && (!coeffs || !rgb))) return c ? fail(c, RT_E_ARG, "albedo bake: invalid argument") : RT_E_ARG;
@@ -4478,6 +4558,32 @@ int rt_debug_ggx_eval(rt_ctx* c, float alpha, int n, const float* normal, const 
     return entry(c, impl_rt_debug_ggx_eval, alpha, n, normal, dir, wi, fcos, pdf);
 }
 int rt_debug_rough_stats(rt_ctx* c, int64_t* launches) { return entry(c, impl_rt_debug_rough_stats, launches); }
+int rt_metal_nk(int metal, int n, const float* lambda, float* n_out, float* k_out) {
+    return guarded([&] {
+        if (metal < 0 || metal >= kMetals || n < 0 || (n && (!lambda || !n_out || !k_out))) return (int)RT_E_ARG;
+        const float* t = metal_nk_table().data() + 2 * (size_t)metal * kMetalSpecN;
+        for (int i = 0; i < n; ++i) {
+            const float l = lambda[i];
+            const long off = l > 0.f && l < 2000.f ? metal_index(l) : -1;  // (a NaN or a huge value is never cast)
+            const bool in = off >= 0 && off < kMetalSpecN;
+            n_out[i] = in ? t[2 * off] : 0.f;
+            k_out[i] = in ? t[2 * off + 1] : 0.f;
+        }
+        return (int)RT_OK;
+    }, [](const std::string&) {});
+}
+int rt_fresnel_conductor(int count, const float* cos, const float* n, const float* k, float* F) {
+    return guarded([&] {
+        if (count < 0 || (count && (!cos || !n || !k || !F))) return (int)RT_E_ARG;
+        for (int i = 0; i < count; ++i) F[i] = fresnel_conductor(cos[i], n[i], k[i]);
+        return (int)RT_OK;
+    }, [](const std::string&) {});
+}
+int rt_debug_conductor_eval(rt_ctx* c, int metal, float alpha, int n, const float* normal, const float* dir,
+                            const float* wi, const float* lambda, float* fcos, float* pdf, float* F) {
+    return entry(c, impl_rt_debug_conductor_eval, metal, alpha, n, normal, dir, wi, lambda, fcos, pdf, F);
+}
+int rt_debug_conductor_stats(rt_ctx* c, int64_t* launches) { return entry(c, impl_rt_debug_conductor_stats, launches); }
 int rt_debug_albedo_bake(rt_ctx* c, int n, const float* coeffs, float* rgb) {
     return entry(c, impl_rt_debug_albedo_bake, n, coeffs, rgb);
 }

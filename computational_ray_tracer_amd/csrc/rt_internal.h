@@ -30,6 +30,9 @@ struct DevSpectra {                 // Spectra::Init products (spectrum.cpp:2612
     // the same dense values packed per wavelength, {SR, SG, SB, D65}[λ - 360]: the kernels stage it in LDS (7.5 KB)
     // and gather one ds_read_b128 per hero wavelength instead of a scattered global load per table (rt_kernels.hip)
     float4 SPK[kSpecN];
+    // the metals' measured optical constants (n, k) per nm (rt_fresnel.h metal_nk_build), read at
+    // dense_query's index through plain global loads by the RGH = 2 instantiations alone; uploaded once per context
+    float2 NK[4][kSpecN];
 };
 
 struct DevCamera {
@@ -507,6 +510,12 @@ struct ShadowQueueIO {
 // The traversals do not share a kernel with the path state (CFG4: 198 VGPRs unbudgeted, 464-656 B/lane spill under
 // the 4-wave budget).
 inline __host__ __device__ int nee_stride(int n_lights) { return 1 + (n_lights + 1) / 2 + (n_lights + 3) / 4; }  // float4s
+// float4s a slot's record holds beyond nee_stride, by the RGH level of the pass's kernels (0 none, 1 rough: DESIGN.md §3k,
+// 2 rough and conductor: §3l): level 2 the lights' clamped wo.h, four per float4, at nee_stride(n); levels 1 and 2 the
+// tail (wb, rough ? 1 : 0, wo.h of the bounce, 0) as the record's last float4
+inline __host__ __device__ int nee_extra_f4(int level, int n_lights) {
+    return level == 2 ? 1 + (n_lights + 3) / 4 : level == 1 ? 1 : 0;
+}
 enum { N_PO = 0, N_UV = 1 };  // the weights at N_UV + ceil(n / 2)
 struct NeeIO {
     float4* rec;   // NEE records, nee_stride(n_lights) float4s per slot; nullptr: inline NEE (not used)
@@ -789,6 +798,10 @@ hipError_t launch_ggx_sample(hipStream_t st, float alpha, int n, const float* nr
                              float2* disk, float4* wi, float2* wbpdf);
 hipError_t launch_ggx_eval(hipStream_t st, float alpha, int n, const float* nrm, const float* dir, const float* wi,
                            float2* out);
+// ---- metal (rt_conductor.hip): the level-2 kernels' device functions for a light's wi, one item per
+// thread: (nrm, dir, wi, lambda) -> out[i] = (fcos, pdf, F(lambda, wo.h), wo.h); sp: the context's spectra (its NK table)
+hipError_t launch_conductor_eval(hipStream_t st, const DevSpectra* sp, int metal, float alpha, int n, const float* nrm,
+                                 const float* dir, const float* wi, const float* lambda, float4* out);
 
 // Albedo textures (rt_texture.hip).  table: the RGB -> sigmoid coefficient table on the device, kRgbRes
 // z-nodes followed by kRgbTableFloats coefficients (rt_texture.h).

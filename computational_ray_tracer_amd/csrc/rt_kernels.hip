@@ -2611,7 +2611,13 @@ __global__ void __launch_bounds__(kBlock) k_occluded(DevScene sc, int n, const f
 // (rt_ggx.h ggx_eval) where Lambert's hold cs, its MIS weights the GGX pdf where Lambert's hold cs / pi, and its bounce is
 // ggx_sample_disk's with prevPdf = the GGX pdf.  The NEE record grows by one float4 (wb, rough ? 1 : 0, 0, 0) at its end,
 // from which k_path_nee<.., RGH> forms x = beta R (no 1 / pi) and the continued throughput beta (R wb).
-template <int QCAP, int MC, bool TEX = false, int TL = 0, bool RGH = false>
+// RGH is a level: 0 none, 1 rough, 2 rough and conductor (a scene with an RT_MAT_CONDUCTOR material).  A
+// conductor vertex is a rough vertex in its control flow: the same draws, ok tests, weights and pdfs.  Level 2 also
+// produces the clamped wo.h of every light's wi (ggx_eval_h) and of the bounce (ggx_sample_disk_h): the record holds the
+// lights' four per float4 after the weights and the bounce's in the tail, (wb, rough ? 1 : 0, ch_b, 0).  Without a light
+// term the kernel forms beta (F(lambda, ch_b) wb) itself from the vertex's 8 (n, k) (metal_nk_query, rt_fresnel.h).
+// Levels 0 and 1 hold none of it.
+template <int QCAP, int MC, bool TEX = false, int TL = 0, int RGH = 0>
 #ifndef RT_FULL_WAVES
 #define RT_FULL_WAVES RT_MULTI_WAVES  // the mixed-scene shade (variant builds)
 #endif
@@ -2623,7 +2629,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
     __shared__ int lds[kBlock / 64 + 1];
     if constexpr (MC != 2) stage_spectra(sp);  // (the mirror / glass bin reads no spectrum table)
     const bool lds_mats = stage_materials(sc);
-    const int nee_f4 = nee_stride(sc.n_lights) + (RGH ? 1 : 0);
+    const int nee_f4 = nee_stride(sc.n_lights) + nee_extra_f4(RGH, sc.n_lights);
     DevTex tx{};
     if constexpr (TEX) tx = *nee.tex;
     // lean depth 0: k_generate stored no β = 1 / L = 0, so they start in registers and every path's L is written
@@ -2790,9 +2796,11 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             float* nwgt = nuv + 4 * ((sc.n_lights + 1) / 2);
                             if (nee.key) neeKey = morton_key(po.x, po.y, po.z, nee.lo, nee.scale, nee.key_bits);
                             bool rough = false;  // (RGH: the vertex's frame and its local wo)
+                            bool cnd = false;    // (RGH 2: a conductor, which is rough as well)
                             V3 ss = v3(0, 0, 0), tt = ss, wol = ss;
                             if constexpr (RGH) {
-                                rough = mt.type == 3;
+                                if constexpr (RGH == 2) cnd = mt.type == 4;
+                                rough = mt.type == 3 || cnd;
                                 if (rough) {
                                     ggx_frame(nrm, ss, tt);
                                     wol = ggx_to_local(v3(-rayd.x, -rayd.y, -rayd.z), ss, tt, nrm);
@@ -2801,6 +2809,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             // the record is written in whole float4s (two lights' samples, four lights' weights per
                             // store) instead of one 4-B store per value: 4 stores per vertex instead of 13 with 4 lights
                             float pu0 = 0.f, pu1 = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
+                            float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;  // (RGH 2: the lights' wo.h, as the weights)
                             const int nl = sc.n_lights;
                             for (int li = 0; li < nl; ++li) {
                                 const DevLight Lt = ldconst(sc.lights, li);
@@ -2810,7 +2819,10 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                                 const LightRay lr = light_ray<TL>(Lt, po, u0, u1, sc.triWorld, ms);
                                 const float cs = vdot(nrm, lr.wi);
                                 float fc = cs, bpdf = 0.f;  // (rough: fcos and the GGX pdf for cs and cs / pi)
-                                if constexpr (RGH) {
+                                float chl = 0.f;
+                                if constexpr (RGH == 2) {
+                                    if (rough) ggx_eval_h(mt.eta, wol, ggx_to_local(lr.wi, ss, tt, nrm), fc, bpdf, chl);
+                                } else if constexpr (RGH) {
                                     if (rough) ggx_eval(mt.eta, wol, ggx_to_local(lr.wi, ss, tt, nrm), fc, bpdf);
                                 }
                                 bool ok;
@@ -2844,6 +2856,13 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                                 pu0 = u0;
                                 pu1 = u1;
                                 if (l4 == 3 || li + 1 == nl) reinterpret_cast<float4*>(nwgt)[li >> 2] = make_float4(w0, w1, w2, w3);
+                                if constexpr (RGH == 2) {
+                                    h0 = l4 == 0 ? chl : h0;
+                                    h1 = l4 == 1 ? chl : h1;
+                                    h2 = l4 == 2 ? chl : h2;
+                                    h3 = l4 == 3 ? chl : h3;
+                                    if (l4 == 3 || li + 1 == nl) nr[nee_stride(nl) + (li >> 2)] = make_float4(h0, h1, h2, h3);
+                                }
                                 wantNee = wantNee || ok;
                             }
                             // cosine-hemisphere bounce (Sampling.h:449-454), pbrt CoordinateSystem frame
@@ -2853,16 +2872,27 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             float z;
                             bool bounced;
                             float rwb = 0.f;  // (RGH: the rough bounce's weight G2 / G1)
+                            float chb = 0.f;  // (RGH 2: the bounce's wo.h)
                             if (RGH && rough) {
                                 float dx, dy, rpdf;
                                 disk_concentric(u0, u1, dx, dy);
                                 V3 wil;
-                                bounced = ggx_sample_disk(mt.eta, wol, dx, dy, wil, rwb, rpdf);
+                                if constexpr (RGH == 2) bounced = ggx_sample_disk_h(mt.eta, wol, dx, dy, wil, rwb, rpdf, chb);
+                                else bounced = ggx_sample_disk(mt.eta, wol, dx, dy, wil, rwb, rpdf);
                                 if (bounced) {
                                     wi = ggx_to_world(wil, ss, tt, nrm);
                                     if (!wantNee) {  // (with NEE, k_path_nee forms β (R wb) after the light terms)
+                                        if (RGH == 2 && cnd) {  // β (F(λ, ch_b) wb): the vertex's 8 (n, k), fetched once
+                                            const int metal = (int)mt.c0;
 #pragma unroll
-                                        for (int i = 0; i < 8; ++i) beta[i] *= (R[i] * rwb);
+                                            for (int i = 0; i < 8; ++i) {
+                                                const float2 nk = metal_nk_query(sp, metal, lam[i]);
+                                                beta[i] *= (fresnel_conductor(chb, nk.x, nk.y) * rwb);
+                                            }
+                                        } else {
+#pragma unroll
+                                            for (int i = 0; i < 8; ++i) beta[i] *= (R[i] * rwb);
+                                        }
                                         rstore8(io.rec, slot, R_BETA, beta);
                                     }
                                     wantNext = true;
@@ -2887,7 +2917,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             if (wantNee) {
                                 nr[N_PO] = make_float4(po.x, po.y, po.z,
                                                        __uint_as_float(tagid | (bounced ? 0x80000000u : 0u)));
-                                if constexpr (RGH) nr[nee_f4 - 1] = make_float4(rwb, rough ? 1.f : 0.f, 0.f, 0.f);
+                                if constexpr (RGH) nr[nee_f4 - 1] = make_float4(rwb, rough ? 1.f : 0.f, chb, 0.f);
                             }
                         }
                         save_sampler(io, slot, sm, io.dim >= 0);
@@ -2975,7 +3005,10 @@ __global__ void __launch_bounds__(kBlock) k_occluded_path(DevScene sc, int n, co
 // texel's Le(lambda) per wavelength where the other lights use sc_le D65.
 // RGH: the record's last float4 is (wb, rough, 0, 0); a rough vertex's x is beta R, its weights already
 // holding f mu_i / R, and its continued throughput beta (R wb).
-template <int QCAP, bool FB, bool TEX = false, int TL = 0, bool RGH = false>
+// RGH == 2: a vertex whose tag names an RT_MAT_CONDUCTOR material (a conductor takes no texture, so its
+// tag is always a material) fetches its 8 (n, k) once; light l's x is beta F(lambda, ch_l), ch_l from the record's float4s
+// after the weights, and its continued throughput beta (F(lambda, ch_b) wb), ch_b from the tail's z.
+template <int QCAP, bool FB, bool TEX = false, int TL = 0, int RGH = 0>
 #ifndef RT_NEE_WAVES
 #define RT_NEE_WAVES 4  // (variant builds: Makefile `variants`)
 #endif
@@ -2984,7 +3017,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
     stage_spectra(sp);
     stage_scene<QCAP>(sc, 0);
     ctr_t snn = 0, snt = 0, nsh = 0, sfb = 0, nvx = 0, novf = 0;
-    const int nl = sc.n_lights, nf4 = nee_stride(nl) + (RGH ? 1 : 0);
+    const int nl = sc.n_lights, nf4 = nee_stride(nl) + nee_extra_f4(RGH, nl);
     // one path vertex: visibility of each sampled light, then the unoccluded lights' contributions in order, then
     // the throughput of the continued path (NeeIO)
     const float InvPi = 0.31830988618379067154f;
@@ -3062,12 +3095,26 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                 rload8(io.rec, slot, R_BETA, beta);
             }
             float rc0, rc1, rc2;
+            bool cnd = false;  // (RGH 2: the vertex is a conductor; its (n, k) at the 8 wavelengths)
+            float cn[8], ck[8];
             if (TEX && (int)(tag & 0x7fffffffu) >= sc.n_materials) {
                 const float4 tc = texels[(tag & 0x7fffffffu) - (unsigned)sc.n_materials];
                 rc0 = tc.x; rc1 = tc.y; rc2 = tc.z;
             } else {
                 const DevMaterial mt = sc.materials[tag & 0x7fffffffu];
                 rc0 = mt.c0; rc1 = mt.c1; rc2 = mt.c2;
+                if constexpr (RGH == 2) cnd = mt.type == 4;
+            }
+            if constexpr (RGH == 2) {
+                if (cnd) {
+                    const int metal = (int)rc0;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const float2 nk = metal_nk_query(sp, metal, lam[i]);
+                        cn[i] = nk.x;
+                        ck[i] = nk.y;
+                    }
+                }
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) R[i] = sigmoid_eval(rc0, rc1, rc2, lam[i]);
@@ -3080,6 +3127,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
 #pragma unroll
                 for (int i = 0; i < 8; ++i) x[i] = RGH && rough ? beta[i] * R[i] : beta[i] * (R[i] * InvPi);
                 float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);  // the weights again, four per 16-B load
+                float4 c4 = w4;                               // (RGH 2: the lights' wo.h the same way)
                 int wq = -1;
                 for (int li = 0; li < nl; ++li) {
                     if (!((vis >> li) & 1)) continue;
@@ -3088,9 +3136,17 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                     if ((li >> 2) != wq) {
                         wq = li >> 2;
                         w4 = reinterpret_cast<const float4*>(wg)[wq];
+                        if constexpr (RGH == 2) c4 = r[nee_stride(nl) + wq];
                     }
                     const int l4 = li & 3;
                     const float wgt = l4 == 0 ? w4.x : l4 == 1 ? w4.y : l4 == 2 ? w4.z : w4.w;
+                    if constexpr (RGH == 2) {
+                        if (cnd) {  // x_l = β F(λ, ch_l)
+                            const float chl = l4 == 0 ? c4.x : l4 == 1 ? c4.y : l4 == 2 ? c4.z : c4.w;
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) x[i] = beta[i] * fresnel_conductor(chl, cn[i], ck[i]);
+                        }
+                    }
                     if (TL == 2 && Lt.type == kLightEnv) {
                         const float4 ec = env_tab(Lt).coef[envTexel];
 #pragma unroll
@@ -3108,7 +3164,10 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             }
             if (bounced) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) beta[i] *= RGH && rough ? R[i] * rg.x : R[i];
+                for (int i = 0; i < 8; ++i) {
+                    if (RGH == 2 && cnd) beta[i] *= (fresnel_conductor(rg.z, cn[i], ck[i]) * rg.x);
+                    else beta[i] *= RGH && rough ? R[i] * rg.x : R[i];
+                }
                 rstore8(io.rec, slot, R_BETA, beta);
             }
         }
@@ -3399,17 +3458,18 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
         void (*k)(DevScene, const DevSpectra*, DevSampler, DevFilm, SampleIds, PathIO, NeeIO);
         // a textured scene: the TEX instantiations; a scene with a mesh light: TL 1; with an environment light: TL 2
         const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);
-        // a scene with a rough material (NeeIO ml bit 2): the RGH instantiations, except for the specular bin
-        const bool rg = (nee.ml & 4) != 0;
+        // a scene with a rough material (NeeIO ml bit 2): the RGH instantiations, except for the specular bin; with a
+        // conductor (bit 3): level 2
+        const int rg = (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;
 #define RT_SHADE_FULL_R(Q, M, R) \
     (v == 0 ? k_path_shade_full<Q, M, false, 0, R> : v == 1 ? k_path_shade_full<Q, M, true, 0, R> \
      : v == 2 ? k_path_shade_full<Q, M, false, 1, R> : v == 3 ? k_path_shade_full<Q, M, true, 1, R> \
      : v == 4 ? k_path_shade_full<Q, M, false, 2, R> : k_path_shade_full<Q, M, true, 2, R>)
-#define RT_SHADE_FULL(Q, M) (rg ? RT_SHADE_FULL_R(Q, M, true) : RT_SHADE_FULL_R(Q, M, false))
+#define RT_SHADE_FULL(Q, M) (rg == 2 ? RT_SHADE_FULL_R(Q, M, 2) : rg ? RT_SHADE_FULL_R(Q, M, 1) : RT_SHADE_FULL_R(Q, M, 0))
         switch (qcap) {
-            case 0: k = matclass == 1 ? RT_SHADE_FULL(0, 1) : matclass == 2 ? RT_SHADE_FULL_R(0, 2, false) : RT_SHADE_FULL(0, 0); break;
+            case 0: k = matclass == 1 ? RT_SHADE_FULL(0, 1) : matclass == 2 ? RT_SHADE_FULL_R(0, 2, 0) : RT_SHADE_FULL(0, 0); break;
             case 1: k = RT_SHADE_FULL(1, 0); break;
-            case 16: k = matclass == 1 ? RT_SHADE_FULL(16, 1) : matclass == 2 ? RT_SHADE_FULL_R(16, 2, false) : RT_SHADE_FULL(16, 0); break;
+            case 16: k = matclass == 1 ? RT_SHADE_FULL(16, 1) : matclass == 2 ? RT_SHADE_FULL_R(16, 2, 0) : RT_SHADE_FULL(16, 0); break;
             default: return hipErrorInvalidValue;
         }
 #undef RT_SHADE_FULL
@@ -3436,12 +3496,12 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
     if (qcap != 1 && (!nee.fb_slot || !nee.fb_len)) return hipErrorInvalidValue;  // the fallback list is required
     void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
     const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);  // (as launch_path_shade)
-    const bool rg = (nee.ml & 4) != 0;  // (as launch_path_shade)
+    const int rg = (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;  // (as launch_path_shade)
 #define RT_NEE_R(Q, R) \
     (v == 0 ? k_path_nee<Q, false, false, 0, R> : v == 1 ? k_path_nee<Q, false, true, 0, R> \
      : v == 2 ? k_path_nee<Q, false, false, 1, R> : v == 3 ? k_path_nee<Q, false, true, 1, R> \
      : v == 4 ? k_path_nee<Q, false, false, 2, R> : k_path_nee<Q, false, true, 2, R>)
-#define RT_NEE(Q) (rg ? RT_NEE_R(Q, true) : RT_NEE_R(Q, false))
+#define RT_NEE(Q) (rg == 2 ? RT_NEE_R(Q, 2) : rg ? RT_NEE_R(Q, 1) : RT_NEE_R(Q, 0))
     switch (qcap) {
         case 0: k = RT_NEE(0); break;
         case 1: k = RT_NEE(1); break;
@@ -3460,12 +3520,12 @@ hipError_t launch_path_nee_fallback(hipStream_t st, int grid, int qcap, const De
     const int gb = ring_clamp(std::min(grid > 0 ? grid : 1, kFallbackBlocks), qcap, sc);
     void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
     const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);
-    const bool rg = (nee.ml & 4) != 0;
+    const int rg = (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;
 #define RT_NEE_FB_R(Q, R) \
     (v == 0 ? k_path_nee<Q, true, false, 0, R> : v == 1 ? k_path_nee<Q, true, true, 0, R> \
      : v == 2 ? k_path_nee<Q, true, false, 1, R> : v == 3 ? k_path_nee<Q, true, true, 1, R> \
      : v == 4 ? k_path_nee<Q, true, false, 2, R> : k_path_nee<Q, true, true, 2, R>)
-#define RT_NEE_FB(Q) (rg ? RT_NEE_FB_R(Q, true) : RT_NEE_FB_R(Q, false))
+#define RT_NEE_FB(Q) (rg == 2 ? RT_NEE_FB_R(Q, 2) : rg ? RT_NEE_FB_R(Q, 1) : RT_NEE_FB_R(Q, 0))
     switch (qcap) {
         case 0: k = RT_NEE_FB(0); break;
         case 16: k = RT_NEE_FB(16); break;

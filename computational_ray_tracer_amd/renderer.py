@@ -244,6 +244,31 @@ class Renderer:
         self._chk("rt_debug_rough_stats", self.lib.rt_debug_rough_stats(self.h, n))
         return int(n[0]) + int(n[1])
 
+    # ---- metal (capi.RT_MAT_CONDUCTOR) -----------------------------------------------------------
+    def conductor_eval(self, metal, alpha, normal, dirs, wi, lam):
+        """rt_debug_conductor_eval: the level-2 kernels' light term at a conductor vertex of metal (an RT_METAL_* id) for
+        normals (n, 3), incoming ray directions (n, 3), world-space light directions wi (n, 3) and wavelengths lam (n)
+        -> dict(fcos (n), pdf (n): rt_debug_ggx_eval's bits, F (n): F(lambda, wo.h))."""
+        nr = np.ascontiguousarray(normal, np.float32)
+        d = np.ascontiguousarray(dirs, np.float32)
+        w = np.ascontiguousarray(wi, np.float32)
+        lam = np.ascontiguousarray(lam, np.float32)
+        n = len(nr)
+        assert nr.shape == (n, 3) and d.shape == (n, 3) and w.shape == (n, 3) and lam.shape == (n,)
+        fcos, pdf, fr = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_conductor_eval", self.lib.rt_debug_conductor_eval(
+            self.h, int(metal), float(alpha), n, nr.ctypes.data_as(F), d.ctypes.data_as(F), w.ctypes.data_as(F),
+            lam.ctypes.data_as(F), fcos.ctypes.data_as(F), pdf.ctypes.data_as(F), fr.ctypes.data_as(F)))
+        return dict(fcos=fcos, pdf=pdf, F=fr)
+
+    def conductor_launches(self):
+        """rt_debug_conductor_stats: launches of the level-2 (rough and conductor) instantiations of k_path_shade_full
+        and k_path_nee by the last path pass, summed (0 for a scene without a conductor)."""
+        n = (C.c_int64 * 2)()
+        self._chk("rt_debug_conductor_stats", self.lib.rt_debug_conductor_stats(self.h, n))
+        return int(n[0]) + int(n[1])
+
     def set_shard(self, tile_size, n_shards, shard_id):
         self._chk("rt_set_shard",self.lib.rt_set_shard(self.h, tile_size, n_shards, shard_id))
 

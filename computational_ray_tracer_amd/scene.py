@@ -605,6 +605,45 @@ def ggx_sample(alpha, wo, disk):
     return wi, wb, pdf
 
 
+METALS = {"Ag": capi.RT_METAL_AG, "Al": capi.RT_METAL_AL, "Au": capi.RT_METAL_AU, "Cu": capi.RT_METAL_CU}
+
+
+def metal(name, alpha):
+    """The material tuple of a metal (capi.RT_MAT_CONDUCTOR): name in "Ag" | "Al" | "Au" | "Cu" and GGX
+    roughness alpha in [0.01, 1] (rt_material.eta).  The metal travels in sigmoid[0]; the other two coefficients are 0."""
+    if name not in METALS:
+        raise ValueError(f"metal {name!r}: one of {sorted(METALS)}")
+    return ((float(METALS[name]), 0.0, 0.0), 0.0, capi.RT_MAT_CONDUCTOR, float(alpha))
+
+
+def metal_nk(name_or_id, lam):
+    """rt_metal_nk (host only): the dense table's (n, k) of a metal (a name or an RT_METAL_* id) at the dense spectra's
+    index of each wavelength lam (m) -> (n (m), k (m)), 0 outside 360-830 nm."""
+    m = METALS[name_or_id] if isinstance(name_or_id, str) else int(name_or_id)
+    lam = np.ascontiguousarray(lam, np.float32)
+    assert lam.ndim == 1
+    n, k = np.zeros(len(lam), np.float32), np.zeros(len(lam), np.float32)
+    F = C.POINTER(C.c_float)
+    r = capi.load_library().rt_metal_nk(m, len(lam), lam.ctypes.data_as(F), n.ctypes.data_as(F), k.ctypes.data_as(F))
+    if r != capi.RT_OK:
+        raise capi.RTError("rt_metal_nk", r, "a metal id 0..3 and non-NULL pointers")
+    return n, k
+
+
+def fresnel_conductor(cos, n, k):
+    """rt_fresnel_conductor (host only): the unpolarised conductor Fresnel reflectance F (m) of cosines cos (clamped to
+    [0, 1]) and complex indices n + i k, each (m)."""
+    cos, n, k = (np.ascontiguousarray(a, np.float32) for a in (cos, n, k))
+    assert cos.ndim == 1 and cos.shape == n.shape == k.shape
+    out = np.zeros(len(cos), np.float32)
+    F = C.POINTER(C.c_float)
+    r = capi.load_library().rt_fresnel_conductor(len(cos), cos.ctypes.data_as(F), n.ctypes.data_as(F),
+                                                 k.ctypes.data_as(F), out.ctypes.data_as(F))
+    if r != capi.RT_OK:
+        raise capi.RTError("rt_fresnel_conductor", r, "non-NULL pointers")
+    return out
+
+
 def _flat_mesh(faces_xyz):
     """(nt, 3, 3) float64 corner positions -> one-vertex-per-corner float32 mesh with flat normals."""
     p = np.asarray(faces_xyz, dtype=np.float64)

@@ -59,7 +59,9 @@ typedef struct { float r, g, b, w; } rt_pixel;
  * sum = sum + v and sumsq = sumsq + v * v for every sample, in the film's index order (float32, nothing fused). */
 typedef struct { float sum, sumsq; } rt_moment;
 
-enum { RT_MAT_DIFFUSE = 0, RT_MAT_MIRROR = 1, RT_MAT_DIELECTRIC = 2, RT_MAT_ROUGH = 3 };
+enum { RT_MAT_DIFFUSE = 0, RT_MAT_MIRROR = 1, RT_MAT_DIELECTRIC = 2, RT_MAT_ROUGH = 3, RT_MAT_CONDUCTOR = 4 };
+/* the metal of an RT_MAT_CONDUCTOR material, carried as a float in rt_material.sigmoid[0] */
+enum { RT_METAL_AG = 0, RT_METAL_AL = 1, RT_METAL_AU = 2, RT_METAL_CU = 3 };
 /* Build-defined material (the reference has none: Shading.h:1-21 is a comment stub).
  * DIFFUSE: Lambert R/π; MIRROR: perfect specular reflection scaled by R; R(λ) is an RGBSigmoidPolynomial
  *   (color.h:363-403): R(λ) = s(c0 λ² + c1 λ + c2).
@@ -92,8 +94,31 @@ enum { RT_MAT_DIFFUSE = 0, RT_MAT_MIRROR = 1, RT_MAT_DIELECTRIC = 2, RT_MAT_ROUG
  *   pdf(wo, wi) to the next emitter hit or environment miss.  An albedo texture supplies R as for Lambert.
  *   RT_INTEGRATOR_REFERENCE never sees materials; the feature, position and chain passes end a chain on a rough surface,
  *   as on a Lambert one; rt_render_features_albedo demodulates it by A of its material or texel, as Lambert (exact: f
- *   is R(lambda) times a scalar).  Limits: no transmission, no anisotropy, no Schlick or conductor Fresnel (the grazing
- *   rise would need a second scalar per light and per bounce), no multiple-scattering compensation, no roughness textures.
+ *   is R(lambda) times a scalar).  Limits: no transmission, no anisotropy, no angle-dependent Fresnel on this material
+ *   (RT_MAT_CONDUCTOR below has the conductor's), no multiple-scattering compensation, no roughness textures.
+ * CONDUCTOR (additive): a metal: ROUGH's GGX lobe with the exact unpolarised conductor Fresnel term of a
+ *   measured complex index n + i k in place of R(lambda).  `eta` is the roughness alpha, with ROUGH's rule (RT_E_ARG
+ *   unless finite and in [0.01, 1], "alpha" in rt_last_error); sigmoid[0] is the metal as a float (RT_METAL_AG = 0,
+ *   RT_METAL_AL = 1, RT_METAL_AU = 2, RT_METAL_CU = 3); sigmoid[1] and sigmoid[2] must be 0; anything else is RT_E_ARG and
+ *   the scene bound before stays.  An emissive material's type, eta and sigmoid are not validated or read.
+ *   Optical constants: one dense table NK[4][471] of (n, k) pairs; entry j is the piecewise-linear value of the metal's
+ *   two measured tables (56 (lambda, value) pairs each, 298.76-885.60 nm) at lambda = 360 + j, computed on the host in
+ *   float32 with PiecewiseLinearSpectrum::Query's operations (the same interval search, t = (lambda - l[o]) /
+ *   (l[o+1] - l[o]), (1 - t) v[o] + t v[o+1]) and uploaded once per context (15 KB).  Kernels read it at the dense
+ *   spectra's index, (long)roundf(lambda) - 360, as D65 and the sensor bars are read.
+ *   Fresnel: unpolarised, exact, real arithmetic; only + - * /, sqrtf and comparisons, float32 in the order written,
+ *   nothing fused.  With c = fminf(fmaxf(wo.h, 0), 1), h = normalize(wo + wi):
+ *     c2 = c c;  s2 = 1 - c2;  t0 = (n n - k k) - s2;  ab = sqrtf(t0 t0 + (4 (n n)) (k k));  t1 = ab + c2
+ *     a  = sqrtf(fmaxf(0.5f (ab + t0), 0));  t2 = (2 a) c;  Rs = (t1 - t2) / (t1 + t2)
+ *     t3 = c2 ab + s2 s2;  t4 = t2 s2;  Rp = (Rs (t3 - t4)) / (t3 + t4);  F = 0.5f (Rp + Rs)
+ *   BSDF: f = F(lambda, wo.h) D(h) G2 / (4 mu_o mu_i); D, Lambda, G2, the frame, the visible-normal sampling, the pdf and
+ *   wb = G2 / G1(wo) are ROUGH's; F replaces R(lambda) and is in no pdf and no MIS weight.  A conductor vertex is a rough
+ *   vertex in its control flow (the same draws in the same order, the same acceptance tests, weights and prevPdf); light
+ *   l adds ((beta F(lambda, ch_l)) Le) wgt, ch_l the clamped wo.h of the light's wi, and the bounce multiplies beta by
+ *   F(lambda, ch_b) wb, ch_b that of the bounce's wi.  No texture binds to a conductor (rt_scene_set_textures: RT_E_ARG);
+ *   its entry of the albedo table is (1, 1, 1), so rt_render_features_albedo leaves it un-demodulated (its colour
+ *   depends on the angle); the feature, position and chain passes end a chain on it, as on ROUGH.  Limits: no smooth conductor
+ *   (alpha < 0.01) in the specular bin, no tints or textures, no user-supplied n, k, no multiple-scattering compensation.
  * emission_scale > 0 makes the surface a pure one-sided emitter with Le = scale · stdillum-D65. */
 typedef struct {
     int type;
@@ -655,6 +680,23 @@ int rt_debug_ggx_eval(rt_ctx* ctx, float alpha, int n, const float* normal, cons
 /* launches[2]: launches of the RGH instantiations of k_path_shade_full and of k_path_nee (the fallback included) by the
  * context's last path pass (0, 0 for a scene without a rough material). */
 int rt_debug_rough_stats(rt_ctx* ctx, int64_t* launches);
+
+/* ---- metal (additive): RT_MAT_CONDUCTOR above ------------------------------------------
+ * rt_metal_nk (host only, no context): the dense table's entry of metal (RT_METAL_*) at the dense spectra's index of
+ * each of n wavelengths, n_out[i] = n, k_out[i] = k; 0 outside 360-830 nm.  rt_fresnel_conductor (host only): F[i] of
+ * count (cos, n, k) triples, cos clamped to [0, 1].  RT_E_ARG: a NULL pointer with a positive count, a negative count,
+ * metal out of range. */
+int rt_metal_nk(int metal, int n, const float* lambda, float* n_out, float* k_out);
+int rt_fresnel_conductor(int count, const float* cos, const float* n, const float* k, float* F);
+/* The path kernels' own device functions for a light's wi at a conductor vertex, one item per thread, on world-space
+ * vectors as rt_debug_ggx_eval (whose bits fcos and pdf have): normal, dir, wi (3n each), lambda (n) ->
+ * fcos, pdf, F (n): F = F(lambda, wo.h) from the context's table.  RT_E_ARG as rt_debug_ggx_eval, and for a metal out of
+ * range. */
+int rt_debug_conductor_eval(rt_ctx* ctx, int metal, float alpha, int n, const float* normal, const float* dir,
+                            const float* wi, const float* lambda, float* fcos, float* pdf, float* F);
+/* launches[2]: launches of the level-2 (rough and conductor) instantiations of k_path_shade_full and of k_path_nee (the
+ * fallback included) by the context's last path pass (0, 0 for a scene without a conductor). */
+int rt_debug_conductor_stats(rt_ctx* ctx, int64_t* launches);
 
 /* ---- albedo demodulation for the denoiser (additive) ------------------------------
  * The filter divides the film by a noise-free first-hit albedo, filters the demodulated irradiance (smooth across the
