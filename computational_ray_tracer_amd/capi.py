@@ -15,6 +15,7 @@ RT_OK, RT_E_ARG, RT_E_HIP, RT_E_RCCL, RT_E_OOM, RT_E_STATE, RT_E_NODEVICE, RT_E_
 STATUS_NAMES = {0: "RT_OK", -1: "RT_E_ARG", -2: "RT_E_HIP", -3: "RT_E_RCCL", -4: "RT_E_OOM", -5: "RT_E_STATE",
                 -6: "RT_E_NODEVICE", -7: "RT_E_LIMIT"}
 RT_MAT_DIFFUSE, RT_MAT_MIRROR, RT_MAT_DIELECTRIC, RT_MAT_ROUGH, RT_MAT_CONDUCTOR = 0, 1, 2, 3, 4
+RT_MAT_ROUGH_DIELECTRIC = 5
 RT_METAL_AG, RT_METAL_AL, RT_METAL_AU, RT_METAL_CU = 0, 1, 2, 3   # rt_material.sigmoid[0] of an RT_MAT_CONDUCTOR
 RT_SHAPE_SPHERE, RT_SHAPE_DISK, RT_SHAPE_TRIANGLE = 0, 1, 2
 RT_LIGHT_QUAD, RT_LIGHT_DISK, RT_LIGHT_POINT, RT_LIGHT_DISTANT, RT_LIGHT_MESH, RT_LIGHT_ENV = 0, 1, 2, 3, 4, 5
@@ -206,6 +207,8 @@ EXPORTS = [
     "rt_debug_env_stats",
     "rt_ggx_eval", "rt_ggx_sample", "rt_debug_ggx_sample", "rt_debug_ggx_eval", "rt_debug_rough_stats",
     "rt_metal_nk", "rt_fresnel_conductor", "rt_debug_conductor_eval", "rt_debug_conductor_stats",
+    "rt_roughglass_eval", "rt_roughglass_sample", "rt_debug_roughglass_sample", "rt_debug_roughglass_eval",
+    "rt_debug_roughglass_stats",
 ]
 
 _lib = None
@@ -336,6 +339,16 @@ def load_library(path=None):
         "rt_debug_conductor_eval": ([C.c_void_p, C.c_int, C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float),
                                      P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)], C.c_int),
         "rt_debug_conductor_stats": ([C.c_void_p, P(C.c_int64)], C.c_int),
+        "rt_roughglass_eval": ([C.c_float, C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)],
+                               C.c_int),
+        "rt_roughglass_sample": ([C.c_float, C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                  P(C.c_float), P(C.c_float), P(C.c_int32)], C.c_int),
+        "rt_debug_roughglass_sample": ([C.c_void_p, C.c_float, C.c_float, C.c_int, P(C.c_float), P(C.c_float),
+                                        P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                        P(C.c_int32)], C.c_int),
+        "rt_debug_roughglass_eval": ([C.c_void_p, C.c_float, C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float),
+                                      P(C.c_float), P(C.c_float)], C.c_int),
+        "rt_debug_roughglass_stats": ([C.c_void_p, P(C.c_int64)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

@@ -12,6 +12,7 @@
 #include "rt_envmap.h"
 #include "rt_fresnel.h"
 #include "rt_ggx.h"
+#include "rt_roughglass.h"
 #include "rt_internal.h"
 #include "rt_mathf.h"
 #include "rt_texture.h"
@@ -721,17 +722,10 @@ RT_DEV float power_heuristic(float f, float g) {
     if (__builtin_isinf(f2)) return 1;
     return f2 / (f2 + g2);
 }
-RT_DEV float fr_dielectric(float cosi, float eta) {
+RT_DEV float fr_dielectric(float cosi, float eta) {  // (the body is rt_fresnel.h's, shared with the rough glass)
     cosi = gclamp(cosi, -1.0f, 1.0f);
     if (cosi < 0) { eta = 1 / eta; cosi = -cosi; }
-    float sin2i = 1 - cosi * cosi;
-    float sin2t = sin2i / (eta * eta);
-    if (sin2t >= 1) return 1.f;
-    float x = 1 - sin2t;
-    float cost = sqrtf(x > 0.f ? x : 0.f);
-    float r_parl = (eta * cosi - cost) / (eta * cosi + cost);
-    float r_perp = (cosi - eta * cost) / (cosi + eta * cost);
-    return (r_parl * r_parl + r_perp * r_perp) / 2;
+    return fr_dielectric_pos(cosi, eta);
 }
 // The shadow ray toward one light sample (Lights.h semantics): area lights (quad: p + u0 e1 + u1 e2;
 // disk: the concentric mapping of the Disk shape) and point lights aim at the point, tMax = 0.999 dist; a distant

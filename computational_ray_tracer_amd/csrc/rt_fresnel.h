@@ -46,6 +46,19 @@ RT_HD float fresnel_conductor(float c, float n, float k) {
     return 0.5f * (Rp + Rs);
 }
 
+// The unpolarised dielectric Fresnel reflectance for a cosine already in [0, 1] and the relative index of that side: the
+// one text of rt_device.h's fr_dielectric (smooth glass) and rt_roughglass.h's roughglass_F (rough glass)
+RT_HD float fr_dielectric_pos(float cosi, float eta) {
+    const float sin2i = 1 - cosi * cosi;
+    const float sin2t = sin2i / (eta * eta);
+    if (sin2t >= 1) return 1.f;
+    const float x = 1 - sin2t;
+    const float cost = sqrtf(x > 0.f ? x : 0.f);
+    const float r_parl = (eta * cosi - cost) / (eta * cosi + cost);
+    const float r_perp = (cosi - eta * cost) / (cosi + eta * cost);
+    return (r_parl * r_parl + r_perp * r_perp) / 2;
+}
+
 // dense_query's index (rt_device.h): roundf is half away from zero, as std::lround
 RT_HD long metal_index(float lambda) { return (long)roundf(lambda) - 360; }
 

@@ -77,13 +77,9 @@ RT_HD void ggx_eval(float alpha, V3 wo, V3 wi, float& fcos, float& pdf) {
     pdf = (G1 * D) / d4;
 }
 
-// the bounce from a disk point: false = no bounce (wo or wi below the horizon; wi, wb, pdf are then 0)
-RT_HD bool ggx_sample_disk(float alpha, V3 wo, float dx, float dy, V3& wi, float& wb, float& pdf) {
-    wi = V3{0.f, 0.f, 0.f};
-    wb = 0.f;
-    pdf = 0.f;
-    if (!(wo.z > 0.f)) return false;
-    const float a2 = alpha * alpha;
+// the visible normal h of wo (wo.z > 0) from a disk point: the half vector ggx_sample_disk reflects about and
+// rt_roughglass.h reflects or refracts through
+RT_HD V3 ggx_sample_h(float alpha, V3 wo, float dx, float dy) {
     const V3 wh = ggx_norm(V3{alpha * wo.x, alpha * wo.y, wo.z});
     V3 T1 = V3{1.f, 0.f, 0.f};
     if (wh.z < 0.99999f) T1 = ggx_norm(ggx_cross(V3{0.f, 0.f, 1.f}, wh));
@@ -96,7 +92,17 @@ RT_HD bool ggx_sample_disk(float alpha, V3 wo, float dx, float dy, V3& wi, float
     pz = sqrtf(pz > 0.f ? pz : 0.f);
     const V3 nh = V3{(T1.x * dx + T2.x * dy) + wh.x * pz, (T1.y * dx + T2.y * dy) + wh.y * pz,
                      (T1.z * dx + T2.z * dy) + wh.z * pz};
-    const V3 h = ggx_norm(V3{alpha * nh.x, alpha * nh.y, nh.z > 1e-6f ? nh.z : 1e-6f});
+    return ggx_norm(V3{alpha * nh.x, alpha * nh.y, nh.z > 1e-6f ? nh.z : 1e-6f});
+}
+
+// the bounce from a disk point: false = no bounce (wo or wi below the horizon; wi, wb, pdf are then 0)
+RT_HD bool ggx_sample_disk(float alpha, V3 wo, float dx, float dy, V3& wi, float& wb, float& pdf) {
+    wi = V3{0.f, 0.f, 0.f};
+    wb = 0.f;
+    pdf = 0.f;
+    if (!(wo.z > 0.f)) return false;
+    const float a2 = alpha * alpha;
+    const V3 h = ggx_sample_h(alpha, wo, dx, dy);
     const float d2 = 2.0f * ggx_dot(wo, h);
     const V3 w = V3{d2 * h.x - wo.x, d2 * h.y - wo.y, d2 * h.z - wo.z};
     if (!(w.z > 0.f)) return false;

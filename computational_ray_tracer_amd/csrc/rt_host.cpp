@@ -32,6 +32,7 @@
 #include "rt_envmap.h"
 #include "rt_fresnel.h"
 #include "rt_ggx.h"
+#include "rt_roughglass.h"
 #include "rt_texture.h"
 
 using namespace rtmi;
@@ -553,6 +554,8 @@ struct rt_ctx {
     long long rgh_launches[2] = {0, 0};  // the last path pass's launches of them: shade, NEE (rt_debug_rough_stats)
     bool scene_conductor = false;  // a non-emissive RT_MAT_CONDUCTOR material: RGH level 2
     long long cnd_launches[2] = {0, 0};  // the last path pass's level-2 launches: shade, NEE (rt_debug_conductor_stats)
+    bool scene_rough_dielectric = false;  // a non-emissive RT_MAT_ROUGH_DIELECTRIC material: RGH level 3
+    long long rgl_launches[2] = {0, 0};  // the last path pass's level-3 launches: shade, NEE (rt_debug_roughglass_stats)
     DevScene dsc{};
     std::vector<DevBuf<unsigned char>> scene_allocs;  // the arrays dsc points to
     const float* d_kappa = nullptr;  // per analytic shape: the curvature the curved chain guides use (in scene_allocs)
@@ -584,7 +587,7 @@ struct rt_ctx {
     // albedo textures of the uploaded scene (rt_scene_set_textures): live = the path kernels run their TEX
     // instantiations on dev (the DevTex in device memory that points to the other arrays).  table: the RGB -> sigmoid
     // coefficient table (kRgbRes z-nodes, then kRgbTableFloats coefficients), uploaded once per context on first use.
-    // mat_flags: per material of the scene, bit 0 = it emits, bit 1 = an analytic shape uses it, bit 2 = a conductor (none takes a texture).
+    // mat_flags: per material of the scene, bit 0 = it emits, bit 1 = an analytic shape uses it, bit 2 = a conductor, bit 3 = a rough glass (none takes a texture).
     struct Textures {
         bool live = false;
         DevBuf<float4> texels;
@@ -1213,6 +1216,7 @@ PassFacts pass_facts(const rt_ctx* c, int n_work, int ib, int ie) {
     f.environment = c->env.live;
     f.rough = c->scene_rough;
     f.conductor = c->scene_conductor;
+    f.rough_dielectric = c->scene_rough_dielectric;
     f.integ = c->integ.kind == RT_INTEGRATOR_PATH_MIS ? kIntegPathMis
               : c->integ.kind == RT_INTEGRATOR_PATH   ? kIntegPath : kIntegReference;
     f.max_depth = c->integ.max_depth;
@@ -1477,12 +1481,14 @@ int stage_shade(const PathPass& p, const Lane& L, Bounce& bo) {
                                         bo.sqio, bo.nio, 1 + cl));
             if (p.pp.rgh && cl == 0) ++c->rgh_launches[0];  // (the specular bin has no RGH instantiation)
             if (p.pp.cnd && cl == 0) ++c->cnd_launches[0];
+            if (p.pp.rgl && cl == 0) ++c->rgl_launches[0];
         }
     } else {
         HIPCHK(c, launch_path_shade(L.s, c->grid, L.sc.qcap, L.sc, d_spec, p.smp, p.fd, L.ids, bo.pio, c->d_ctr.get(),
                                     bo.sqio, bo.nio, 0, p.pp.hit_pack));
         if (p.pp.rgh && p.pp.nee) ++c->rgh_launches[0];
         if (p.pp.cnd && p.pp.nee) ++c->cnd_launches[0];
+        if (p.pp.rgl && p.pp.nee) ++c->rgl_launches[0];
     }
     ev_mark(c, L.s, ST_SHADE, e0);
     return RT_OK;
@@ -1520,6 +1526,7 @@ int stage_nee(const PathPass& p, const Lane& L, const Bounce& bo) {
         HIPCHK(c, launch_path_nee_fallback(L.s, c->grid, L.sc.qcap, L.sc, c->d_spec.get(), bo.pio, bo.nio, c->d_ctr.get()));
     if (p.pp.rgh) c->rgh_launches[1] += bo.d.nee_fallback ? 2 : 1;
     if (p.pp.cnd) c->cnd_launches[1] += bo.d.nee_fallback ? 2 : 1;
+    if (p.pp.rgl) c->rgl_launches[1] += bo.d.nee_fallback ? 2 : 1;
     ev_mark(c, L.s, ST_SHADOW, e0);
     return RT_OK;
 }
@@ -1557,6 +1564,7 @@ int render_path(rt_ctx* c, const PassFacts& f, const BatchPlan& bp, int ib, int 
     int rc;
     c->rgh_launches[0] = c->rgh_launches[1] = 0;
     c->cnd_launches[0] = c->cnd_launches[1] = 0;
+    c->rgl_launches[0] = c->rgl_launches[1] = 0;
     if ((rc = path_workspaces(p))) return rc;
     if (lanes > 1) {  // lanes 1.. start after the caller's earlier work on st
         HIPCHK(c, hipEventRecord(c->ws[0].film_done, st));
@@ -1976,7 +1984,7 @@ static std::string validate_scene(const rt_scene_desc* s, bool geometry_only = f
             if (!mat_ok(s->tri_material[t])) return "material id out of range";
     for (int i = 0; i < s->n_materials; ++i) {
         const rt_material& m = s->materials[i];
-        if (m.type < RT_MAT_DIFFUSE || m.type > RT_MAT_CONDUCTOR) return "unknown material type";
+        if (m.type < RT_MAT_DIFFUSE || m.type > RT_MAT_ROUGH_DIELECTRIC) return "unknown material type";
         if (m.type == RT_MAT_DIELECTRIC && m.eta < 0) return "dielectric eta must be >= 0";
         // (the roughness travels in eta; an emitter of type 3 is an emitter like any other: its eta is not read)
         if (m.type == RT_MAT_ROUGH && !(m.emission_scale > 0) && !ggx_alpha_ok(m.eta))
@@ -1986,6 +1994,15 @@ static std::string validate_scene(const rt_scene_desc* s, bool geometry_only = f
             if (!ggx_alpha_ok(m.eta)) return "conductor material: alpha (rt_material.eta) must be in [0.01, 1]";
             if (!metal_id_ok(m.sigmoid[0])) return "conductor material: sigmoid[0] must be a metal, RT_METAL_AG .. RT_METAL_CU";
             if (!(m.sigmoid[1] == 0.f && m.sigmoid[2] == 0.f)) return "conductor material: sigmoid[1] and sigmoid[2] must be 0";
+        }
+        // a rough glass: a constant index above 1 in eta, alpha by the rough rule in sigmoid[0]
+        if (m.type == RT_MAT_ROUGH_DIELECTRIC && !(m.emission_scale > 0)) {
+            if (m.eta == 0.f)
+                return "rough dielectric material: eta 0 (dispersive BK7) is not supported on a rough interface; give a constant eta > 1";
+            if (!roughglass_eta_ok(m.eta)) return "rough dielectric material: eta must be finite and > 1";
+            if (!ggx_alpha_ok(m.sigmoid[0])) return "rough dielectric material: alpha (rt_material.sigmoid[0]) must be in [0.01, 1]";
+            if (!(m.sigmoid[1] == 0.f && m.sigmoid[2] == 0.f))
+                return "rough dielectric material: sigmoid[1] and sigmoid[2] must be 0";
         }
     }
     if (s->n_shapes < 0 || (s->n_shapes > 0 && !s->shapes)) return "shapes";
@@ -2203,6 +2220,7 @@ struct ShadingArrays {
     bool full = false;              // the scene needs the general path-shade kernel
     bool rough = false;             // a non-emissive RT_MAT_ROUGH material (the RGH instantiations)
     bool conductor = false;         // a non-emissive RT_MAT_CONDUCTOR material (RGH level 2)
+    bool rough_dielectric = false;  // a non-emissive RT_MAT_ROUGH_DIELECTRIC material (RGH level 3)
 };
 // The curvature magnitude the curved chain guides give a shape: 1 / (radius sigma) for a sphere whose
 // object_to_render linear part L is a rotation times a uniform scale sigma, 0 for every other shape.  In float64:
@@ -2244,6 +2262,7 @@ static void shading_arrays(const rt_scene_desc* s, const SceneWorld& sw, Shading
         const int cls = material_class(m.type, m.emission_scale > 0);  // (rt_pass_plan.h)
         a.rough = a.rough || rough_fact(m.type, m.emission_scale > 0);
         a.conductor = a.conductor || conductor_fact(m.type, m.emission_scale > 0);
+        a.rough_dielectric = a.rough_dielectric || rough_dielectric_fact(m.type, m.emission_scale > 0);
         mats.push_back(DevMaterial{m.sigmoid[0], m.sigmoid[1], m.sigmoid[2], m.emission_scale, m.type, m.eta, -1, cls});
     }
     if (mats.empty()) mats.push_back(DevMaterial{0.f, 0.f, 0.f, 0.f, RT_MAT_DIFFUSE, 0.f, -1, 0});
@@ -2470,6 +2489,7 @@ static int upload_scene(rt_ctx* c, const rt_scene_desc* s, const FlatOctree& f, 
     c->scene_full = a.full;
     c->scene_rough = a.rough;
     c->scene_conductor = a.conductor;
+    c->scene_rough_dielectric = a.rough_dielectric;
     d.qcap = qcap;
     // the cooperative BFS's FIFO holds 16-bit group ids (first child = 1 + 8 g) and kCoopFifo of them
     d.coop_ok = c->knobs.coop && qcap != 1 && lim.bound <= kCoopFifo && lim.ids16 ? 1 : 0;
@@ -2541,7 +2561,8 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
     if ((rc = upload_scene(c, s, flat, lim, shade, clus, bvh, wabs, oguard))) return rc;
     c->tx.mat_flags.assign(shade.mats.size(), 0);
     for (size_t i = 0; i < shade.mats.size(); ++i)
-        c->tx.mat_flags[i] = shade.mats[i].emit > 0 ? 1 : shade.mats[i].type == RT_MAT_CONDUCTOR ? 4 : 0;
+        c->tx.mat_flags[i] = shade.mats[i].emit > 0 ? 1 : shade.mats[i].type == RT_MAT_CONDUCTOR ? 4
+                             : shade.mats[i].type == RT_MAT_ROUGH_DIELECTRIC ? 8 : 0;
     for (const DevShape& h : shade.shapes) c->tx.mat_flags[h.material] |= 2;
     return RT_OK;
 }
@@ -2902,7 +2923,7 @@ int ensure_albedo_table(rt_ctx* c, hipStream_t st) {
     // or k_albedo_bake would change those kernels' register figures for every scene
     static const float4 one = make_float4(1.f, 1.f, 1.f, 0.f);
     for (int m = 0; m < c->dsc.n_materials && m < (int)c->tx.mat_flags.size(); ++m)
-        if (c->tx.mat_flags[m] & 4)
+        if (c->tx.mat_flags[m] & (4 | 8))  // (a rough glass as well, DESIGN.md §3m: it has no colour of its own)
             HIPCHK(c, hipMemcpyAsync(c->alb.table.get() + m, &one, sizeof(one), hipMemcpyHostToDevice, st));
     c->alb.valid = true;
     return RT_OK;
@@ -3860,6 +3881,8 @@ static int impl_rt_scene_set_textures(rt_ctx* c, const rt_texture_desc* d) {
         if (t >= 0 && (c->tx.mat_flags[m] & 1)) return fail(c, RT_E_ARG, "a texture cannot be bound to an emissive material");
         if (t >= 0 && (c->tx.mat_flags[m] & 4))
             return fail(c, RT_E_ARG, "a texture cannot be bound to a conductor material (its colour is F(lambda, angle))");
+        if (t >= 0 && (c->tx.mat_flags[m] & 8))
+            return fail(c, RT_E_ARG, "a texture cannot be bound to a rough dielectric material (it has no albedo)");
         if (t >= 0 && (c->tx.mat_flags[m] & 2))
             return fail(c, RT_E_ARG, "a texture cannot be bound to a material an analytic shape uses");
     }
@@ -4202,6 +4225,74 @@ static int impl_rt_debug_rough_stats(rt_ctx* c, int64_t* launches) {
     if (!c || !launches) return c ? fail(c, RT_E_ARG, "rough stats: NULL") : RT_E_ARG;
     launches[0] = c->rgh_launches[0];
     launches[1] = c->rgh_launches[1];
+    return RT_OK;
+}
+
+// ---- rough glass: the level-3 kernels' device functions at a rough-glass vertex, on explicit inputs
+static bool roughglass_er_ok(float er) { return er > 0.f && er < 3.0e38f; }
+static int impl_rt_debug_roughglass_sample(rt_ctx* c, float alpha, float er, int n, const float* normal, const float* dir,
+                                           const float* u, float* disk_out, float* wi, float* w, float* pdf, int32_t* branch) {
+    if (!c || n < 0 || !ggx_alpha_ok(alpha) || !roughglass_er_ok(er) ||
+        (n && (!normal || !dir || !u || !disk_out || !wi || !w || !pdf || !branch)))
+        return c ? fail(c, RT_E_ARG, "roughglass sample: invalid argument") : RT_E_ARG;
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float> dn, dd, du;
+        DevBuf<float2> dk, dp;
+        DevBuf<float4> dw;
+        if (dn.reserve(3 * (size_t)n) || dd.reserve(3 * (size_t)n) || du.reserve(3 * (size_t)n) || dk.reserve(n) ||
+            dp.reserve(n) || dw.reserve(n))
+            return fail(c, RT_E_OOM, "roughglass sample buffers");
+        std::vector<float4> hw(n);
+        std::vector<float2> hp(n);
+        if (hipMemcpy(dn.get(), normal, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dd.get(), dir, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(du.get(), u, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_roughglass_sample(c->stream, alpha, er, n, dn.get(), dd.get(), du.get(), dk.get(), dw.get(), dp.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(disk_out, dk.get(), 8 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hw.data(), dw.get(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hp.data(), dp.get(), sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("roughglass sample: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) {
+            wi[3 * i] = hw[i].x; wi[3 * i + 1] = hw[i].y; wi[3 * i + 2] = hw[i].z;
+            branch[i] = (int32_t)hw[i].w;
+            w[i] = hp[i].x; pdf[i] = hp[i].y;
+        }
+        return RT_OK;
+    });
+}
+
+static int impl_rt_debug_roughglass_eval(rt_ctx* c, float alpha, float er, int n, const float* normal, const float* dir,
+                                         const float* wi, float* fcos, float* pdf) {
+    if (!c || n < 0 || !ggx_alpha_ok(alpha) || !roughglass_er_ok(er) || (n && (!normal || !dir || !wi || !fcos || !pdf)))
+        return c ? fail(c, RT_E_ARG, "roughglass eval: invalid argument") : RT_E_ARG;
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float> dn, dd, dw;
+        DevBuf<float2> dp;
+        if (dn.reserve(3 * (size_t)n) || dd.reserve(3 * (size_t)n) || dw.reserve(3 * (size_t)n) || dp.reserve(n))
+            return fail(c, RT_E_OOM, "roughglass eval buffers");
+        std::vector<float2> hp(n);
+        if (hipMemcpy(dn.get(), normal, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dd.get(), dir, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dw.get(), wi, 12 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_roughglass_eval(c->stream, alpha, er, n, dn.get(), dd.get(), dw.get(), dp.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(hp.data(), dp.get(), sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("roughglass eval: ") + hipGetErrorString(hipGetLastError()));
+        for (int i = 0; i < n; ++i) { fcos[i] = hp[i].x; pdf[i] = hp[i].y; }
+        return RT_OK;
+    });
+}
+
+// launches of the level-3 instantiations by the context's last path pass (render_path counts them)
+static int impl_rt_debug_roughglass_stats(rt_ctx* c, int64_t* launches) {
+    if (!c || !launches) return c ? fail(c, RT_E_ARG, "roughglass stats: NULL") : RT_E_ARG;
+    launches[0] = c->rgl_launches[0];
+    launches[1] = c->rgl_launches[1];
     return RT_OK;
 }
 
@@ -4558,6 +4649,39 @@ int rt_debug_ggx_eval(rt_ctx* c, float alpha, int n, const float* normal, const 
     return entry(c, impl_rt_debug_ggx_eval, alpha, n, normal, dir, wi, fcos, pdf);
 }
 int rt_debug_rough_stats(rt_ctx* c, int64_t* launches) { return entry(c, impl_rt_debug_rough_stats, launches); }
+int rt_roughglass_eval(float alpha, float eta_r, int n, const float* wo, const float* wi, float* fcos, float* pdf) {
+    return guarded([&] {
+        if (n < 0 || !ggx_alpha_ok(alpha) || !roughglass_er_ok(eta_r) || (n && (!wo || !wi || !fcos || !pdf))) return (int)RT_E_ARG;
+        for (int i = 0; i < n; ++i)
+            roughglass_eval(alpha, eta_r, V3{wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]},
+                            V3{wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]}, fcos[i], pdf[i]);
+        return (int)RT_OK;
+    }, [](const std::string&) {});
+}
+int rt_roughglass_sample(float alpha, float eta_r, int n, const float* wo, const float* disk, const float* u, float* wi,
+                         float* w, float* pdf, int32_t* branch) {
+    return guarded([&] {
+        if (n < 0 || !ggx_alpha_ok(alpha) || !roughglass_er_ok(eta_r) ||
+            (n && (!wo || !disk || !u || !wi || !w || !pdf || !branch)))
+            return (int)RT_E_ARG;
+        for (int i = 0; i < n; ++i) {
+            V3 v;
+            branch[i] = roughglass_sample(alpha, eta_r, V3{wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]}, disk[2 * i],
+                                          disk[2 * i + 1], u[i], v, w[i], pdf[i]);
+            wi[3 * i] = v.x; wi[3 * i + 1] = v.y; wi[3 * i + 2] = v.z;
+        }
+        return (int)RT_OK;
+    }, [](const std::string&) {});
+}
+int rt_debug_roughglass_sample(rt_ctx* c, float alpha, float eta_r, int n, const float* normal, const float* dir,
+                               const float* u, float* disk_out, float* wi, float* w, float* pdf, int32_t* branch) {
+    return entry(c, impl_rt_debug_roughglass_sample, alpha, eta_r, n, normal, dir, u, disk_out, wi, w, pdf, branch);
+}
+int rt_debug_roughglass_eval(rt_ctx* c, float alpha, float eta_r, int n, const float* normal, const float* dir,
+                             const float* wi, float* fcos, float* pdf) {
+    return entry(c, impl_rt_debug_roughglass_eval, alpha, eta_r, n, normal, dir, wi, fcos, pdf);
+}
+int rt_debug_roughglass_stats(rt_ctx* c, int64_t* launches) { return entry(c, impl_rt_debug_roughglass_stats, launches); }
 int rt_metal_nk(int metal, int n, const float* lambda, float* n_out, float* k_out) {
     return guarded([&] {
         if (metal < 0 || metal >= kMetals || n < 0 || (n && (!lambda || !n_out || !k_out))) return (int)RT_E_ARG;

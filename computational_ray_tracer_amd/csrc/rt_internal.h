@@ -513,8 +513,9 @@ inline __host__ __device__ int nee_stride(int n_lights) { return 1 + (n_lights +
 // float4s a slot's record holds beyond nee_stride, by the RGH level of the pass's kernels (0 none, 1 rough: DESIGN.md §3k,
 // 2 rough and conductor: §3l): level 2 the lights' clamped wo.h, four per float4, at nee_stride(n); levels 1 and 2 the
 // tail (wb, rough ? 1 : 0, wo.h of the bounce, 0) as the record's last float4
+// (level 3, rough, conductor and rough glass: §3m, is level 2's record; a rough-glass vertex's tail is (w, 2, 0, 0))
 inline __host__ __device__ int nee_extra_f4(int level, int n_lights) {
-    return level == 2 ? 1 + (n_lights + 3) / 4 : level == 1 ? 1 : 0;
+    return level >= 2 ? 1 + (n_lights + 3) / 4 : level == 1 ? 1 : 0;
 }
 enum { N_PO = 0, N_UV = 1 };  // the weights at N_UV + ceil(n / 2)
 struct NeeIO {
@@ -798,6 +799,13 @@ hipError_t launch_ggx_sample(hipStream_t st, float alpha, int n, const float* nr
                              float2* disk, float4* wi, float2* wbpdf);
 hipError_t launch_ggx_eval(hipStream_t st, float alpha, int n, const float* nrm, const float* dir, const float* wi,
                            float2* out);
+// ---- rough glass (rt_roughglass.hip): the level-3 kernels' device functions at a rough-glass vertex, one
+// item per thread.  sample: (nrm, dir, u[3]: the Get2D then the Get1D) -> disk, wi.xyz (world) with wi.w = the branch
+// (0 none, 1 reflected, 2 transmitted), (w, prevPdf); eval: (nrm, dir, wi) -> (fcosF, pdfF).  er: the relative index
+hipError_t launch_roughglass_sample(hipStream_t st, float alpha, float er, int n, const float* nrm, const float* dir,
+                                    const float* u, float2* disk, float4* wi, float2* wpdf);
+hipError_t launch_roughglass_eval(hipStream_t st, float alpha, float er, int n, const float* nrm, const float* dir,
+                                  const float* wi, float2* out);
 // ---- metal (rt_conductor.hip): the level-2 kernels' device functions for a light's wi, one item per
 // thread: (nrm, dir, wi, lambda) -> out[i] = (fcos, pdf, F(lambda, wo.h), wo.h); sp: the context's spectra (its NK table)
 hipError_t launch_conductor_eval(hipStream_t st, const DevSpectra* sp, int metal, float alpha, int n, const float* nrm,

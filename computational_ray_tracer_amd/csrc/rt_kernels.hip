@@ -2617,6 +2617,11 @@ __global__ void __launch_bounds__(kBlock) k_occluded(DevScene sc, int n, const f
 // lights' four per float4 after the weights and the bounce's in the tail, (wb, rough ? 1 : 0, ch_b, 0).  Without a light
 // term the kernel forms beta (F(lambda, ch_b) wb) itself from the vertex's 8 (n, k) (metal_nk_query, rt_fresnel.h).
 // Levels 0 and 1 hold none of it.
+// Level 3 (a scene with an RT_MAT_ROUGH_DIELECTRIC material) is level 2 and the rough glass: such a vertex
+// is a rough vertex whose light weights hold fcosF and whose MIS weights hold pdfF (rt_roughglass.h roughglass_eval, the
+// relative index er = front ? eta : 1 / eta, alpha in c0), and whose bounce takes one more Get1D after the Get2D:
+// roughglass_sample reflects (prevPdf = pdfF) or transmits (prevPdf = 0, the next ray from p - nrm off).  The tail is
+// (w, 2, 0, 0), w with the 1 / er^2 in it; without a light term the kernel forms beta w itself.  Levels 0-2 hold none of it.
 template <int QCAP, int MC, bool TEX = false, int TL = 0, int RGH = 0>
 #ifndef RT_FULL_WAVES
 #define RT_FULL_WAVES RT_MULTI_WAVES  // the mixed-scene shade (variant builds)
@@ -2797,10 +2802,16 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             if (nee.key) neeKey = morton_key(po.x, po.y, po.z, nee.lo, nee.scale, nee.key_bits);
                             bool rough = false;  // (RGH: the vertex's frame and its local wo)
                             bool cnd = false;    // (RGH 2: a conductor, which is rough as well)
+                            bool rgl = false;    // (RGH 3: a rough glass, rough as well; its relative index)
+                            float er = 1.f;
                             V3 ss = v3(0, 0, 0), tt = ss, wol = ss;
                             if constexpr (RGH) {
-                                if constexpr (RGH == 2) cnd = mt.type == 4;
-                                rough = mt.type == 3 || cnd;
+                                if constexpr (RGH >= 2) cnd = mt.type == 4;
+                                if constexpr (RGH == 3) {
+                                    rgl = mt.type == 5;
+                                    if (rgl) er = front ? mt.eta : 1 / mt.eta;
+                                }
+                                rough = mt.type == 3 || cnd || rgl;
                                 if (rough) {
                                     ggx_frame(nrm, ss, tt);
                                     wol = ggx_to_local(v3(-rayd.x, -rayd.y, -rayd.z), ss, tt, nrm);
@@ -2820,7 +2831,10 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                                 const float cs = vdot(nrm, lr.wi);
                                 float fc = cs, bpdf = 0.f;  // (rough: fcos and the GGX pdf for cs and cs / pi)
                                 float chl = 0.f;
-                                if constexpr (RGH == 2) {
+                                if constexpr (RGH == 3) {
+                                    if (rgl) roughglass_eval(mt.c0, er, wol, ggx_to_local(lr.wi, ss, tt, nrm), fc, bpdf);
+                                    else if (rough) ggx_eval_h(mt.eta, wol, ggx_to_local(lr.wi, ss, tt, nrm), fc, bpdf, chl);
+                                } else if constexpr (RGH == 2) {
                                     if (rough) ggx_eval_h(mt.eta, wol, ggx_to_local(lr.wi, ss, tt, nrm), fc, bpdf, chl);
                                 } else if constexpr (RGH) {
                                     if (rough) ggx_eval(mt.eta, wol, ggx_to_local(lr.wi, ss, tt, nrm), fc, bpdf);
@@ -2856,7 +2870,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                                 pu0 = u0;
                                 pu1 = u1;
                                 if (l4 == 3 || li + 1 == nl) reinterpret_cast<float4*>(nwgt)[li >> 2] = make_float4(w0, w1, w2, w3);
-                                if constexpr (RGH == 2) {
+                                if constexpr (RGH >= 2) {
                                     h0 = l4 == 0 ? chl : h0;
                                     h1 = l4 == 1 ? chl : h1;
                                     h2 = l4 == 2 ? chl : h2;
@@ -2873,16 +2887,36 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             bool bounced;
                             float rwb = 0.f;  // (RGH: the rough bounce's weight G2 / G1)
                             float chb = 0.f;  // (RGH 2: the bounce's wo.h)
-                            if (RGH && rough) {
+                            if (RGH == 3 && rgl) {  // the Fresnel choice's Get1D, then reflect or transmit
+                                float dx, dy, rpdf;
+                                disk_concentric(u0, u1, dx, dy);
+                                const float uf = sm.get1d(smp);
+                                V3 wil;
+                                const int br = roughglass_sample(mt.c0, er, wol, dx, dy, uf, wil, rwb, rpdf);
+                                bounced = br != 0;
+                                if (bounced) {
+                                    wi = ggx_to_world(wil, ss, tt, nrm);
+                                    if (!wantNee) {  // (with NEE, k_path_nee forms β w after the light terms)
+#pragma unroll
+                                        for (int i = 0; i < 8; ++i) beta[i] *= rwb;
+                                        rstore8(io.rec, slot, R_BETA, beta);
+                                    }
+                                    const V3 pb = br == 2 ? vsub(p, vmul(nrm, off)) : po;  // (transmitted: the far side)
+                                    wantNext = true;
+                                    nO = make_float4(pb.x, pb.y, pb.z, 0.f);
+                                    nD = make_float4(wi.x, wi.y, wi.z, 0.f);
+                                    misc.y = rpdf;
+                                }
+                            } else if (RGH && rough) {
                                 float dx, dy, rpdf;
                                 disk_concentric(u0, u1, dx, dy);
                                 V3 wil;
-                                if constexpr (RGH == 2) bounced = ggx_sample_disk_h(mt.eta, wol, dx, dy, wil, rwb, rpdf, chb);
+                                if constexpr (RGH >= 2) bounced = ggx_sample_disk_h(mt.eta, wol, dx, dy, wil, rwb, rpdf, chb);
                                 else bounced = ggx_sample_disk(mt.eta, wol, dx, dy, wil, rwb, rpdf);
                                 if (bounced) {
                                     wi = ggx_to_world(wil, ss, tt, nrm);
                                     if (!wantNee) {  // (with NEE, k_path_nee forms β (R wb) after the light terms)
-                                        if (RGH == 2 && cnd) {  // β (F(λ, ch_b) wb): the vertex's 8 (n, k), fetched once
+                                        if (RGH >= 2 && cnd) {  // β (F(λ, ch_b) wb): the vertex's 8 (n, k), fetched once
                                             const int metal = (int)mt.c0;
 #pragma unroll
                                             for (int i = 0; i < 8; ++i) {
@@ -2917,7 +2951,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                             if (wantNee) {
                                 nr[N_PO] = make_float4(po.x, po.y, po.z,
                                                        __uint_as_float(tagid | (bounced ? 0x80000000u : 0u)));
-                                if constexpr (RGH) nr[nee_f4 - 1] = make_float4(rwb, rough ? 1.f : 0.f, chb, 0.f);
+                                if constexpr (RGH) nr[nee_f4 - 1] = make_float4(rwb, rgl ? 2.f : rough ? 1.f : 0.f, chb, 0.f);
                             }
                         }
                         save_sampler(io, slot, sm, io.dim >= 0);
@@ -3008,6 +3042,8 @@ __global__ void __launch_bounds__(kBlock) k_occluded_path(DevScene sc, int n, co
 // RGH == 2: a vertex whose tag names an RT_MAT_CONDUCTOR material (a conductor takes no texture, so its
 // tag is always a material) fetches its 8 (n, k) once; light l's x is beta F(lambda, ch_l), ch_l from the record's float4s
 // after the weights, and its continued throughput beta (F(lambda, ch_b) wb), ch_b from the tail's z.
+// RGH == 3: level 2, and a vertex whose tail names kind 2 (a rough glass): F is a scalar already in the
+// weights, so its x is beta (no R, no 1 / pi) and its continued throughput beta w.
 template <int QCAP, bool FB, bool TEX = false, int TL = 0, int RGH = 0>
 #ifndef RT_NEE_WAVES
 #define RT_NEE_WAVES 4  // (variant builds: Makefile `variants`)
@@ -3103,9 +3139,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             } else {
                 const DevMaterial mt = sc.materials[tag & 0x7fffffffu];
                 rc0 = mt.c0; rc1 = mt.c1; rc2 = mt.c2;
-                if constexpr (RGH == 2) cnd = mt.type == 4;
+                if constexpr (RGH >= 2) cnd = mt.type == 4;
             }
-            if constexpr (RGH == 2) {
+            if constexpr (RGH >= 2) {
                 if (cnd) {
                     const int metal = (int)rc0;
 #pragma unroll
@@ -3121,11 +3157,13 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             float4 rg = make_float4(0.f, 0.f, 0.f, 0.f);
             if constexpr (RGH) rg = r[nf4 - 1];
             const bool rough = RGH && rg.y != 0.f;
+            const bool rgl = RGH == 3 && rg.y == 2.f;
             if (vis) {
                 float L[8], x[8];
                 rload8(io.rec, slot, R_L, L);
 #pragma unroll
-                for (int i = 0; i < 8; ++i) x[i] = RGH && rough ? beta[i] * R[i] : beta[i] * (R[i] * InvPi);
+                for (int i = 0; i < 8; ++i)
+                    x[i] = RGH == 3 && rgl ? beta[i] : RGH && rough ? beta[i] * R[i] : beta[i] * (R[i] * InvPi);
                 float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);  // the weights again, four per 16-B load
                 float4 c4 = w4;                               // (RGH 2: the lights' wo.h the same way)
                 int wq = -1;
@@ -3136,11 +3174,11 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
                     if ((li >> 2) != wq) {
                         wq = li >> 2;
                         w4 = reinterpret_cast<const float4*>(wg)[wq];
-                        if constexpr (RGH == 2) c4 = r[nee_stride(nl) + wq];
+                        if constexpr (RGH >= 2) c4 = r[nee_stride(nl) + wq];
                     }
                     const int l4 = li & 3;
                     const float wgt = l4 == 0 ? w4.x : l4 == 1 ? w4.y : l4 == 2 ? w4.z : w4.w;
-                    if constexpr (RGH == 2) {
+                    if constexpr (RGH >= 2) {
                         if (cnd) {  // x_l = β F(λ, ch_l)
                             const float chl = l4 == 0 ? c4.x : l4 == 1 ? c4.y : l4 == 2 ? c4.z : c4.w;
 #pragma unroll
@@ -3165,7 +3203,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QCA
             if (bounced) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
-                    if (RGH == 2 && cnd) beta[i] *= (fresnel_conductor(rg.z, cn[i], ck[i]) * rg.x);
+                    if (RGH == 3 && rgl) beta[i] *= rg.x;
+                    else if (RGH >= 2 && cnd) beta[i] *= (fresnel_conductor(rg.z, cn[i], ck[i]) * rg.x);
                     else beta[i] *= RGH && rough ? R[i] * rg.x : R[i];
                 }
                 rstore8(io.rec, slot, R_BETA, beta);
@@ -3460,12 +3499,12 @@ hipError_t launch_path_shade(hipStream_t st, int grid, int qcap, const DevScene&
         const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);
         // a scene with a rough material (NeeIO ml bit 2): the RGH instantiations, except for the specular bin; with a
         // conductor (bit 3): level 2
-        const int rg = (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;
+        const int rg = (nee.ml & 16) ? 3 : (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;  // (bit 4: a rough glass, level 3)
 #define RT_SHADE_FULL_R(Q, M, R) \
     (v == 0 ? k_path_shade_full<Q, M, false, 0, R> : v == 1 ? k_path_shade_full<Q, M, true, 0, R> \
      : v == 2 ? k_path_shade_full<Q, M, false, 1, R> : v == 3 ? k_path_shade_full<Q, M, true, 1, R> \
      : v == 4 ? k_path_shade_full<Q, M, false, 2, R> : k_path_shade_full<Q, M, true, 2, R>)
-#define RT_SHADE_FULL(Q, M) (rg == 2 ? RT_SHADE_FULL_R(Q, M, 2) : rg ? RT_SHADE_FULL_R(Q, M, 1) : RT_SHADE_FULL_R(Q, M, 0))
+#define RT_SHADE_FULL(Q, M) (rg == 3 ? RT_SHADE_FULL_R(Q, M, 3) : rg == 2 ? RT_SHADE_FULL_R(Q, M, 2) : rg ? RT_SHADE_FULL_R(Q, M, 1) : RT_SHADE_FULL_R(Q, M, 0))
         switch (qcap) {
             case 0: k = matclass == 1 ? RT_SHADE_FULL(0, 1) : matclass == 2 ? RT_SHADE_FULL_R(0, 2, 0) : RT_SHADE_FULL(0, 0); break;
             case 1: k = RT_SHADE_FULL(1, 0); break;
@@ -3496,12 +3535,12 @@ hipError_t launch_path_nee(hipStream_t st, int grid, int qcap, const DevScene& s
     if (qcap != 1 && (!nee.fb_slot || !nee.fb_len)) return hipErrorInvalidValue;  // the fallback list is required
     void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
     const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);  // (as launch_path_shade)
-    const int rg = (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;  // (as launch_path_shade)
+    const int rg = (nee.ml & 16) ? 3 : (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;  // (as launch_path_shade)
 #define RT_NEE_R(Q, R) \
     (v == 0 ? k_path_nee<Q, false, false, 0, R> : v == 1 ? k_path_nee<Q, false, true, 0, R> \
      : v == 2 ? k_path_nee<Q, false, false, 1, R> : v == 3 ? k_path_nee<Q, false, true, 1, R> \
      : v == 4 ? k_path_nee<Q, false, false, 2, R> : k_path_nee<Q, false, true, 2, R>)
-#define RT_NEE(Q) (rg == 2 ? RT_NEE_R(Q, 2) : rg ? RT_NEE_R(Q, 1) : RT_NEE_R(Q, 0))
+#define RT_NEE(Q) (rg == 3 ? RT_NEE_R(Q, 3) : rg == 2 ? RT_NEE_R(Q, 2) : rg ? RT_NEE_R(Q, 1) : RT_NEE_R(Q, 0))
     switch (qcap) {
         case 0: k = RT_NEE(0); break;
         case 1: k = RT_NEE(1); break;
@@ -3520,12 +3559,12 @@ hipError_t launch_path_nee_fallback(hipStream_t st, int grid, int qcap, const De
     const int gb = ring_clamp(std::min(grid > 0 ? grid : 1, kFallbackBlocks), qcap, sc);
     void (*k)(DevScene, const DevSpectra*, PathIO, NeeIO, unsigned long long*);
     const int v = (nee.tex ? 1 : 0) | (nee.ml & 2 ? 4 : nee.ml ? 2 : 0);
-    const int rg = (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;
+    const int rg = (nee.ml & 16) ? 3 : (nee.ml & 8) ? 2 : (nee.ml & 4) ? 1 : 0;
 #define RT_NEE_FB_R(Q, R) \
     (v == 0 ? k_path_nee<Q, true, false, 0, R> : v == 1 ? k_path_nee<Q, true, true, 0, R> \
      : v == 2 ? k_path_nee<Q, true, false, 1, R> : v == 3 ? k_path_nee<Q, true, true, 1, R> \
      : v == 4 ? k_path_nee<Q, true, false, 2, R> : k_path_nee<Q, true, true, 2, R>)
-#define RT_NEE_FB(Q) (rg == 2 ? RT_NEE_FB_R(Q, 2) : rg ? RT_NEE_FB_R(Q, 1) : RT_NEE_FB_R(Q, 0))
+#define RT_NEE_FB(Q) (rg == 3 ? RT_NEE_FB_R(Q, 3) : rg == 2 ? RT_NEE_FB_R(Q, 2) : rg ? RT_NEE_FB_R(Q, 1) : RT_NEE_FB_R(Q, 0))
     switch (qcap) {
         case 0: k = RT_NEE_FB(0); break;
         case 16: k = RT_NEE_FB(16); break;

@@ -114,16 +114,21 @@ struct PassFacts {
     bool environment = false;
     bool rough = false;        // a non-emissive RT_MAT_ROUGH material (it also makes the scene full)
     bool conductor = false;    // a non-emissive RT_MAT_CONDUCTOR material (it makes the scene full too)
+    bool rough_dielectric = false;  // a non-emissive RT_MAT_ROUGH_DIELECTRIC material (§3m; it makes the scene full too)
     PassIntegrator integ = kIntegReference;
     int max_depth = 0;
     int n_work = 0, ib = 0, ie = 0;
 };
 
 // The material bin of a material (DevMaterial cls, kMatClasses) by its rt_material type and whether it emits: 0 = the bin
-// that reads spectra and writes NEE records (an emitter, Lambert 0, rough 3, conductor 4), 1 = the specular bin (mirror 1,
-// glass 2), whose kernels hold no RGH code.  rough_fact: the material makes the scene's `rough` fact (an emitter of type 3
-// does not); conductor_fact: its `conductor` fact (a non-emissive type 4 alone).
-inline int material_class(int type, bool emissive) { return emissive || type == 0 || type == 3 || type == 4 ? 0 : 1; }
+// that reads spectra and writes NEE records (an emitter, Lambert 0, rough 3, conductor 4, rough glass 5), 1 = the specular
+// bin (mirror 1, glass 2), whose kernels hold no RGH code.  rough_fact: the material makes the scene's `rough` fact (an
+// emitter of type 3 does not); conductor_fact: its `conductor` fact (a non-emissive type 4 alone); rough_dielectric_fact:
+// its `rough_dielectric` fact (a non-emissive type 5 alone).
+inline int material_class(int type, bool emissive) {
+    return emissive || type == 0 || type == 3 || type == 4 || type == 5 ? 0 : 1;
+}
+inline bool rough_dielectric_fact(int type, bool emissive) { return type == 5 && !emissive; }
 inline bool rough_fact(int type, bool emissive) { return type == 3 && !emissive; }
 inline bool conductor_fact(int type, bool emissive) { return type == 4 && !emissive; }
 
@@ -212,7 +217,7 @@ struct PathPlan {
     // mixed multi-level scenes: the trace kernel bins the hits by material class and each class is shaded by a kernel
     // holding only its materials' code (k_path_shade_full<Q, 1 / 2>)
     bool bins = false;
-    // NeeIO ml: bit 0 the scene has a mesh light, bit 1 an environment light, bit 2 = rgh, bit 3 = cnd
+    // NeeIO ml: bit 0 the scene has a mesh light, bit 1 an environment light, bit 2 = rgh, bit 3 = cnd, bit 4 = rgl
     int ml = 0;
     // a rough material: the RGH instantiations of k_path_shade_full (classes 0 and 1) and k_path_nee,
     // whose NEE record is one float4 longer
@@ -221,6 +226,9 @@ struct PathPlan {
     // rough vertex in its control flow); the NEE record also holds the lights' wo.h, four per float4 (nee_extra_f4)
     bool cnd = false;
     bool env = false;          // an environment light is bound: every traced depth ends with the miss stage
+    // a rough-glass material: RGH level 3 of the same kernels, whatever else the scene holds.  rgl implies
+    // rgh; the NEE record is level 2's (cnd stays the scene's own conductor fact)
+    bool rgl = false;
     // slot state layout (rt_internal.h RecView): records for multi-level scenes (sorted, scattered slots), SoA for
     // single-leaf ones (slots stay in queue order)
     bool records = false;
@@ -255,8 +263,9 @@ struct PathPlan {
     }
 };
 
-// the RGH level of the pass's kernels: 0 none, 1 rough, 2 rough and conductor (it sizes the NEE record: nee_extra_f4)
-inline int rgh_level(const PathPlan& p) { return p.cnd ? 2 : p.rgh ? 1 : 0; }
+// the RGH level of the pass's kernels: 0 none, 1 rough, 2 rough and conductor, 3 those and rough glass (it sizes the NEE
+// record: nee_extra_f4)
+inline int rgh_level(const PathPlan& p) { return p.rgl ? 3 : p.cnd ? 2 : p.rgh ? 1 : 0; }
 
 inline PathPlan plan_path(const PassFacts& f, const Knobs& kn, const BatchPlan& b) {
     PathPlan p;
@@ -274,8 +283,9 @@ inline PathPlan plan_path(const PassFacts& f, const Knobs& kn, const BatchPlan& 
     p.bins = p.nee && multi && kn.mat_bins;
     p.env = f.environment && b.path;
     p.cnd = f.conductor && b.path;
-    p.rgh = (f.rough && b.path) || p.cnd;
-    p.ml = (f.mesh_light ? 1 : 0) | (p.env ? 2 : 0) | (p.rgh ? 4 : 0) | (p.cnd ? 8 : 0);
+    p.rgl = f.rough_dielectric && b.path;
+    p.rgh = (f.rough && b.path) || p.cnd || p.rgl;
+    p.ml = (f.mesh_light ? 1 : 0) | (p.env ? 2 : 0) | (p.rgh ? 4 : 0) | (p.cnd ? 8 : 0) | (p.rgl ? 16 : 0);
     p.records = multi;
     p.rec_fs = p.records ? 1 : b.nmax;
     p.rec_ss = p.records ? (unsigned)kRecF4 : 1u;

@@ -269,6 +269,47 @@ class Renderer:
         self._chk("rt_debug_conductor_stats", self.lib.rt_debug_conductor_stats(self.h, n))
         return int(n[0]) + int(n[1])
 
+    # ---- rough glass (capi.RT_MAT_ROUGH_DIELECTRIC) -----------------------------------------------
+    def roughglass_sample(self, alpha, eta_r, normal, dirs, u):
+        """rt_debug_roughglass_sample: the level-3 shade kernel's bounce at a rough-glass vertex for shading-side normals
+        (n, 3), incoming ray directions (n, 3) and u (n, 3): the bounce's Get2D then the Fresnel choice's Get1D
+        -> dict(disk (n, 2), wi (n, 3) world, w (n), pdf (n), branch (n): 0 none, 1 reflected, 2 transmitted)."""
+        nr = np.ascontiguousarray(normal, np.float32)
+        d = np.ascontiguousarray(dirs, np.float32)
+        u = np.ascontiguousarray(u, np.float32)
+        n = len(nr)
+        assert nr.shape == (n, 3) and d.shape == (n, 3) and u.shape == (n, 3)
+        disk, wi = np.zeros((n, 2), np.float32), np.zeros((n, 3), np.float32)
+        w, pdf, br = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_roughglass_sample", self.lib.rt_debug_roughglass_sample(
+            self.h, float(alpha), float(eta_r), n, nr.ctypes.data_as(F), d.ctypes.data_as(F), u.ctypes.data_as(F),
+            disk.ctypes.data_as(F), wi.ctypes.data_as(F), w.ctypes.data_as(F), pdf.ctypes.data_as(F),
+            br.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(disk=disk, wi=wi, w=w, pdf=pdf, branch=br)
+
+    def roughglass_eval(self, alpha, eta_r, normal, dirs, wi):
+        """rt_debug_roughglass_eval: the level-3 kernels' light term at a rough-glass vertex for normals (n, 3), incoming
+        ray directions (n, 3) and world-space light directions wi (n, 3) -> dict(fcos (n), pdf (n)): fcosF, pdfF."""
+        nr = np.ascontiguousarray(normal, np.float32)
+        d = np.ascontiguousarray(dirs, np.float32)
+        w = np.ascontiguousarray(wi, np.float32)
+        n = len(nr)
+        assert nr.shape == (n, 3) and d.shape == (n, 3) and w.shape == (n, 3)
+        fcos, pdf = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_roughglass_eval", self.lib.rt_debug_roughglass_eval(
+            self.h, float(alpha), float(eta_r), n, nr.ctypes.data_as(F), d.ctypes.data_as(F), w.ctypes.data_as(F),
+            fcos.ctypes.data_as(F), pdf.ctypes.data_as(F)))
+        return dict(fcos=fcos, pdf=pdf)
+
+    def roughglass_launches(self):
+        """rt_debug_roughglass_stats: launches of the level-3 (rough, conductor and rough glass) instantiations of
+        k_path_shade_full and k_path_nee by the last path pass, summed (0 for a scene without a rough glass)."""
+        n = (C.c_int64 * 2)()
+        self._chk("rt_debug_roughglass_stats", self.lib.rt_debug_roughglass_stats(self.h, n))
+        return int(n[0]) + int(n[1])
+
     def set_shard(self, tile_size, n_shards, shard_id):
         self._chk("rt_set_shard",self.lib.rt_set_shard(self.h, tile_size, n_shards, shard_id))
 

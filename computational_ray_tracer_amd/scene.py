@@ -644,6 +644,49 @@ def fresnel_conductor(cos, n, k):
     return out
 
 
+def rough_glass(eta, alpha):
+    """The material tuple of a rough glass (capi.RT_MAT_ROUGH_DIELECTRIC): a constant index eta > 1 of the
+    side the geometric normal points away from (rt_material.eta) and GGX roughness alpha in [0.01, 1] (sigmoid[0]); the
+    other two coefficients are 0."""
+    return ((float(alpha), 0.0, 0.0), 0.0, capi.RT_MAT_ROUGH_DIELECTRIC, float(eta))
+
+
+def roughglass_eval(alpha, eta_r, wo, wi):
+    """rt_roughglass_eval (host only): local wo, wi (n, 3) and the relative index eta_r of the shading side ->
+    (fcosF (n), pdfF (n)): F(wo.h, eta_r) times rt_ggx_eval's values, 0 when wi.z <= 0."""
+    wo = np.ascontiguousarray(wo, np.float32)
+    wi = np.ascontiguousarray(wi, np.float32)
+    n = len(wo)
+    assert wo.shape == (n, 3) and wi.shape == (n, 3)
+    fcos, pdf = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    F = C.POINTER(C.c_float)
+    r = capi.load_library().rt_roughglass_eval(float(alpha), float(eta_r), n, wo.ctypes.data_as(F), wi.ctypes.data_as(F),
+                                               fcos.ctypes.data_as(F), pdf.ctypes.data_as(F))
+    if r != capi.RT_OK:
+        raise capi.RTError("rt_roughglass_eval", r, "alpha in [0.01, 1], eta_r finite and > 0, non-NULL pointers")
+    return fcos, pdf
+
+
+def roughglass_sample(alpha, eta_r, wo, disk, u):
+    """rt_roughglass_sample (host only): local wo (n, 3), disk points (n, 2) and the Fresnel choice's u (n) ->
+    (wi (n, 3), w (n), prevPdf (n), branch (n) int32: 0 none, 1 reflected, 2 transmitted)."""
+    wo = np.ascontiguousarray(wo, np.float32)
+    disk = np.ascontiguousarray(disk, np.float32)
+    u = np.ascontiguousarray(u, np.float32)
+    n = len(wo)
+    assert wo.shape == (n, 3) and disk.shape == (n, 2) and u.shape == (n,)
+    wi, w, pdf = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    br = np.zeros(n, np.int32)
+    F = C.POINTER(C.c_float)
+    r = capi.load_library().rt_roughglass_sample(float(alpha), float(eta_r), n, wo.ctypes.data_as(F),
+                                                 disk.ctypes.data_as(F), u.ctypes.data_as(F), wi.ctypes.data_as(F),
+                                                 w.ctypes.data_as(F), pdf.ctypes.data_as(F),
+                                                 br.ctypes.data_as(C.POINTER(C.c_int32)))
+    if r != capi.RT_OK:
+        raise capi.RTError("rt_roughglass_sample", r, "alpha in [0.01, 1], eta_r finite and > 0, non-NULL pointers")
+    return wi, w, pdf, br
+
+
 def _flat_mesh(faces_xyz):
     """(nt, 3, 3) float64 corner positions -> one-vertex-per-corner float32 mesh with flat normals."""
     p = np.asarray(faces_xyz, dtype=np.float64)

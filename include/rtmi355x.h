@@ -59,7 +59,8 @@ typedef struct { float r, g, b, w; } rt_pixel;
  * sum = sum + v and sumsq = sumsq + v * v for every sample, in the film's index order (float32, nothing fused). */
 typedef struct { float sum, sumsq; } rt_moment;
 
-enum { RT_MAT_DIFFUSE = 0, RT_MAT_MIRROR = 1, RT_MAT_DIELECTRIC = 2, RT_MAT_ROUGH = 3, RT_MAT_CONDUCTOR = 4 };
+enum { RT_MAT_DIFFUSE = 0, RT_MAT_MIRROR = 1, RT_MAT_DIELECTRIC = 2, RT_MAT_ROUGH = 3, RT_MAT_CONDUCTOR = 4,
+       RT_MAT_ROUGH_DIELECTRIC = 5 };
 /* the metal of an RT_MAT_CONDUCTOR material, carried as a float in rt_material.sigmoid[0] */
 enum { RT_METAL_AG = 0, RT_METAL_AL = 1, RT_METAL_AU = 2, RT_METAL_CU = 3 };
 /* Build-defined material (the reference has none: Shading.h:1-21 is a comment stub).
@@ -95,7 +96,8 @@ enum { RT_METAL_AG = 0, RT_METAL_AL = 1, RT_METAL_AU = 2, RT_METAL_CU = 3 };
  *   RT_INTEGRATOR_REFERENCE never sees materials; the feature, position and chain passes end a chain on a rough surface,
  *   as on a Lambert one; rt_render_features_albedo demodulates it by A of its material or texel, as Lambert (exact: f
  *   is R(lambda) times a scalar).  Limits: no transmission, no anisotropy, no angle-dependent Fresnel on this material
- *   (RT_MAT_CONDUCTOR below has the conductor's), no multiple-scattering compensation, no roughness textures.
+ *   (RT_MAT_CONDUCTOR below has the conductor's; RT_MAT_ROUGH_DIELECTRIC the dielectric's, with transmission), no
+ *   multiple-scattering compensation, no roughness textures.
  * CONDUCTOR (additive): a metal: ROUGH's GGX lobe with the exact unpolarised conductor Fresnel term of a
  *   measured complex index n + i k in place of R(lambda).  `eta` is the roughness alpha, with ROUGH's rule (RT_E_ARG
  *   unless finite and in [0.01, 1], "alpha" in rt_last_error); sigmoid[0] is the metal as a float (RT_METAL_AG = 0,
@@ -119,6 +121,30 @@ enum { RT_METAL_AG = 0, RT_METAL_AL = 1, RT_METAL_AU = 2, RT_METAL_CU = 3 };
  *   its entry of the albedo table is (1, 1, 1), so rt_render_features_albedo leaves it un-demodulated (its colour
  *   depends on the angle); the feature, position and chain passes end a chain on it, as on ROUGH.  Limits: no smooth conductor
  *   (alpha < 0.01) in the specular bin, no tints or textures, no user-supplied n, k, no multiple-scattering compensation.
+ * ROUGH_DIELECTRIC (additive): rough glass, the non-absorbing rough interface of Walter et al. 2007 with
+ *   ROUGH's isotropic GGX.  `eta` is the index of the side the geometric normal points away from, as DIELECTRIC's, and
+ *   must be finite and > 1; eta == 0 (dispersive BK7) is refused for this type.  sigmoid[0] is the roughness alpha with
+ *   ROUGH's rule ([0.01, 1], "alpha" in rt_last_error); sigmoid[1] and sigmoid[2] must be 0; anything else is RT_E_ARG and
+ *   the scene bound before stays.  An emissive material's fields are not validated or read.
+ *   Vectors local to ROUGH's frame of the shading-side normal (wo.z > 0); er = front ? eta : 1 / eta.  Only + - * /, sqrtf
+ *   and comparisons, float32 in the order written, nothing fused:
+ *     F(c, er): c = fminf(fmaxf(c, 0), 1); s2t = (1 - c c) / (er er); 1 when s2t >= 1; ct = sqrtf(max(1 - s2t, 0));
+ *               rp = (er c - ct) / (er c + ct); rs = (c - er ct) / (c + er ct); F = (rp rp + rs rs) / 2
+ *     light (reflection side only; the cs > 0 test refuses a light below): with ROUGH's fcos, pdf and ch = the clamped
+ *               wo.h of (wo, wi): fcosF = F(ch, er) fcos in the light weight, pdfF = F(ch, er) pdf in every power heuristic
+ *     bounce:   one Get2D per light in list order, one Get2D for the disk point, then one Get1D u.  h = ROUGH's visible
+ *               normal; c = wo.h; F = F(c, er).
+ *               u < F: wi = (2 c) h - wo, none when wi.z <= 0; weight G2(wo, wi) / G1(wo); prevPdf = F (G1 D / (4 wo.z))
+ *               else:  s2t = max(1 - c c, 0) / (er er); ct = sqrtf(max(1 - s2t, 0)); wt = -wo / er + (c / er - ct) h,
+ *                      none unless wt.z < 0; weight (G2(wo, wt) / G1(wo)) / (er er), Lambda(wt) from wt.z^2;
+ *                      prevPdf = 0 (the next emitter or environment hit counts in full); the next ray starts at p - nrm off
+ *   Both weights are f |mu_i| / pdf of the whole BSDF (reflection F D G2 / (4 mu_o mu_i) plus Walter's transmission term)
+ *   under "visible normal, then Fresnel choice"; the 1 / er^2 is DIELECTRIC's radiance scaling.  The reflection
+ *   hemisphere is covered by NEE plus the sampled emitter or environment hit under the power heuristic with pdfF; the
+ *   transmission hemisphere by the sampled direction alone.  No texture binds to it (RT_E_ARG); its albedo-table entry is
+ *   (1, 1, 1); the feature, position and chain passes end a chain on it.  Limits: constant eta only, no absorption or
+ *   tint, no NEE through the interface (delta lights reach the reflection lobe only, shadow rays stop at glass), single
+ *   scattering, no roughness textures.
  * emission_scale > 0 makes the surface a pure one-sided emitter with Le = scale · stdillum-D65. */
 typedef struct {
     int type;
@@ -680,6 +706,29 @@ int rt_debug_ggx_eval(rt_ctx* ctx, float alpha, int n, const float* normal, cons
 /* launches[2]: launches of the RGH instantiations of k_path_shade_full and of k_path_nee (the fallback included) by the
  * context's last path pass (0, 0 for a scene without a rough material). */
 int rt_debug_rough_stats(rt_ctx* ctx, int64_t* launches);
+
+/* ---- rough glass (additive): RT_MAT_ROUGH_DIELECTRIC above --------------------------------------
+ * rt_roughglass_eval / rt_roughglass_sample (host only, no context): the header's functions on vectors local to the
+ * shading frame.  eval: wo, wi (3n each) -> fcosF, pdfF (n).  sample: wo (3n), disk points (2n), u (n) -> wi (3n), the
+ * weight w (n, the 1 / eta_r^2 in it when transmitted), prevPdf (n) and branch (n): 0 none, 1 reflected, 2 transmitted.
+ * eta_r is the relative index of the shading side (eta on the front side, 1 / eta on the back).  RT_E_ARG: alpha outside
+ * [0.01, 1], eta_r not finite and positive, a negative count, a NULL pointer with a positive count. */
+int rt_roughglass_eval(float alpha, float eta_r, int n, const float* wo, const float* wi, float* fcos, float* pdf);
+int rt_roughglass_sample(float alpha, float eta_r, int n, const float* wo, const float* disk, const float* u, float* wi,
+                         float* w, float* pdf, int32_t* branch);
+/* The path kernels' own device functions at a rough-glass vertex, one item per thread, on world-space vectors as
+ * rt_debug_ggx_sample / rt_debug_ggx_eval: normal (the shading-side normal), dir (the incoming ray) (3n each);
+ * sample: u (3n: the bounce's Get2D, then its Get1D) -> disk_out (2n), wi (3n, world), w, pdf, branch (n);
+ * eval: wi (3n, world) -> fcos, pdf (n). */
+int rt_debug_roughglass_sample(rt_ctx* ctx, float alpha, float eta_r, int n, const float* normal, const float* dir,
+                               const float* u, float* disk_out, float* wi, float* w, float* pdf, int32_t* branch);
+int rt_debug_roughglass_eval(rt_ctx* ctx, float alpha, float eta_r, int n, const float* normal, const float* dir,
+                             const float* wi, float* fcos, float* pdf);
+/* launches[2]: launches of the level-3 (rough, conductor and rough glass) instantiations of k_path_shade_full and of
+ * k_path_nee (the fallback included) by the context's last path pass (0, 0 for a scene without a rough glass).  On such
+ * a pass rt_debug_rough_stats counts the same launches (level 3 is an RGH level), and rt_debug_conductor_stats counts
+ * them only when the scene also holds a conductor. */
+int rt_debug_roughglass_stats(rt_ctx* ctx, int64_t* launches);
 
 /* ---- metal (additive): RT_MAT_CONDUCTOR above ------------------------------------------
  * rt_metal_nk (host only, no context): the dense table's entry of metal (RT_METAL_*) at the dense spectra's index of
