@@ -174,6 +174,11 @@ class rt_environment_desc(C.Structure):
                 ("world_to_env", F9), ("reserved", C.c_int * 4)]
 
 
+class rt_medium(C.Structure):
+    """An absorbing medium of a glass material: sigma_a(lambda) = sigma * sigmoid(lambda)."""
+    _fields_ = [("sigmoid", F3), ("sigma", C.c_float)]
+
+
 class rt_albedo(C.Structure):
     """Albedo film entry: sums over the first hits of a feature pass."""
     _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("hits", C.c_float)]
@@ -209,6 +214,7 @@ EXPORTS = [
     "rt_metal_nk", "rt_fresnel_conductor", "rt_debug_conductor_eval", "rt_debug_conductor_stats",
     "rt_roughglass_eval", "rt_roughglass_sample", "rt_debug_roughglass_sample", "rt_debug_roughglass_eval",
     "rt_debug_roughglass_stats",
+    "rt_scene_set_media", "rt_medium_transmittance", "rt_debug_medium_eval", "rt_debug_medium_stats",
 ]
 
 _lib = None
@@ -349,6 +355,10 @@ def load_library(path=None):
         "rt_debug_roughglass_eval": ([C.c_void_p, C.c_float, C.c_float, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float),
                                       P(C.c_float), P(C.c_float)], C.c_int),
         "rt_debug_roughglass_stats": ([C.c_void_p, P(C.c_int64)], C.c_int),
+        "rt_scene_set_media": ([C.c_void_p, P(rt_medium), C.c_int], C.c_int),
+        "rt_medium_transmittance": ([P(rt_medium), C.c_int, P(C.c_float), P(C.c_float), P(C.c_float)], C.c_int),
+        "rt_debug_medium_eval": ([C.c_void_p, P(rt_medium), C.c_int, P(C.c_float), P(C.c_float), P(C.c_float)], C.c_int),
+        "rt_debug_medium_stats": ([C.c_void_p, P(C.c_int), P(C.c_ulonglong)], C.c_int),
     }
     # RTMI_AB_COMPAT=1 (A/B tooling only: scripts/gpu_ab_sets.sh timing an earlier build through RTMI_LIB) accepts an
     # older ABI and skips entry points it lacks; the rt_stats fields it predates read as 0

@@ -599,6 +599,20 @@ struct rt_ctx {
         std::vector<unsigned char> mat_flags;
         size_t n_texels = 0;
     } tx;
+    // absorbing media of the uploaded scene (rt_scene_set_media): bound = one entry per material, table =
+    // their (c0, c1, c2, sigma) on the device, live = some sigma > 0, so depths >= 1 of a path pass run k_medium_absorb.
+    // mat_type / mat_emits: per material of the scene, what rt_scene_set_media validates against.  ctr: the stage's
+    // spread segment counter, zeroed per path pass; launches: the last path pass's launches of the stage.
+    struct Media {
+        bool live = false;
+        std::vector<rt_medium> bound;
+        DevBuf<float4> table;
+        DevBuf<unsigned long long> ctr;
+        std::vector<int> mat_type;
+        std::vector<unsigned char> mat_emits;
+        int launches = 0;
+        bool counted = false;  // the last path pass ran the stage: ctr holds its segments (else they are 0)
+    } med;
     // albedo demodulation: the sensor albedo of the scene's materials, then of its texels, 16 B per
     // entry; built on first use and again after rt_scene_upload, rt_scene_set_textures or rt_film_set
     struct Albedo {
@@ -737,9 +751,19 @@ void free_environment(rt_ctx* c) {
     c->env = rt_ctx::Environment{};
 }
 
+// (the counter stays: it belongs to the context)
+void free_media(rt_ctx* c) {
+    c->med.live = false;
+    c->med.bound.clear();
+    c->med.table.reset();
+}
+
 void free_scene(rt_ctx* c) {
     free_textures(c);
     free_environment(c);
+    free_media(c);
+    c->med.mat_type.clear();
+    c->med.mat_emits.clear();
     c->h_lights.clear();
     c->base_lights = nullptr;
     c->tx.mat_flags.clear();
@@ -1217,6 +1241,7 @@ PassFacts pass_facts(const rt_ctx* c, int n_work, int ib, int ie) {
     f.rough = c->scene_rough;
     f.conductor = c->scene_conductor;
     f.rough_dielectric = c->scene_rough_dielectric;
+    f.media = c->med.live;
     f.integ = c->integ.kind == RT_INTEGRATOR_PATH_MIS ? kIntegPathMis
               : c->integ.kind == RT_INTEGRATOR_PATH   ? kIntegPath : kIntegReference;
     f.max_depth = c->integ.max_depth;
@@ -1413,6 +1438,22 @@ int stage_trace(const PathPass& p, const Lane& L, Bounce& bo) {
     return trace_with_fallback(c, L.s, L.sc, tio, d.trace_fallback);
 }
 
+// the media's absorb stage of this depth: over the queue the trace just wrote, before the shade (and
+// before k_bin_materials) reads beta, so the vertex's own light terms carry the attenuation.  Timed with the shade stage,
+// as the miss stage is.
+int stage_absorb(const PathPass& p, const Lane& L, const Bounce& bo) {
+    rt_ctx* c = p.c;
+    if (!bo.d.absorb) return RT_OK;
+    const Batch& b = L.w->b;
+    const MediumIO mio{bo.qv, bo.cO, b.hitB.get(), b.hitPrim.get(), L.rv, bo.depth, L.sc.triWorld, L.sc.triMaterial,
+                       L.sc.shapes, L.sc.n_tris, c->med.table.get(), (int)c->med.bound.size(), c->med.ctr.get()};
+    hipEvent_t e0 = ev_start(c, L.s);
+    HIPCHK(c, launch_medium_absorb(L.s, c->grid, mio));
+    ++c->med.launches;
+    ev_mark(c, L.s, ST_SHADE, e0);
+    return RT_OK;
+}
+
 // the shade's arguments over the traced rays: PathIO, the shadow queue, the NEE queue
 void shade_io(const PathPass& p, const Lane& L, Bounce& bo) {
     const rt_ctx* c = p.c;
@@ -1565,6 +1606,12 @@ int render_path(rt_ctx* c, const PassFacts& f, const BatchPlan& bp, int ib, int 
     c->rgh_launches[0] = c->rgh_launches[1] = 0;
     c->cnd_launches[0] = c->cnd_launches[1] = 0;
     c->rgl_launches[0] = c->rgl_launches[1] = 0;
+    c->med.launches = 0;
+    c->med.counted = p.pp.med;
+    if (p.pp.med) {  // the segment counter of this pass (ahead of every lane: they start after st)
+        HIPCHK(c, c->med.ctr.reserve(kMediumCtrWords));
+        HIPCHK(c, hipMemsetAsync(c->med.ctr.get(), 0, kMediumCtrWords * sizeof(unsigned long long), st));
+    }
     if ((rc = path_workspaces(p))) return rc;
     if (lanes > 1) {  // lanes 1.. start after the caller's earlier work on st
         HIPCHK(c, hipEventRecord(c->ws[0].film_done, st));
@@ -1580,7 +1627,8 @@ int render_path(rt_ctx* c, const PassFacts& f, const BatchPlan& bp, int ib, int 
             for (int l = 0; l < n; ++l) {
                 Lane& L = lane[l];
                 Bounce bo{depth, p.pp.at(depth)};
-                if ((rc = stage_trace(p, L, bo)) || (rc = stage_shade(p, L, bo)) || (rc = stage_env_miss(p, L, bo)) ||
+                if ((rc = stage_trace(p, L, bo)) || (rc = stage_absorb(p, L, bo)) || (rc = stage_shade(p, L, bo)) ||
+                    (rc = stage_env_miss(p, L, bo)) ||
                     (rc = stage_nee(p, L, bo)) ||
                     (rc = stage_shadow(p, L, bo)))
                     return rc;
@@ -2564,6 +2612,12 @@ static int scene_upload_one(rt_ctx* c, const rt_scene_desc* s) {
         c->tx.mat_flags[i] = shade.mats[i].emit > 0 ? 1 : shade.mats[i].type == RT_MAT_CONDUCTOR ? 4
                              : shade.mats[i].type == RT_MAT_ROUGH_DIELECTRIC ? 8 : 0;
     for (const DevShape& h : shade.shapes) c->tx.mat_flags[h.material] |= 2;
+    c->med.mat_type.resize(shade.mats.size());
+    c->med.mat_emits.resize(shade.mats.size());
+    for (size_t i = 0; i < shade.mats.size(); ++i) {
+        c->med.mat_type[i] = shade.mats[i].type;
+        c->med.mat_emits[i] = shade.mats[i].emit > 0 ? 1 : 0;
+    }
     return RT_OK;
 }
 
@@ -4296,6 +4350,88 @@ static int impl_rt_debug_roughglass_stats(rt_ctx* c, int64_t* launches) {
     return RT_OK;
 }
 
+// ---- absorbing media
+static int impl_rt_scene_set_media(rt_ctx* c, const rt_medium* media, int n) {
+    if (!c) return RT_E_ARG;
+    if (!c->have_scene) return fail(c, RT_E_STATE, "rt_scene_set_media needs an uploaded scene");
+    if (c->ad.live) return fail(c, RT_E_STATE, "rt_scene_set_media during an adaptive session (rt_adaptive_end first)");
+    if (c->tp.live) return fail(c, RT_E_STATE, "rt_scene_set_media during a temporal session (rt_temporal_end first)");
+    if (!c->peers.empty()) return fail(c, RT_E_STATE, "media support one-device contexts only");
+    hipSetDevice(c->device);
+    if (!media || n == 0) {  // clear: no absorb stage again
+        HIPCHK(c, hipDeviceSynchronize());  // (passes on a caller's stream included)
+        free_media(c);
+        return RT_OK;
+    }
+    if (n != c->dsc.n_materials || (size_t)n != c->med.mat_type.size())
+        return fail(c, RT_E_ARG, "media: n_materials differs from the uploaded scene's");
+    bool any = false;
+    for (int m = 0; m < n; ++m) {
+        const rt_medium& x = media[m];
+        const std::string at = "media: material " + std::to_string(m) + ": ";
+        if (!(x.sigma >= 0.f && x.sigma < std::numeric_limits<float>::infinity()))
+            return fail(c, RT_E_ARG, at + "sigma must be finite and >= 0");
+        if (!(x.sigma > 0.f)) continue;
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(x.sigmoid[k]))
+                return fail(c, RT_E_ARG, at + "sigmoid[" + std::to_string(k) + "] must be finite when sigma > 0");
+        if (c->med.mat_emits[m]) return fail(c, RT_E_ARG, at + "sigma > 0 on an emissive material");
+        if (c->med.mat_type[m] != RT_MAT_DIELECTRIC && c->med.mat_type[m] != RT_MAT_ROUGH_DIELECTRIC)
+            return fail(c, RT_E_ARG, at + "sigma > 0 on a material whose type is neither RT_MAT_DIELECTRIC nor "
+                                          "RT_MAT_ROUGH_DIELECTRIC");
+        any = true;
+    }
+    std::vector<float4> h((size_t)n);
+    for (int m = 0; m < n; ++m) h[m] = make_float4(media[m].sigmoid[0], media[m].sigmoid[1], media[m].sigmoid[2], media[m].sigma);
+    HIPCHK(c, hipDeviceSynchronize());
+    DevBuf<float4> t;  // (a failure below leaves the media bound before in place)
+    HIPCHK(c, t.reserve((size_t)n));
+    HIPCHK(c, hipMemcpy(t.get(), h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
+    c->med.table = std::move(t);
+    c->med.bound.assign(media, media + n);
+    c->med.live = any;
+    return RT_OK;
+}
+
+static bool medium_items_ok(const rt_medium* m, int n, const float* lambda, const float* len, const float* out) {
+    return n >= 0 && (n == 0 || (m && lambda && len && out));
+}
+static int impl_rt_debug_medium_eval(rt_ctx* c, const rt_medium* m, int n, const float* lambda, const float* len, float* out) {
+    if (!c || !medium_items_ok(m, n, lambda, len, out)) return c ? fail(c, RT_E_ARG, "medium eval: invalid argument") : RT_E_ARG;
+    if (n == 0) return RT_OK;
+    hipSetDevice(c->device);
+    return ordered(c, c->stream, [&]() -> int {
+        DevBuf<float4> dm;
+        DevBuf<float> dl, dn, dout;
+        if (dm.reserve(n) || dl.reserve(8 * (size_t)n) || dn.reserve(n) || dout.reserve(8 * (size_t)n))
+            return fail(c, RT_E_OOM, "medium eval buffers");
+        std::vector<float4> hm(n);
+        for (int i = 0; i < n; ++i) hm[i] = make_float4(m[i].sigmoid[0], m[i].sigmoid[1], m[i].sigmoid[2], m[i].sigma);
+        if (hipMemcpy(dm.get(), hm.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dl.get(), lambda, 32 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dn.get(), len, 4 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+            launch_medium_eval(c->stream, n, dm.get(), dl.get(), dn.get(), dout.get()) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(out, dout.get(), 32 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, RT_E_HIP, std::string("medium eval: ") + hipGetErrorString(hipGetLastError()));
+        return RT_OK;
+    });
+}
+
+// launches of k_medium_absorb and the segments it attenuated in the context's last path pass (render_path zeroes both)
+static int impl_rt_debug_medium_stats(rt_ctx* c, int* launches, unsigned long long* segments) {
+    if (!c || !launches || !segments) return c ? fail(c, RT_E_ARG, "medium stats: NULL") : RT_E_ARG;
+    *launches = c->med.launches;
+    *segments = 0;
+    if (!c->med.counted || !c->med.ctr.get()) return RT_OK;
+    hipSetDevice(c->device);
+    HIPCHK(c, hipDeviceSynchronize());  // (passes on a caller's stream included)
+    std::vector<unsigned long long> raw(kMediumCtrWords);
+    HIPCHK(c, hipMemcpy(raw.data(), c->med.ctr.get(), kMediumCtrWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int u = 0; u < kCtrSubs; ++u) *segments += raw[ctr_word(0, u)];
+    return RT_OK;
+}
+
 // ---- metal: the level-2 kernels' device functions for a light's wi, on explicit inputs
 static int impl_rt_debug_conductor_eval(rt_ctx* c, int metal, float alpha, int n, const float* normal, const float* dir,
                                         const float* wi, const float* lambda, float* fcos, float* pdf, float* F) {
@@ -4682,6 +4818,16 @@ int rt_debug_roughglass_eval(rt_ctx* c, float alpha, float eta_r, int n, const f
     return entry(c, impl_rt_debug_roughglass_eval, alpha, eta_r, n, normal, dir, wi, fcos, pdf);
 }
 int rt_debug_roughglass_stats(rt_ctx* c, int64_t* launches) { return entry(c, impl_rt_debug_roughglass_stats, launches); }
+int rt_scene_set_media(rt_ctx* c, const rt_medium* media, int n_materials) {
+    return entry(c, impl_rt_scene_set_media, media, n_materials);
+}
+// (rt_medium_transmittance: rt_medium_host.cpp)
+int rt_debug_medium_eval(rt_ctx* c, const rt_medium* m, int n, const float* lambda, const float* len, float* out) {
+    return entry(c, impl_rt_debug_medium_eval, m, n, lambda, len, out);
+}
+int rt_debug_medium_stats(rt_ctx* c, int* launches, unsigned long long* segments) {
+    return entry(c, impl_rt_debug_medium_stats, launches, segments);
+}
 int rt_metal_nk(int metal, int n, const float* lambda, float* n_out, float* k_out) {
     return guarded([&] {
         if (metal < 0 || metal >= kMetals || n < 0 || (n && (!lambda || !n_out || !k_out))) return (int)RT_E_ARG;

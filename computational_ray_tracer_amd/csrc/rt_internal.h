@@ -787,6 +787,29 @@ struct EnvMissIO {
     DevLight env;
 };
 hipError_t launch_env_miss(hipStream_t st, int grid, const DevSpectra* sp, const EnvMissIO& io);
+// Absorbing media (rt_medium.hip).  The absorb stage of one depth >= 1 (k_medium_absorb): every queue
+// position whose hit lies on the back face of a material with sigma > 0 multiplies its slot's beta by the segment's
+// transmittance (rt_medium.h) over len = t |d|.  Runs between the depth's trace and its shade.  The scene's arrays
+// travel here, not in a DevScene, and the per-material table is a buffer of its own: no other kernel's arguments move.
+constexpr size_t kMediumCtrWords = (size_t)kCtrSubs * kCtrLine;  // one counter slot, spread (ctr_word(0, sub))
+struct MediumIO {
+    QueueView q;              // the traced queue (the shade's)
+    const float4* ray;        // its rays, interleaved pairs: ray k at ray[2k] (w = slot), ray[2k + 1]
+    const float4* hitB;       // at queue position: w = t
+    const int* hitPrim;
+    RecView rec;
+    int depth;
+    const float4* triWorld;   // DevScene's
+    const int* triMaterial;
+    const DevShape* shapes;
+    int n_tris;
+    const float4* media;      // per material: (c0, c1, c2, sigma)
+    int n_media;
+    unsigned long long* ctr;  // kMediumCtrWords: absorbed segments, one word per wave index mod kCtrSubs
+};
+hipError_t launch_medium_absorb(hipStream_t st, int grid, const MediumIO& io);
+// parity entry: item i of n, m[i] = (c0, c1, c2, sigma), lambda[8 i ..], len[i] -> out[8 i ..]
+hipError_t launch_medium_eval(hipStream_t st, int n, const float4* m, const float* lambda, const float* len, float* out);
 // parity entries: the kernels' own env_sample / env_eval (rt_device.h), one item per thread.
 // sample: u[2 i ..] -> wi[i] = (direction, pdf_omega), texel[i]; eval: dir[3 i ..] -> texel[i], pdf[i]
 // launches of k_path_shade_full (out[0..2]: TL 0, 1, 2) and k_path_nee (out[3..5]) since the process started (rt_kernels.hip)

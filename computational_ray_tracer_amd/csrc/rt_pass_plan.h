@@ -115,6 +115,7 @@ struct PassFacts {
     bool rough = false;        // a non-emissive RT_MAT_ROUGH material (it also makes the scene full)
     bool conductor = false;    // a non-emissive RT_MAT_CONDUCTOR material (it makes the scene full too)
     bool rough_dielectric = false;  // a non-emissive RT_MAT_ROUGH_DIELECTRIC material (§3m; it makes the scene full too)
+    bool media = false;        // some bound medium has sigma > 0 (rt_scene_set_media, §3n; its material is a glass: full)
     PassIntegrator integ = kIntegReference;
     int max_depth = 0;
     int n_work = 0, ib = 0, ie = 0;
@@ -188,6 +189,10 @@ struct DepthPlan {
     // the environment light's miss stage (k_env_miss): after this depth's shade, which zero-initialises L
     // of the misses at lean depth 0, and before the next depth reuses the queue's hit and ray buffers
     bool env_miss = false;
+    // the media's absorb stage (k_medium_absorb): between this depth's trace and its shade.  Never at depth
+    // 0 (a camera ray's first segment is not attenuated; lean depth 0 holds beta = 1 in registers) and never on an
+    // emitter-filtered depth, whose queue holds emitter hits only
+    bool absorb = false;
 };
 
 // The path pass: computed once per pass.
@@ -229,6 +234,7 @@ struct PathPlan {
     // a rough-glass material: RGH level 3 of the same kernels, whatever else the scene holds.  rgl implies
     // rgh; the NEE record is level 2's (cnd stays the scene's own conductor fact)
     bool rgl = false;
+    bool med = false;          // a medium with sigma > 0 is bound: depths >= 1 run the absorb stage
     // slot state layout (rt_internal.h RecView): records for multi-level scenes (sorted, scattered slots), SoA for
     // single-leaf ones (slots stay in queue order)
     bool records = false;
@@ -259,6 +265,7 @@ struct PathPlan {
         d.nee_fallback = nee_fallback;
         d.shadow = shadow;
         d.env_miss = env;
+        d.absorb = med && depth >= 1 && !d.efilter;
         return d;
     }
 };
@@ -284,6 +291,7 @@ inline PathPlan plan_path(const PassFacts& f, const Knobs& kn, const BatchPlan& 
     p.env = f.environment && b.path;
     p.cnd = f.conductor && b.path;
     p.rgl = f.rough_dielectric && b.path;
+    p.med = f.media && b.path;
     p.rgh = (f.rough && b.path) || p.cnd || p.rgl;
     p.ml = (f.mesh_light ? 1 : 0) | (p.env ? 2 : 0) | (p.rgh ? 4 : 0) | (p.cnd ? 8 : 0) | (p.rgl ? 16 : 0);
     p.records = multi;

@@ -310,6 +310,33 @@ class Renderer:
         self._chk("rt_debug_roughglass_stats", self.lib.rt_debug_roughglass_stats(self.h, n))
         return int(n[0]) + int(n[1])
 
+    # ---- absorbing media inside glass (rt_scene_set_media) ---------------------------------------
+    def set_media(self, media):
+        """Bind one scene.Medium (or None) per material of the uploaded scene; None or an empty list clears them.  Only
+        glass materials (RT_MAT_DIELECTRIC, RT_MAT_ROUGH_DIELECTRIC) take sigma > 0."""
+        if not media:
+            self._chk("rt_scene_set_media", self.lib.rt_scene_set_media(self.h, None, 0))
+            return
+        from . import scene
+        self._chk("rt_scene_set_media", self.lib.rt_scene_set_media(self.h, scene.media_array(list(media)), len(media)))
+
+    def medium_eval(self, media, lam, length):
+        """rt_debug_medium_eval: the device function the absorb stage calls, one item per thread: a scene.Medium (or n of
+        them), hero wavelengths lam (n, 8), segment lengths (n) -> transmittances (n, 8) float32."""
+        from . import scene
+        arr, n, lam, length = scene._medium_items(media, lam, length)
+        out = np.zeros((n, 8), np.float32)
+        F = C.POINTER(C.c_float)
+        self._chk("rt_debug_medium_eval", self.lib.rt_debug_medium_eval(
+            self.h, arr, n, lam.ctypes.data_as(F), length.ctypes.data_as(F), out.ctypes.data_as(F)))
+        return out
+
+    def medium_stats(self):
+        """rt_debug_medium_stats: (launches of the absorb stage, segments it attenuated) in the last path pass."""
+        n, s = C.c_int(0), C.c_ulonglong(0)
+        self._chk("rt_debug_medium_stats", self.lib.rt_debug_medium_stats(self.h, C.byref(n), C.byref(s)))
+        return int(n.value), int(s.value)
+
     def set_shard(self, tile_size, n_shards, shard_id):
         self._chk("rt_set_shard",self.lib.rt_set_shard(self.h, tile_size, n_shards, shard_id))
 

@@ -687,6 +687,59 @@ def roughglass_sample(alpha, eta_r, wo, disk, u):
     return wi, w, pdf, br
 
 
+@dataclass
+class Medium:
+    """An absorbing medium of a glass material (capi.rt_medium): sigma_a(lambda) = sigma S(lambda), S the
+    sigmoid of coefficients (c0, c1, c2), sigma >= 0 per render-space unit length.  Renderer.set_media takes one per
+    material (None: no medium)."""
+    sigmoid: tuple = (0.0, 0.0, 0.0)
+    sigma: float = 0.0
+
+
+def absorbing(rgb, sigma):
+    """The Medium whose absorption spectrum has the colour rgb (rt_rgb_to_sigmoid; the medium removes that colour, so
+    white light comes out in its complement) and strength sigma."""
+    co = (C.c_float * 3)()
+    src = (C.c_float * 3)(*[float(v) for v in rgb])
+    r = capi.load_library().rt_rgb_to_sigmoid(src, co)
+    if r != capi.RT_OK:
+        raise capi.RTError("rt_rgb_to_sigmoid", r, "rgb in [0, 1]")
+    return Medium((float(co[0]), float(co[1]), float(co[2])), float(sigma))
+
+
+def media_array(media):
+    """(capi.rt_medium * n) of a list of Medium (None entries: sigma = 0)."""
+    arr = (capi.rt_medium * len(media))()
+    for i, m in enumerate(media):
+        if m is not None:
+            arr[i].sigmoid[:] = [float(v) for v in m.sigmoid]
+            arr[i].sigma = float(m.sigma)
+    return arr
+
+
+def _medium_items(media, lam, length):
+    lam = np.ascontiguousarray(lam, np.float32)
+    length = np.ascontiguousarray(length, np.float32)
+    n = len(length)
+    assert lam.shape == (n, 8) and length.shape == (n,)
+    media = [media] * n if isinstance(media, Medium) else list(media)
+    assert len(media) == n
+    return media_array(media), n, lam, length
+
+
+def medium_transmittance(media, lam, length):
+    """rt_medium_transmittance (host only): a Medium (or n of them), hero wavelengths lam (n, 8) and segment lengths
+    length (n) -> the transmittances (n, 8) float32: x = (sigma S(lambda)) len, 0 when x >= 87, else (float)exp(-x)."""
+    arr, n, lam, length = _medium_items(media, lam, length)
+    out = np.zeros((n, 8), np.float32)
+    F = C.POINTER(C.c_float)
+    r = capi.load_library().rt_medium_transmittance(arr, n, lam.ctypes.data_as(F), length.ctypes.data_as(F),
+                                                    out.ctypes.data_as(F))
+    if r != capi.RT_OK:
+        raise capi.RTError("rt_medium_transmittance", r, "non-NULL pointers")
+    return out
+
+
 def _flat_mesh(faces_xyz):
     """(nt, 3, 3) float64 corner positions -> one-vertex-per-corner float32 mesh with flat normals."""
     p = np.asarray(faces_xyz, dtype=np.float64)

@@ -143,7 +143,8 @@ enum { RT_METAL_AG = 0, RT_METAL_AL = 1, RT_METAL_AU = 2, RT_METAL_CU = 3 };
  *   hemisphere is covered by NEE plus the sampled emitter or environment hit under the power heuristic with pdfF; the
  *   transmission hemisphere by the sampled direction alone.  No texture binds to it (RT_E_ARG); its albedo-table entry is
  *   (1, 1, 1); the feature, position and chain passes end a chain on it.  Limits: constant eta only, no absorption or
- *   tint, no NEE through the interface (delta lights reach the reflection lobe only, shadow rays stop at glass), single
+ *   tint of its own (a medium bound with rt_scene_set_media, DESIGN.md §3n, absorbs inside DIELECTRIC and
+ *   ROUGH_DIELECTRIC solids), no NEE through the interface (delta lights reach the reflection lobe only, shadow rays stop at glass), single
  *   scattering, no roughness textures.
  * emission_scale > 0 makes the surface a pure one-sided emitter with Le = scale · stdillum-D65. */
 typedef struct {
@@ -729,6 +730,41 @@ int rt_debug_roughglass_eval(rt_ctx* ctx, float alpha, float eta_r, int n, const
  * a pass rt_debug_rough_stats counts the same launches (level 3 is an RGH level), and rt_debug_conductor_stats counts
  * them only when the scene also holds a conductor. */
 int rt_debug_roughglass_stats(rt_ctx* ctx, int64_t* launches);
+
+/* ---- absorbing media inside glass (additive; build-defined: the reference has no media) ----------
+ * A medium belongs to a material of type RT_MAT_DIELECTRIC or RT_MAT_ROUGH_DIELECTRIC.  Its absorption coefficient is
+ * sigma_a(lambda) = sigma S(lambda), S the RGBSigmoidPolynomial of `sigmoid` as a material's R(lambda), sigma >= 0 per
+ * render-space unit length.
+ * The back-face rule: a path segment is attenuated when it ends on the back face of a non-emissive surface whose material
+ * carries a medium with sigma > 0 (the back face by the shade kernel's own test: the ray runs along the geometric
+ * normal of the triangle, or along the analytic shape's object-space normal).  Such a segment is taken to have run inside
+ * the medium over its whole length len = t sqrtf((dx dx + dy dy) + dz dz), t the hit distance along the ray's
+ * unnormalised direction d, and for each of the path's eight wavelengths
+ *   x = (sigma S(lambda)) len;   a = x >= 87 ? 0 : (float)exp(-(double)x);   beta = beta a
+ * (float32 in the order written; S with sigmoid_eval's two fmaf; terminated secondaries included).  The rule needs no
+ * per-path "current medium" and is exact for closed, non-nested solids with nothing embedded in them.  The attenuation is
+ * applied before the vertex is shaded, so the vertex's own light terms (a rough glass hit from inside runs NEE for its
+ * reflection lobe) carry it.
+ * Limits: the first segment of a camera ray is never attenuated (a camera inside a solid sees it unattenuated); a segment
+ * that ends on anything else inside the solid (an embedded emitter or diffuse object) is not attenuated; no scattering;
+ * shadow rays still stop at glass; RT_INTEGRATOR_REFERENCE, the feature, position, chain and albedo passes ignore media.
+ *
+ * rt_scene_set_media: one entry per material of the uploaded scene.  NULL or n_materials == 0 clears the media, and so
+ * does rt_scene_upload (as for textures).  With no medium bound, or every sigma == 0, no pass launches anything new and
+ * every film keeps its bits.  RT_E_STATE: no scene, an adaptive or temporal session is open, a multi-device context.
+ * RT_E_ARG: n_materials differs from the scene's; a sigma is NaN, infinite or negative; a coefficient is not finite
+ * while sigma > 0; sigma > 0 on a material whose type is not 2 or 5, or that is emissive; rt_last_error names the
+ * material index and the field.  After a refusal the media bound before stay bound.
+ * rt_medium_transmittance (host only, no context) and rt_debug_medium_eval (the device function the stage calls, one item
+ * per thread): item j of n uses medium m[j], lambda[8j .. 8j+7] and len[j] and writes the a above to out[8j .. 8j+7].
+ * RT_E_ARG: a negative count, a NULL pointer with a positive count.
+ * rt_debug_medium_stats: launches of the absorb stage and the segments it attenuated in the context's last path pass
+ * (0, 0 without a medium). */
+typedef struct { float sigmoid[3]; float sigma; } rt_medium;
+int rt_scene_set_media(rt_ctx* ctx, const rt_medium* media, int n_materials);
+int rt_medium_transmittance(const rt_medium* m, int n, const float* lambda, const float* len, float* out);
+int rt_debug_medium_eval(rt_ctx* ctx, const rt_medium* m, int n, const float* lambda, const float* len, float* out);
+int rt_debug_medium_stats(rt_ctx* ctx, int* launches, unsigned long long* segments);
 
 /* ---- metal (additive): RT_MAT_CONDUCTOR above ------------------------------------------
  * rt_metal_nk (host only, no context): the dense table's entry of metal (RT_METAL_*) at the dense spectra's index of

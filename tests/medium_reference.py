@@ -1,0 +1,366 @@
+"""Absorbing media inside glass: the float32 restatement of rt_medium.h's transmittance, its float64
+truth, and three closed-form films in float64 (M1 a tilted slab, M2 a sphere in a furnace, M3 a rough interface behind a
+window).  Imports radiometry_reference and roughglass_reference and changes neither.
+
+The restatement: S(lambda) is sigmoid_eval's operations, its two fmaf included (`fma32`: the exact product in float64,
+one TwoSum, round-to-odd, one rounding to float32 - numpy has no fmaf); x = (sigma S) len in float32; a = 0 from 87 up,
+else np.exp(-float64(x)) rounded to float32.  The library returns the float rounding of any double evaluation better than
+2^-46 (rt_medium.h), so the two agree bit for bit unless float64 exp(-x) lies within numpy's own error of a float32
+rounding midpoint; `near_midpoint64` finds such inputs from the float64 side alone.
+
+A film case is a function returning (cfg, media, mu, vmax, include [, extras]) in radiometry_reference's conventions.
+"""
+import math
+
+import numpy as np
+
+import radiometry_reference as ref
+import roughglass_reference as rgr
+from computational_ray_tracer_amd import capi, scene
+
+f32 = np.float32
+CUT = f32(87.0)
+
+# the largest relative error of the float32 restatement against float64, measured on the CPU over the items of
+# tests/test_medium_reference.py (items() below; zeros on both sides excluded); the test allows twice this
+MEASURED = 2.145e-4
+
+
+# ------------------------------------------------------------------------------------------- float32 restatement
+
+def fma32(a, b, c):
+    """fmaf(a, b, c) for float32 arrays: round_to_float32(a b + c) with ONE rounding.  a b is exact in float64 (48
+    bits); p + c is rounded to odd in float64 (53 >= 24 + 2 bits, so the final rounding to float32 is that of the exact
+    sum)."""
+    a, b, c = (np.asarray(v, f32).astype(np.float64) for v in (a, b, c))
+    a, b, c = np.broadcast_arrays(a, b, c)
+    p = a * b
+    s = p + c
+    with np.errstate(invalid="ignore"):
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)                      # TwoSum: p + c = s + e exactly (finite inputs)
+    s = np.ascontiguousarray(s)
+    bits = s.view(np.int64)
+    fix = np.isfinite(s) & np.isfinite(e) & (e != 0) & ((bits & 1) == 0)
+    toward = np.where(e > 0, np.inf, -np.inf)
+    s = np.where(fix, np.nextafter(s, toward), s)
+    return s.astype(f32)
+
+
+def sigmoid32(c, lam):
+    """sigmoid_eval (rt_device.h) / medium_sigmoid (rt_medium.h) in float32, bit for bit."""
+    c0, c1, c2 = (np.asarray(v, f32) for v in c)
+    lam = np.asarray(lam, f32)
+    x = fma32(lam, fma32(lam, c0, c1), c2)
+    with np.errstate(over="ignore", invalid="ignore"):
+        den = (f32(2) * np.sqrt((f32(1) + (x * x).astype(f32)).astype(f32))).astype(f32)
+        v = (f32(0.5) + (x / den).astype(f32)).astype(f32)
+    return np.where(np.isinf(x), np.where(x > 0, f32(1), f32(0)), v).astype(f32)
+
+
+def exponent32(c, sigma, lam, length):
+    """x = (sigma S(lambda)) len in float32: c (.., 3), sigma (..), lam (.., 8), length (..) -> (.., 8)."""
+    c = np.asarray(c, f32)
+    s = sigmoid32((c[..., 0, None], c[..., 1, None], c[..., 2, None]), lam)
+    sg = np.asarray(sigma, f32)[..., None]
+    ln = np.asarray(length, f32)[..., None]
+    return (((sg * s).astype(f32)) * ln).astype(f32)
+
+
+def transmittance32(c, sigma, lam, length):
+    """rt_medium_transmittance's bits: 0 from x = 87 up, else float32(np.exp(-float64(x)))."""
+    x = exponent32(c, sigma, lam, length)
+    with np.errstate(under="ignore"):
+        a = np.exp(-x.astype(np.float64)).astype(f32)
+    return np.where(x >= CUT, f32(0), a).astype(f32)
+
+
+def near_midpoint64(x, rel=2.0 ** -45):
+    """True where float64 exp(-x) lies within `rel` (relative) of a midpoint between two float32 values: the inputs on
+    which two accurate double evaluations may round differently.  x float32 below 87 (every result is a normal float)."""
+    r = np.exp(-np.asarray(x, f32).astype(np.float64))
+    lo = r.astype(f32)
+    other = np.where(lo.astype(np.float64) > r, np.nextafter(lo, f32(0)), np.nextafter(lo, f32(2)))
+    mid = 0.5 * (lo.astype(np.float64) + other.astype(np.float64))
+    return np.abs(r - mid) <= rel * r
+
+
+# ------------------------------------------------------------------------------------------- float64 truth
+
+def sigma_a(c, sigma, lam):
+    """sigma S(lambda), float64 at the continuous wavelength (coefficients and sigma rounded to float32 first)."""
+    return float(f32(sigma)) * ref.sigmoid(c, lam)
+
+
+def transmittance64(c, sigma, lam, length):
+    return np.exp(-sigma_a(c, sigma, lam) * np.asarray(length, np.float64))
+
+
+GREY = scene.grey_sigmoid(0.5)       # S = 0.5 exactly at every wavelength: sigma_a = sigma / 2
+SIGMOIDS = (("grey", GREY), ("red", ref.S_RED), ("green", ref.S_GREEN))
+SEED = 20260117
+
+
+def items(n, seed=SEED):
+    """n seeded items per sigmoid for the bit-equality tests: lambda uniform over 360-830, sigma len log-uniform over
+    1e-6 .. 100 (x = sigma S len lies on both sides of 87 where S_RED and S_GREEN come near 1; the grey S is 1/2), the
+    first items with len = 0 and with sigma = 0.  Returns a list of (name, c (n, 3), sigma (n), lam (n, 8), length (n))."""
+    out = []
+    for k, (name, c) in enumerate(SIGMOIDS):
+        rng = np.random.default_rng(seed + k)
+        lam = rng.uniform(360.0, 830.0, (n, 8)).astype(f32)
+        prod = np.exp(rng.uniform(math.log(1e-6), math.log(100.0), n))
+        length = np.exp(rng.uniform(math.log(1e-3), math.log(1e3), n))
+        sigma = (prod / length).astype(f32)
+        length = length.astype(f32)
+        length[0:4] = 0.0
+        sigma[4:8] = 0.0
+        lam[8] = np.linspace(360.0, 830.0, 8, dtype=f32)
+        out.append((name, np.broadcast_to(np.asarray(c, f32), (n, 3)).copy(), sigma, lam, length))
+    return out
+
+
+def media_of(c, sigma):
+    return [scene.Medium(tuple(float(v) for v in ci), float(si)) for ci, si in zip(c, sigma)]
+
+
+# ------------------------------------------------------------------------------------------- M1: the tilted slab
+
+M1_TILT = 30.0
+M1_Y0, M1_D = 100.0, 200.0           # the slab's bottom face and its thickness
+M1_SIGMA = 1.0 / M1_D                # sigma d = 1
+M1_SENSOR_HALF = 200.0
+
+
+def _quad_tris(y, n, up, half=ref.FLOOR_HALF):
+    """The square |x|, |z| <= half at height y as n x n x 2 triangles, geometric normal +y (up) or -y."""
+    t = ref._floor_tris(n).copy()
+    t[:, :, 1] = y
+    assert half == ref.FLOOR_HALF
+    return t if up else t[:, [0, 2, 1]]
+
+
+def m1_camera():
+    th = math.radians(M1_TILT)
+    look = np.array([math.sin(th), -math.cos(th), 0.0])
+    pos = np.array([0.0, M1_Y0 + M1_D / 2, 0.0]) - 1000.0 * look
+    return scene.OrthographicCamera(near=1e-2, far=5000.0, sensor=(2 * M1_SENSOR_HALF, 2 * M1_SENSOR_HALF),
+                                    position=tuple(pos), look=tuple(look), worldup=(0.0, 0.0, 1.0), res=ref.RES)
+
+
+def m1_slab(tessellated=False, sensor="xyz", illum=capi.RT_ILLUM_D65, spp=256, c=ref.S_GREEN, sigma=M1_SIGMA,
+            max_depth=3, res=ref.RES):
+    """M1: an emissive floor Le = k D65 facing up; above it a slab of smooth glass with eta = 1 (no reflection, no
+    deflection: asserted in tests/test_medium_reference.py) between y = M1_Y0 (normal down) and M1_Y0 + M1_D (normal up),
+    its medium sigma S; an orthographic camera tilted M1_TILT degrees, PATH, max_depth 3.  Every sample enters through the
+    top face (front, depth 0), ends its second segment on the back face of the bottom (attenuated over d / cos theta) and
+    meets the emitter: every pixel expects k response(bars, imaging_ratio, exp(-sigma_a(lambda) d / cos theta)).  The
+    inside segment starts 1e-4 (1 + max|p|) below the top face (the shade's ray offset: |p| <= 1100 here, so at most
+    0.11 of 231 length units, 5e-4 of x, inside the float allowance).  Returns (cfg, media, mu, vmax, include, extras)
+    with extras = dict(cos, k, bars, film, wrong_no_cos, wrong_mean_sigma)."""
+    film = ref._film(sensor, illum)
+    if tuple(res) != tuple(ref.RES):
+        film.res = tuple(res)
+    bars = ref.sensor_bars(film.sensor)
+    m8, _ = ref.sample_maxima(film.imaging_ratio, bars=bars)
+    k = float(f32(0.9 / m8.max()))
+    n = 48 if tessellated else 1
+    tris = np.concatenate([ref._floor_tris(1), _quad_tris(M1_Y0, n, False), _quad_tris(M1_Y0 + M1_D, n, True)])
+    mats = [0] * 2 + [1] * (4 * n * n)
+    glass = ((0.0, 0.0, 0.0), 0.0, capi.RT_MAT_DIELECTRIC, 1.0)
+    model = ref._model(tris, mats, [((0.0, 0.0, 0.0), k), glass])
+    cam = m1_camera()
+    cam.res = tuple(res)
+    cfg = ref._config("m1_slab" + ("_tess" if tessellated else ""), model, cam, spp, capi.RT_INTEGRATOR_PATH, max_depth,
+                      res=tuple(res), film=film)
+    cos_t = math.cos(math.radians(M1_TILT))
+    path = M1_D / cos_t
+    mu1 = k * ref.response(bars, film.imaging_ratio, lambda lam: transmittance64(c, sigma, lam, path))
+    npx = res[0] * res[1]
+    mu = np.broadcast_to(mu1, (npx, 3)).copy()
+    vmax = k * m8 * (1 + 1e-5)
+    # what the film must not show: the forgotten 1 / cos theta, and absorption as a colour (one Y-weighted mean sigma_a)
+    no_cos = k * ref.response(bars, film.imaging_ratio, lambda lam: transmittance64(c, sigma, lam, M1_D))
+    wy = ref.BARS[1] * ref.D65
+    mean_sa = float(np.sum(wy * sigma_a(c, sigma, ref.LAMBDA)) / np.sum(wy))
+    one = lambda lam: np.ones_like(np.asarray(lam, np.float64))
+    mean_sigma = k * math.exp(-mean_sa * path) * ref.response(bars, film.imaging_ratio, one)
+    media = [None, scene.Medium(tuple(float(f32(v)) for v in c), float(f32(sigma)))]
+    extras = dict(cos=cos_t, k=k, bars=bars, film=film, path=path,
+                  wrong_no_cos=np.broadcast_to(no_cos, (npx, 3)).copy(),
+                  wrong_mean_sigma=np.broadcast_to(mean_sigma, (npx, 3)).copy())
+    if tuple(res) == tuple(ref.RES):
+        cfg, mu, vmax, include = ref._finish(cfg.name, cfg, mu, vmax, np.ones(npx, bool), spp)
+    else:
+        include = np.ones(npx, bool)
+    return cfg, media, mu, vmax, include, extras
+
+
+# ------------------------------------------------------------------------------------------- M2: chords behind refraction
+
+M2_ETA = 1.5
+M2_SIGMA_GREY = 2.0 / (2 * ref.FURNACE_R)     # S = 1/2: sigma_a 2 r = 1
+M2_SIGMA_RED = 1.0 / (2 * ref.FURNACE_R)      # S_RED rises to 1: sigma_a 2 r up to 1
+M2_NODES = 24
+
+
+def m2_series(F, a):
+    """What a ray entering a sphere of entry reflectance F and chord transmittance a carries out, the surface reflection
+    included: F + (1 - F)^2 a / (1 - F a) (every chord and every F of a sphere are the same)."""
+    return F + (1 - F) ** 2 * a / (1 - F * a)
+
+
+def m2_expression(cos_i, c, sigma, lam):
+    """The series at entry cosine cos_i (..) and wavelengths lam (k): (.., k)."""
+    cos_i = np.asarray(cos_i, np.float64)[..., None]
+    F = ref.fr_dielectric(cos_i, M2_ETA)
+    cos_t = np.sqrt(np.maximum(0.0, 1 - (1 - cos_i * cos_i) / (M2_ETA * M2_ETA)))
+    a = np.exp(-sigma_a(c, sigma, np.asarray(lam, np.float64)) * (2 * ref.FURNACE_R) * cos_t)
+    return m2_series(F, a)
+
+
+def m2_response_table(bars, imaging_ratio, c, sigma, lo, nodes=M2_NODES):
+    """cos_i -> response(bars, imaging_ratio, the series at cos_i) on [lo, 1] as a Chebyshev interpolant per channel
+    through `nodes` + 1 quadratures (the series is smooth in cos_i; tests compare it with a doubled table)."""
+    t = 0.5 * (lo + 1.0) + 0.5 * (1.0 - lo) * np.polynomial.chebyshev.chebpts1(nodes + 1)
+    y = np.array([ref.response(bars, imaging_ratio, lambda lam, x=x: m2_expression(x, c, sigma, lam.reshape(-1))
+                               .reshape(lam.shape)) for x in t])
+    ch = [np.polynomial.chebyshev.Chebyshev.fit(t, y[:, i], nodes, domain=[lo, 1.0]) for i in range(3)]
+    return lambda x: np.stack([p(x) for p in ch], -1)
+
+
+def m2_sphere(coloured=False, spp=256, s=ref.S, table_nodes=M2_NODES):
+    """M2: K6's furnace with the glass Sphere (eta 1.5) and a medium in it: grey with sigma_a 2 r = 1, or S_RED.  A pixel
+    ray at incidence theta_i sees L0 response(F + (1 - F)^2 a / (1 - F a)), a = exp(-sigma_a 2 r cos theta_t), averaged
+    over the pixel's s x s sub-samples; pixels off the sphere see L0 W.  K6's exclusions (mixed pixels, a cut-off tail
+    above LOST_MAX) are kept as they are; the series is at most 1, so K6's bound holds.  Returns (cfg, media, mu, vmax,
+    include, on)."""
+    cfg, mu0, vmax, include = ref.k6_furnace("glass", spp=spp)
+    c = ref.S_RED if coloured else GREY
+    sigma = M2_SIGMA_RED if coloured else M2_SIGMA_GREY
+    film = cfg.film
+    bars = ref.sensor_bars(film.sensor)
+    l0 = float(cfg.model.materials[0][1])
+    w = ref.sensor_white(film.imaging_ratio)
+    o, d = ref.camera_rays(cfg, ref._midpoints(s))
+    bq = d @ o
+    disc = bq * bq - (o @ o - ref.FURNACE_R ** 2)
+    hit = disc > 0
+    on = np.all(hit, axis=1)
+    t = -bq - np.sqrt(np.maximum(disc, 0.0))
+    x = o + t[..., None] * d
+    cos_i = np.where(hit, -np.sum(x * d, axis=-1) / ref.FURNACE_R, 1.0)
+    if coloured:
+        lo = max(0.0, float(cos_i[on & include].min()) - 1e-3) if np.any(on & include) else 0.0
+        tab = m2_response_table(bars, film.imaging_ratio, c, sigma, lo, table_nodes)
+        val = tab(np.clip(cos_i, lo, 1.0))                                        # (npx, s s, 3)
+    else:
+        val = m2_expression(cos_i, c, sigma, np.array([550.0]))[..., 0, None] * w[None, None, :]
+    mu = l0 * np.where(hit[..., None], val, w[None, None, :]).mean(axis=1)
+    cfg.name = "m2_sphere_" + ("red" if coloured else "grey")
+    cfg, mu, vmax, include = ref._finish(cfg.name, cfg, mu, vmax, include, spp)
+    media = [None, scene.Medium(tuple(float(f32(v)) for v in c), float(f32(sigma)))]
+    return cfg, media, mu, vmax, include, on
+
+
+# ------------------------------------------------------------------------------------------- M3: rough glass behind a window
+
+M3_T = 500.0                # window to floor
+M3_SIGMA = 2 * 0.7 / M3_T   # grey, S = 1/2: sigma_a t = 0.7
+M3_VIEW = 4.0               # the orthographic camera's sensor edge
+M3_WINDOW = 3.0             # the window's half edge
+M3_ALPHA = rgr.D3_ALPHA
+
+
+def m3_window_share():
+    """An upper bound of the share of the floor's reflected light that the window could take away: the window's solid
+    angle from a floor point times the largest fcosF per steradian (D_max / (4 mu_o), G2, F <= 1), over the smallest
+    total the case can have."""
+    omega = (2 * M3_WINDOW + M3_VIEW) ** 2 / M3_T ** 2
+    return omega / (math.pi * M3_ALPHA ** 2 * 4)
+
+
+def m3_rough(mis, max_depth, spp=256, target=0.9, sigma=M3_SIGMA):
+    """M3: §3m's D3b - a rough-glass floor (eta 1.5, alpha 0.5) under a constant map c D65, seen from below - with an
+    orthographic camera looking straight up (mu_o = 1 in every pixel) and a small horizontal eta = 1 window without a
+    medium at y = -M3_T, so the floor's back face is hit at depth 1 and that segment, of length t, is attenuated by the
+    grey medium on the floor's material before the vertex is shaded: mu = exp(-sigma_a t) c response(1) (E_R' + E_T' eta^2)
+    at mu_o = 1, er = 1 / eta.  The window is 6 units wide 500 below the floor: it hides at most `m3_window_share()` of
+    the reflected light from the floor's NEE and bounce (asserted below 1e-4 of the total).  Returns (cfg, media, env,
+    mu, vmax, include, extras) with extras = dict(a, c, E_R, E_T, w)."""
+    import envlight_reference as env
+    film = ref._film()
+    m8, _ = ref.sample_maxima(film.imaging_ratio)
+    w = ref.sensor_white(film.imaging_ratio)
+    er = 1 / rgr.ETA
+    alpha = M3_ALPHA
+    probe = env.constant_map(1, 1, (1.0, 1.0, 1.0))
+    t_max = max(1.0, 1 / (er * er))
+    per_c = 0.5 + t_max if mis else 1 / (math.pi * alpha * alpha * 4 * 1.0) / env.pdf_min(probe) + 1 / (er * er)
+    per_c *= 1 + 1e-5
+    c = float(f32(target / (per_c * m8.max())))
+    h = M3_WINDOW
+    win = np.array([[(-h, -M3_T, -h), (h, -M3_T, h), (h, -M3_T, -h)], [(-h, -M3_T, -h), (-h, -M3_T, h), (h, -M3_T, h)]])
+    window = ((0.0, 0.0, 0.0), 0.0, capi.RT_MAT_DIELECTRIC, 1.0)
+    model = rgr._glass_floor(False, alpha, extra_tris=win, extra_mats=[1, 1], materials=[window])
+    cam = scene.OrthographicCamera(near=1e-2, far=5000.0, sensor=(M3_VIEW, M3_VIEW), position=(0.0, -ref.EYE_HEIGHT, 0.0),
+                                   look=(0.0, 1.0, 0.0), worldup=(0.0, 0.0, 1.0), res=ref.RES)
+    kind = capi.RT_INTEGRATOR_PATH_MIS if mis else capi.RT_INTEGRATOR_PATH
+    cfg = ref._config("m3_rough_" + ("mis" if mis else "path"), model, cam, spp, kind, max_depth, film=film)
+    e_r, e_t = rgr.E_R(alpha, 1.0, er, 1e-7), rgr.E_T(alpha, 1.0, er, 1e-7)
+    total = e_r + e_t / (er * er)
+    assert m3_window_share() <= 1e-4 * total
+    a = math.exp(-float(f32(sigma)) * 0.5 * M3_T)
+    npx = ref.RES[0] * ref.RES[1]
+    mu = np.broadcast_to(a * c * total * w, (npx, 3)).copy()
+    # (every contribution of a sample passes the attenuated segment: D3b's bound of one sample, times a)
+    cfg, mu, vmax, include = ref._finish(cfg.name, cfg, mu, a * c * per_c * m8, np.ones(npx, bool), spp)
+    media = [scene.Medium(GREY, float(f32(sigma))), None]
+    return cfg, media, scene.Environment(env.constant_map(1, 1, (c, c, c))), mu, vmax, include, \
+        dict(a=a, c=c, E_R=e_r, E_T=e_t, w=w, er=er, alpha=alpha)
+
+
+def m3_after_shade(extras, nee):
+    """What M3's PATH_MIS film would show with the stage run after the shade: the vertex's own NEE term (`nee`, its share
+    of E_R' from m3_nee_share) unattenuated, everything the bounce brings attenuated:
+    c response(1) (E_R'_nee + a (E_R' - E_R'_nee + E_T' eta^2))."""
+    er = extras["er"]
+    rest = extras["E_R"] - nee + extras["E_T"] / (er * er)
+    return extras["c"] * (nee + extras["a"] * rest) * extras["w"]
+
+
+def m3_nee_share(alpha, er, n=32):
+    """PATH_MIS at the M3 vertex (wo = the normal of the shading side): the part of E_R' that NEE delivers, the integral
+    over the reflection hemisphere of fcosF p_l^2 / (p_l^2 + p_b^2) with p_l the constant map's pdf (envlight_reference's
+    restatement on a 1 x 1 table) and p_b = pdfF.  Composite tensor Gauss-Legendre in (cos theta, phi), n points per panel; returns (share at n, share
+    at 2 n)."""
+    import envlight_reference as env
+    _, wgt = env.bake_weights(env.constant_map(1, 1, (1.0, 1.0, 1.0)))
+    cond, marg, _ = env.table(wgt)
+    M = env.colmajor(np.eye(3))
+
+    # panels: the integrand has kinks where wo.h crosses the critical cosine (cos theta_i = 1 - 2 er^2 for wo on the normal)
+    # and, through p_l, on the octahedral map's fold planes (phi a multiple of pi / 2)
+    kink = 1 - 2 * er * er
+    cpan = [(0.0, 1.0)] if not 0 < kink < 1 else [(0.0, kink), (kink, 1.0)]
+    ppan = [(k * math.pi / 2, (k + 1) * math.pi / 2) for k in range(4)]
+
+    def rule(m):
+        g, wt = np.polynomial.legendre.leggauss(m)
+        ct = np.concatenate([lo + 0.5 * (hi - lo) * (g + 1) for lo, hi in cpan])
+        wc = np.concatenate([0.5 * (hi - lo) * wt for lo, hi in cpan])
+        ph = np.concatenate([lo + 0.5 * (hi - lo) * (g + 1) for lo, hi in ppan])
+        wp = np.concatenate([0.5 * (hi - lo) * wt for lo, hi in ppan])
+        CT, PH = np.meshgrid(ct, ph, indexing="ij")
+        st = np.sqrt(1 - CT * CT)
+        wi = np.stack([st * np.cos(PH), st * np.sin(PH), CT], -1).reshape(-1, 3)      # local: z = the shading normal
+        wo = np.broadcast_to(np.array([0.0, 0.0, 1.0]), wi.shape)
+        fc = rgr.fr_cos64(alpha, er, wo, wi)
+        pb = rgr.pdfF64(alpha, er, wo, wi)
+        # the shading side is below the floor: local z = world -y (the map is constant: the frame's azimuth is free)
+        world = np.stack([wi[:, 0], -wi[:, 2], wi[:, 1]], -1)
+        pl = env.evaluate(cond, marg, M, world.astype(f32))["pdf"].astype(np.float64)
+        wn = pl * pl / (pl * pl + pb * pb)
+        ww = (wc[:, None] * wp[None, :]).reshape(-1)
+        return float(np.sum(fc * wn * ww)), float(np.sum(fc * ww))
+    return rule(n), rule(2 * n)
