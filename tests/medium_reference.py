@@ -164,7 +164,7 @@ def m1_slab(tessellated=False, sensor="xyz", illum=capi.RT_ILLUM_D65, spp=256, c
     bars = ref.sensor_bars(film.sensor)
     m8, _ = ref.sample_maxima(film.imaging_ratio, bars=bars)
     k = float(f32(0.9 / m8.max()))
-    n = 48 if tessellated else 1
+    n = ref.floor_cells(tessellated)
     tris = np.concatenate([ref._floor_tris(1), _quad_tris(M1_Y0, n, False), _quad_tris(M1_Y0 + M1_D, n, True)])
     mats = [0] * 2 + [1] * (4 * n * n)
     glass = ((0.0, 0.0, 0.0), 0.0, capi.RT_MAT_DIELECTRIC, 1.0)

@@ -312,14 +312,20 @@ def _model(tris, tri_material, materials, lights=(), shapes=()):
     return m
 
 
-def _floor_tris(n):
-    """The floor y = 0, |x|, |z| <= FLOOR_HALF, as n x n x 2 triangles."""
+def _floor_tris(n, x_lines=()):
+    """The floor y = 0, |x|, |z| <= FLOOR_HALF, as n x n x 2 triangles.  `x_lines`: further grid lines x = const that
+    are no line of the n x n grid (a seam between two materials that a coarse grid would not hold); each adds a column."""
     g = np.linspace(-FLOOR_HALF, FLOOR_HALF, n + 1)
+    gx = g
+    for x in x_lines:
+        if not np.any(np.abs(gx - x) <= 1e-9 * FLOOR_HALF):
+            assert -FLOOR_HALF < x < FLOOR_HALF
+            gx = np.sort(np.append(gx, x))
     t = []
-    for i in range(n):
+    for i in range(len(gx) - 1):
         for j in range(n):
-            a, b = (g[i], 0.0, g[j]), (g[i + 1], 0.0, g[j])
-            c, d = (g[i + 1], 0.0, g[j + 1]), (g[i], 0.0, g[j + 1])
+            a, b = (gx[i], 0.0, g[j]), (gx[i + 1], 0.0, g[j])
+            c, d = (gx[i + 1], 0.0, g[j + 1]), (gx[i], 0.0, g[j + 1])
             t += [(a, c, b), (a, d, c)]
     return np.array(t)
 
@@ -401,8 +407,21 @@ def _outside_frustum(cfg, pts):
                 np.all(s[:, 1] < lo[1]) or np.all(s[:, 1] > hi[1]))
 
 
-def _floor_model(tessellated, extra_tris=(), extra_mats=(), materials=(), lights=(), shapes=(), albedo=None):
-    tris = _floor_tris(48 if tessellated else 1)
+TESSELLATED_N = 48         # the floor of the "tessellated" cases: a BFS queue bound above 16, the LDS + HBM FIFO (QCAP 0)
+
+
+def floor_cells(tessellated):
+    """The floor's cells per side: False -> 1 (a single leaf), True -> TESSELLATED_N, an int -> itself (a coarser
+    tessellation keeps every closed form, which is of the plane, and selects another traversal instantiation)."""
+    if isinstance(tessellated, (bool, np.bool_)):
+        return TESSELLATED_N if tessellated else 1
+    n = int(tessellated)
+    assert n == tessellated and n >= 1, tessellated
+    return n
+
+
+def _floor_model(tessellated, extra_tris=(), extra_mats=(), materials=(), lights=(), shapes=(), albedo=None, x_lines=()):
+    tris = _floor_tris(floor_cells(tessellated), x_lines)
     mats = [0] * len(tris)
     if len(extra_tris):
         tris = np.concatenate([tris, np.asarray(extra_tris, np.float64)])

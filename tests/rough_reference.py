@@ -561,7 +561,7 @@ def g3m_box(max_depth=1, spp=256, target=0.9):
 G4_X, G4_H, G4_R = -150.0, 400.0, 0.9
 
 
-def g4_mirror(alpha=0.5, spp=256, target=0.5):
+def g4_mirror(alpha=0.5, spp=256, target=0.5, tessellated=True):
     """G4: G1 (tessellated floor: a multi-level octree, so both material bins run) with a vertical MIRROR wall (R = 0.9)
     in the plane x = G4_X, facing +x, |z| <= 200, 0 <= y <= G4_H, PATH depth 2.  A camera ray bound for a floor point with
     x < G4_X meets the wall first (at a height below 250) and is reflected, d' = (-d.x, d.y, d.z), onto the floor at
@@ -578,7 +578,7 @@ def g4_mirror(alpha=0.5, spp=256, target=0.5):
     mirror = (scene.grey_sigmoid(G4_R), 0.0, capi.RT_MAT_MIRROR, 0.0)
 
     def model(e):
-        m = ref._floor_model(True, wall, [1, 1], [mirror], [dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)])
+        m = ref._floor_model(tessellated, wall, [1, 1], [mirror], [dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)])
         m.materials[0] = scene.rough(scene.grey_sigmoid(ref.RHO), alpha)
         return m
 

@@ -662,7 +662,7 @@ def _floor_terms(cfg, a, wi_world, offsets, mirror_x=None):
     return rr.D64(h[..., 1], a) * rr.G2_64(muo, mui, a) / (4 * muo), np.clip(np.sum(wo * h, -1), 0, 1), xf[..., 0]
 
 
-def d5_three_materials(alpha=0.5, spp=256, target=0.5):
+def d5_three_materials(alpha=0.5, spp=256, target=0.5, tessellated=True):
     """D5: D1 (tessellated) with gold on the half x < 0, rough glass on 0 < x < D5_EDGE and a rough grey strip beyond it,
     all at `alpha`, PATH depth 1: level 3 runs the three rough materials in one pass.  Per floor point L = E fcos times
     D65 F_Au(lambda, wo.h) (gold), D65 F(wo.h, eta) (glass), D65 R (grey).  Pixels whose lattice straddles a seam are
@@ -675,10 +675,14 @@ def d5_three_materials(alpha=0.5, spp=256, target=0.5):
     grey = scene.rough(scene.grey_sigmoid(ref.RHO), alpha)
 
     def model(e):
-        m = ref._floor_model(True, materials=[scene.metal("Au", alpha), grey],
-                             lights=[dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)])
+        # (a coarser floor than 48 x 48 has no cell edge at D5_EDGE: it gets that line as a column of its own)
+        m = ref._floor_model(tessellated, materials=[scene.metal("Au", alpha), grey],
+                             lights=[dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)], x_lines=(D5_EDGE,))
         m.materials[0] = scene.rough_glass(ETA, alpha)
-        x = np.asarray(m.positions, np.float64).reshape(-1, 3, 3)[:, :, 0].mean(axis=1)      # (object space: x is world x)
+        xs = np.asarray(m.positions, np.float64).reshape(-1, 3, 3)[:, :, 0]                   # (object space: x is world x)
+        for seam in (0.0, D5_EDGE):
+            assert not np.any((xs.min(axis=1) < seam - 1e-3) & (xs.max(axis=1) > seam + 1e-3)), "a triangle across a seam"
+        x = xs.mean(axis=1)
         m.tri_material = np.where(x < 0, 1, np.where(x < D5_EDGE, 0, 2)).astype(np.int32)
         return m
     probe = ref._config("d5", model(1.0), ref._down_camera(), spp, capi.RT_INTEGRATOR_PATH, 1, film=film)
@@ -707,7 +711,7 @@ def d5_three_materials(alpha=0.5, spp=256, target=0.5):
     return rr.finish("d5_three_materials", cfg, mu, e * fc_max * m8, include, spp) + (parts,)
 
 
-def d6_mirror_wall(alpha=0.5, spp=256, target=0.5):
+def d6_mirror_wall(alpha=0.5, spp=256, target=0.5, tessellated=True):
     """D6 as built: D1 (tessellated, so both material bins run) with G4's vertical MIRROR wall (R = 0.9) in the plane
     x = G4_X, PATH depth 2, under D1's distant light rather than D3's map (under a map the wall hides part of the sky from
     every floor point next to it, and the mirror image shows only such points: that expectation is an integral over the
@@ -724,7 +728,7 @@ def d6_mirror_wall(alpha=0.5, spp=256, target=0.5):
     mirror = (scene.grey_sigmoid(R), 0.0, capi.RT_MAT_MIRROR, 0.0)
 
     def model(e):
-        m = ref._floor_model(True, wall, [1, 1], [mirror], [dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)])
+        m = ref._floor_model(tessellated, wall, [1, 1], [mirror], [dict(type=capi.RT_LIGHT_DISTANT, dir=tuple(d), scale=e)])
         m.materials[0] = scene.rough_glass(ETA, alpha)
         return m
     probe = ref._config("d6", model(1.0), ref._down_camera(), spp, capi.RT_INTEGRATOR_PATH, 2, film=film)
@@ -779,7 +783,10 @@ def wall_fcosF_integral(a, er, x, wo, X, H, zlo, zhi, tol=2e-6, s_min=0.5, order
     raise AssertionError("wall integral did not converge")
 
 
-def d6_map_mirror(mis=True, alpha=D3_ALPHA, spp=256, target=0.9):
+_WALL_INTEGRALS = {}
+
+
+def d6_map_mirror(mis=True, alpha=D3_ALPHA, spp=256, target=0.9, tessellated=True):
     """D6: D3 (tessellated floor: both material bins run) with G4's vertical MIRROR wall (R = 0.9) in the plane x = G4_X,
     depth 2.  With W(x, wo) the integral of fcosF over the directions from a floor point to the wall:
     - a pixel that sees the floor directly: the wall hides those directions from NEE and from the bounce's own miss, and a
@@ -795,7 +802,7 @@ def d6_map_mirror(mis=True, alpha=D3_ALPHA, spp=256, target=0.9):
     w = ref.sensor_white(film.imaging_ratio)
     X, H, R = rr.G4_X, rr.G4_H, rr.G4_R
     wall = np.array([[(X, 0.0, -200.0), (X, 0.0, 200.0), (X, H, 200.0)], [(X, 0.0, -200.0), (X, H, 200.0), (X, H, -200.0)]])
-    model = ref._floor_model(True, wall, [1, 1], [(scene.grey_sigmoid(R), 0.0, capi.RT_MAT_MIRROR, 0.0)])
+    model = ref._floor_model(tessellated, wall, [1, 1], [(scene.grey_sigmoid(R), 0.0, capi.RT_MAT_MIRROR, 0.0)])
     model.materials[0] = scene.rough_glass(ETA, alpha)
     kind = capi.RT_INTEGRATOR_PATH_MIS if mis else capi.RT_INTEGRATOR_PATH
     cfg = ref._config("d6_map_mirror", model, ref._down_camera(), spp, kind, 2, film=film)
@@ -820,7 +827,10 @@ def d6_map_mirror(mis=True, alpha=D3_ALPHA, spp=256, target=0.9):
     # (pixels on the seam are not compared: their points are moved off the wall so that the integral is defined)
     xq = xp.reshape(-1, 3).copy()
     xq[:, 0] = np.maximum(xq[:, 0], X + 0.25)
-    W = wall_fcosF_integral(alpha, ETA, xq, wo.reshape(-1, 3), X, H, -200.0, 200.0).reshape(npx, ns)
+    key = (alpha, xq.tobytes(), wo.tobytes())      # (the integral is of the plane: one per camera, whatever the floor's triangles)
+    if key not in _WALL_INTEGRALS:
+        _WALL_INTEGRALS[key] = wall_fcosF_integral(alpha, ETA, xq, wo.reshape(-1, 3), X, H, -200.0, 200.0).reshape(npx, ns)
+    W = _WALL_INTEGRALS[key]
     rs = float(ref.sigmoid(scene.grey_sigmoid(R), np.array([550.0]))[0])
     tr, tt = albedo_tables(alpha, ETA, math.floor(mu_min * 50) / 50)
     muo = wo[..., 1]

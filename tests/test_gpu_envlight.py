@@ -107,7 +107,8 @@ def _film(cfg, env, spp):
     g = Renderer(cfg)
     try:
         g.set_environment(env)
-        depth = g.octree()["depth"]
+        oc = g.octree()
+        depth = oc["depth"], oc["max_queue_groups"]
         g.reset_stats()
         film = g.render_pass(0, spp)
         return film, g.stats(), depth, g.env_miss_ms()
@@ -119,7 +120,8 @@ def _closed_form(name, case, spp=256, multi_level=None):
     cfg, env, mu, vmax, include = case
     film, st, depth, ms_miss = _film(cfg, env, spp)
     if multi_level is not None:
-        assert depth > 0 if multi_level else depth == 0
+        assert depth[0] > 0 if multi_level else depth[0] == 0
+        assert (depth[1] > 16) == multi_level, depth   # (QCAP 0 with coop_ok: DESIGN §2)
     assert st["coop_overflows"] == 0 and ms_miss > 0, "the miss stage ran"
     rows = ref.compare(film, mu, vmax, include, spp)
     print(f"{name}: max |got - mu| / tol = {ref.deviation(rows):.3f}\n{ref.report(rows)}")

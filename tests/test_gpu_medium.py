@@ -229,7 +229,8 @@ def _render(cfg, media, env=None, spans=((0, SPP),)):
         if env is not None:
             g.set_environment(env)
         g.set_media(media)
-        depth = g.octree()["depth"]
+        oc = g.octree()
+        depth = oc["depth"], oc["max_queue_groups"]
         film, stats = None, []
         for a, b in spans:
             film = g.render_pass(a, b, film)
@@ -266,7 +267,8 @@ def test_m1_tilted_slab(tess, sensor, m1_tess_film):
         case = mr.m1_slab(tess, sensor, capi.RT_ILLUM_D65 if sensor == "xyz" else capi.RT_ILLUM_A)
         film, depth, stats = _render(case[0], case[1])
     cfg, media, mu, vmax, include, ex = case
-    assert (depth > 0) == tess, depth
+    assert (depth[0] > 0) == tess, depth
+    assert (depth[1] > 16) == tess, depth   # (QCAP 0 with coop_ok: DESIGN §2)
     launches, segments = stats[-1]
     assert launches > 0 and segments == 64 * 64 * SPP, stats
     name = f"M1 {'tessellated' if tess else 'plain'} {sensor}"

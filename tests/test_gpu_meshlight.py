@@ -115,7 +115,8 @@ def test_sampling_bit_for_bit_ml1_and_other_types():
 def _film(cfg, spp):
     g = Renderer(cfg)
     try:
-        depth = g.octree()["depth"]
+        oc = g.octree()
+        depth = oc["depth"], oc["max_queue_groups"]
         g.reset_stats()
         film = g.render_pass(0, spp)
         return film, g.stats(), depth
@@ -127,7 +128,8 @@ def _closed_form(name, case, spp=256, multi_level=None):
     cfg, mu, vmax, include = case
     film, st, depth = _film(cfg, spp)
     if multi_level is not None:
-        assert depth > 0 if multi_level else depth == 0
+        assert depth[0] > 0 if multi_level else depth[0] == 0
+        assert (depth[1] > 16) == multi_level, depth   # (QCAP 0 with coop_ok: DESIGN §2)
     assert st["nee_vertices"] > 0 and st["coop_overflows"] == 0
     rows = ref.compare(film, mu, vmax, include, spp)
     print(f"{name}: max |got - mu| / tol = {ref.deviation(rows):.3f}\n{ref.report(rows)}")

@@ -216,7 +216,8 @@ def _render(cfg, env=None, spans=((0, SPP),)):
     try:
         if env is not None:
             g.set_environment(env)
-        depth = g.octree()["depth"]
+        oc = g.octree()
+        depth = oc["depth"], oc["max_queue_groups"]
         film = None
         for a, b in spans:
             film = g.render_pass(a, b, film)
@@ -241,7 +242,8 @@ def _closed_form(name, case, multi_level=None):
     assert np.all(vmax < 1.0)
     film, depth, launches = _render(cfg, env)
     if multi_level is not None:
-        assert (depth > 0) == multi_level, depth
+        assert (depth[0] > 0) == multi_level, depth
+        assert (depth[1] > 16) == multi_level, depth   # (QCAP 0 with coop_ok: DESIGN §2)
     assert launches > 0
     _check(name, film, mu, vmax, include)
     return film

@@ -234,7 +234,8 @@ def _render(cfg, env=None, spans=((0, SPP),)):
     try:
         if env is not None:
             g.set_environment(env)
-        depth = g.octree()["depth"]
+        oc = g.octree()
+        depth = oc["depth"], oc["max_queue_groups"]
         film = None
         for a, b in spans:
             film = g.render_pass(a, b, film)
@@ -251,7 +252,8 @@ def _closed_form(name, case, multi_level=None):
     assert np.all(vmax < 1.0)
     film, depth, launches = _render(cfg, env)
     if multi_level is not None:
-        assert (depth > 0) == multi_level, depth
+        assert (depth[0] > 0) == multi_level, depth
+        assert (depth[1] > 16) == multi_level, depth   # (QCAP 0 with coop_ok: DESIGN §2)
     assert launches > 0
     rows = ref.compare(film, mu, vmax, include, SPP)
     print(f"\n{name}: |got - mu| / tol = {ref.deviation(rows):.3f}\n{ref.report(rows)}")
